@@ -12,7 +12,13 @@ channels are independent units in the reference); `value` 
 aggregate.  `--pooled` additionally SUM-all-reduces the E-step statistics over RCCL (templates
 pooled across channels -- an extension the reference does not have; off by default).
 
-Launch:  python bench.py --gpus 1 --steps 10 --warmup 3
+A plain run sets up, warms up, times the steps, optionally writes the outputs of the last timed step
+(--dump-outputs DIR) and prints the result line.  --full adds everything else this script measures or
+checks: the per-kernel profile and roofline, certificates from separate decode / E-step calls, the split
+Viterbi / E-step rates, the EM loop, other shapes and channel counts, the overlap decodes and the CPU
+baseline.
+
+Launch:  python bench.py --gpus 1 --steps 10 --warmup 3 [--full] [--dump-outputs DIR]
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
                 --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -29,6 +35,34 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X spec (MI355X_MICROARCH.md); 6290 GB/s measured streaming
+DUMP_BUDGET_BYTES = 60 * 2 ** 20  # --dump-outputs: all ranks' .npy payloads together (64 MB cap, headers included)
+DUMP_SEED = 20240607              # fixed sample of an output too large for its share of the budget
+
+
+def dump_outputs(outdir, arrays, budget, suffix=""):
+    """Write `arrays` (name -> (device tensor, numpy dtype: float32 or float64)) as outdir/<name><suffix>.npy.
+    The smallest arrays go first and each takes at most an even share of what is left; an array that does not
+    fit its share is written as a fixed, seeded sample of its flattened (C-order) entries, with the flat indices
+    of the sample beside it as <name>_index<suffix>.npy (float64)."""
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    items = sorted(arrays.items(), key=lambda kv: kv[1][0].numel())
+    left = budget
+    for i, (name, (t, dtype)) in enumerate(items):
+        share = left // (len(items) - i)
+        item = np.dtype(dtype).itemsize
+        flat = t.detach().reshape(-1)
+        if flat.numel() * item <= share:
+            a = t.detach().cpu().numpy().astype(dtype)
+        else:
+            m = max(1, share // (item + 8))
+            rng = np.random.default_rng(DUMP_SEED)
+            idx = np.unique(rng.integers(0, flat.numel(), size=m, dtype=np.int64))
+            a = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy().astype(dtype)
+            np.save(os.path.join(outdir, name + "_index" + suffix + ".npy"), idx.astype(np.float64))
+            left -= idx.size * 8
+        np.save(os.path.join(outdir, name + suffix + ".npy"), a)
+        left -= a.nbytes
 
 
 def contract_bytes(S, T):
@@ -242,21 +276,28 @@ def run_config45(args, torch, H, dist, world, rank, dev):
         tt = torch.tensor([dt], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-    # certificates and near-ties of every group, after the timed region
-    bad = [0, 0, 0, 0]
-    ties_done = 0
-    for gi, grp in enumerate(groups):
-        pl = plan_for(len(grp))
-        pl.viterbi(ys[gi], xs[gi], lls[gi], stream)
-        d1 = pl.diagnostics(stream)
-        ties_done += pl.tie_stats(stream)["decided"]
-        pl.estep(ys[gi], sts[gi], stream)
-        d2 = pl.diagnostics(stream)
-        bad = [bad[0] + d1[0], bad[1] + d2[3], bad[2] + d2[5], bad[3] + d1[7]]
-    if dist is not None:
-        bt = torch.tensor(bad, dtype=torch.int64, device=dev if args.backend == "nccl" else "cpu")
-        dist.all_reduce(bt)
-        bad = [int(v) for v in bt.tolist()]
+    if args.dump_outputs and groups:
+        # this rank's channels in group order (dist.shard_channels(total, rank, world))
+        dump_outputs(args.dump_outputs,
+                     {"viterbi_path": (torch.cat(xs), np.float32), "viterbi_loglik": (torch.cat(lls), np.float64),
+                      "estep_stats": (torch.cat(sts), np.float64), "mstep_out": (torch.cat(outs), np.float64)},
+                     DUMP_BUDGET_BYTES // world, "_rank%d" % rank if world > 1 else "")
+    if args.full:
+        # certificates and near-ties of every group, after the timed region
+        bad = [0, 0, 0, 0]
+        ties_done = 0
+        for gi, grp in enumerate(groups):
+            pl = plan_for(len(grp))
+            pl.viterbi(ys[gi], xs[gi], lls[gi], stream)
+            d1 = pl.diagnostics(stream)
+            ties_done += pl.tie_stats(stream)["decided"]
+            pl.estep(ys[gi], sts[gi], stream)
+            d2 = pl.diagnostics(stream)
+            bad = [bad[0] + d1[0], bad[1] + d2[3], bad[2] + d2[5], bad[3] + d1[7]]
+        if dist is not None:
+            bt = torch.tensor(bad, dtype=torch.int64, device=dev if args.backend == "nccl" else "cpu")
+            dist.all_reduce(bt)
+            bad = [int(v) for v in bt.tolist()]
     if rank == 0:
         roof, info = None, None
         if groups:
@@ -264,10 +305,11 @@ def run_config45(args, torch, H, dist, world, rank, dev):
             info = pl.info()
             info["ring_len"] = K - 1
             gi = 0
-            roof = shape_roofline(pl, info, N, K, T, len(groups[0]), dt / args.steps / max(1, len(groups)), stream,
-                                  lambda: (pl.bind(ys[gi], stream), pl.viterbi(ys[gi], xs[gi], lls[gi], stream),
-                                           pl.estep(ys[gi], sts[gi], stream), pl.mstep(sts[gi], outs[gi], stream),
-                                           pl.unbind()))
+            if args.full:
+                roof = shape_roofline(pl, info, N, K, T, len(groups[0]), dt / args.steps / max(1, len(groups)), stream,
+                                      lambda: (pl.bind(ys[gi], stream), pl.viterbi(ys[gi], xs[gi], lls[gi], stream),
+                                               pl.estep(ys[gi], sts[gi], stream), pl.mstep(sts[gi], outs[gi], stream),
+                                               pl.unbind()))
         ms = dt / args.steps * 1e3
         res = {
             "metric": "Msamples/sec (Viterbi + forward-backward), K=%d L=%d HMM" % (N, K),
@@ -284,16 +326,20 @@ def run_config45(args, torch, H, dist, world, rank, dev):
                        "engine": "wave", "block": info["block"] if info else None,
                        "halo": info["halo"] if info else None, "seed": 1234,
                        "pooled_allreduce": bool(args.pooled)},
-            "roofline": roof,
-            "detail": {"boundary_check_fails": bad[:3], "near_ties_unresolved": bad[3], "near_ties_resolved_rank0": ties_done,
-                       "workspace_GB": info["workspace_bytes"] / 1e9 if info else None},
-            "valid": bool(bad[0] == 0 and bad[1] == 0 and bad[2] == 0 and bad[3] == 0),
         }
-        if world == 1 and not args.no_cpu_baseline and not args.quick:
-            res["cpu_baseline"] = cpu_baseline(H, N, K, temps, pp, sigma, Tv=50_000 if cfg == 4 else 20_000,
-                                               Tem=12_000 if cfg == 4 else 4_000, reps=1)
+        if args.full:
+            res.update({
+                "roofline": roof,
+                "detail": {"boundary_check_fails": bad[:3], "near_ties_unresolved": bad[3],
+                           "near_ties_resolved_rank0": ties_done,
+                           "workspace_GB": info["workspace_bytes"] / 1e9 if info else None},
+                "valid": bool(bad[0] == 0 and bad[1] == 0 and bad[2] == 0 and bad[3] == 0),
+            })
+            if world == 1 and not args.no_cpu_baseline and not args.quick:
+                res["cpu_baseline"] = cpu_baseline(H, N, K, temps, pp, sigma, Tv=50_000 if cfg == 4 else 20_000,
+                                                   Tem=12_000 if cfg == 4 else 4_000, reps=1)
         print(json.dumps(res))
-        if not res["valid"]:
+        if args.full and not res["valid"]:
             print("bench: certificates failed %s: the line above is INVALID" % (bad,), file=sys.stderr)
     for pl in plans.values():
         pl.close()
@@ -352,23 +398,30 @@ def cpu_baseline(H, N, K, temps, pp, sigma, Tv=100_000, Tem=40_000, reps=4):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: per-kernel profile and roofline, certificates from separate calls, "
+                         "split Viterbi / E-step rates, EM loop, multi-channel and config 4/5 shapes, overlap decodes, "
+                         "CPU baseline (off: a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (decoded path, log-likelihood, E-step statistics, "
+                         "M-step output) as DIR/<name>.npy, float32/float64, at most 64 MB in all")
     ap.add_argument("--samples", type=int, default=10_000_000, help="samples per channel")
     ap.add_argument("--pooled", action="store_true", help="all-reduce E-step statistics (extension)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--time-sharded", action="store_true",
                     help="strong scaling: ONE recording of --samples cut into time shards, one per "
                          "rank, statistics SUM-all-reduced every step (default: one channel per rank)")
     ap.add_argument("--channels", type=int, default=4,
-                    help="extra (untimed) measurement: this many channels per GPU on concurrent streams")
+                    help="with --full, extra (untimed) measurement: this many channels per GPU on concurrent streams")
     ap.add_argument("--separate", action="store_true",
                     help="decode and E-step as two calls instead of hmmsort_plan_decode_estep")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL)")
     ap.add_argument("--neurons", type=int, default=4, help="templates (reference N); 4 = headline")
     ap.add_argument("--states", type=int, default=60, help="states per template (reference K)")
     ap.add_argument("--quick", action="store_true",
-                    help="timed region and per-kernel profile only (no CPU baseline, EM loop, multi-channel, overlap extras): for rocprofv3 runs")
+                    help="with --full: timed region and per-kernel profile only (no CPU baseline, EM loop, multi-channel, overlap extras): for rocprofv3 runs")
     ap.add_argument("--config", type=int, default=2, choices=(2, 4, 5),
                     help="BASELINE config: 2 (default; = 3's model) one 10 M-sample channel per GPU, K=4 L=60; "
                          "4: 64 channels x 10 M samples, K=8 L=128, dealt round-robin over the ranks, 8 channels per "
@@ -380,6 +433,8 @@ def main():
     ap.add_argument("--block", type=int, default=0)
     ap.add_argument("--halo", type=int, default=0)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import hmmsort_amd as H
@@ -467,7 +522,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # ---- per-kernel timing (HIP events on the launch stream; separate, untimed pass) ----
+    # ---- priming pass (untimed); with --full it is the per-kernel timing (HIP events on the launch stream) ----
     # Runs BEFORE the warm-up steps: the first ~15 ms of work on an idle GPU run below its sustained clocks
     # (10 timed steps after 3 warm-up steps: 1.25 ms/step, after 30: 1.18 ms/step), and this pass is untimed anyway.
     # decode and E-step as two calls here: in the timed step their kernels overlap on two streams, which
@@ -477,15 +532,17 @@ def main():
     plan.estep(dy, stats, stream)
     fence()
     nprof = max(1, min(args.steps, 8))
-    plan.profile(True)
+    if args.full:
+        plan.profile(True)
     for _ in range(nprof):
         plan.bind(dy, stream)
         plan.viterbi(dy, dx, dll, stream)
         plan.estep(dy, stats, stream)
         plan.mstep(stats, out, stream)
         plan.unbind()
-    prof = plan.profile_read(stream)
-    plan.profile(False)
+    if args.full:
+        prof = plan.profile_read(stream)
+        plan.profile(False)
 
     for _ in range(args.warmup):
         step()
@@ -499,171 +556,182 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-    # boundary certificates: Viterbi calls fill diag[0..2], E-step calls diag[3..6]
-    plan.viterbi(dy, dx, dll, stream)
-    diag = plan.diagnostics(stream)
-    plan.estep(dy, stats, stream)
-    dE = plan.diagnostics(stream)
-    diag = diag[:3] + dE[3:7] + diag[7:8]
+    if args.dump_outputs:
+        # what a caller of the timed path receives from its last step, before anything below reuses the buffers
+        dump_outputs(args.dump_outputs,
+                     {"viterbi_path": (dx, np.float32), "viterbi_loglik": (dll, np.float64),
+                      "estep_stats": (stats, np.float64), "mstep_out": (out, np.float64)},
+                     DUMP_BUDGET_BYTES // world, "_rank%d" % rank if world > 1 else "")
+    if args.full or args.separate:
+        # boundary certificates: Viterbi calls fill diag[0..2], E-step calls diag[3..6]
+        plan.viterbi(dy, dx, dll, stream)
+        diag = plan.diagnostics(stream)
+        plan.estep(dy, stats, stream)
+        dE = plan.diagnostics(stream)
+        diag = diag[:3] + dE[3:7] + diag[7:8]
+    else:
+        # the last timed step's decode_estep filled both halves itself: read back, no further GPU work
+        diag = plan.diagnostics(stream)
 
-    ksum = {k: v[0] / v[1] for k, v in prof.items()}           # average ms per launch
-    per_step_ms = {k: v[0] / nprof for k, v in prof.items()}   # ms per step (a kernel may launch more than once)
-    dom = max(ksum, key=ksum.get)
-    step_ms_kernels = sum(per_step_ms.values())
-    counters, counters_src = measured_traffic(T, info["block"], N, K) if info["engine"] == H.ENGINE_WAVE else (None, None)
-    model = {k: engine_bytes(k, N, T, info) for k in ksum}
-    dom_counter = counters.get(dom) if counters else None
-    dom_bytes = dom_counter if dom_counter is not None else model.get(dom)
-    bound, peak, unit = "hbm", HBM_PEAK_GBS, "GB/s"
-    achieved = dom_bytes / (ksum[dom] * 1e-3) / 1e9 if dom_bytes else None
-    if dom == "kw_gsum":
-        # the statistics kernel is a Toeplitz matrix product on the fp64 matrix cores: G1/G2[lag][ring] over
-        # all onsets = 2 (G1,G2) x 2 flop x N L T useful flops; fp64 MFMA peak = the fp64 vector rate,
-        # 78.6 TFLOP/s (MI355X_MICROARCH.md: FP32 vector 157.3 TF, fp64 at half rate)
-        bound, peak, unit = "mfma", 78.6, "TFLOP/s"
-        achieved = 4.0 * N * (K - 1) * T / (ksum[dom] * 1e-3) / 1e12
-    # the fused backward sweep (3-4 rings, <= 64 states) is not bound by one pipe: besides its HBM streams it
-    # issues the statistics product on the fp64 matrix cores and ~60 k vector instructions per wave
-    other_roofs = None
-    if dom == "kw_bwd" and info["engine"] == H.ENGINE_WAVE and N in (3, 4) and K - 1 <= 64:
-        other_roofs = {"mfma_fp64": {"achieved": 2.0 * N * (K - 1) * T / (ksum[dom] * 1e-3) / 1e12, "peak": 78.6,
-                                     "unit": "TFLOP/s (useful flops of G1)"}}
-        raw = measured_traffic.raw
-        if counters and raw and raw.get(dom, {}).get("valu_insts_per_wave"):
-            lane_ops = raw[dom]["valu_insts_per_wave"] * 64.0 * info["nchains"]
-            other_roofs["valu_fp64"] = {"achieved": lane_ops / ksum[dom] / 1e9, "peak": 35.0,
-                                        "unit": "G lane-instructions per ms (peak measured: scripts/micro/fma_probe.hip)"}
-        for v in other_roofs.values():
-            v["frac"] = v["achieved"] / v["peak"]
-    step_bytes_model = sum(v for v in model.values() if v)
-    step_bytes_counters = (sum(counters.get(k, 0.0) * prof[k][1] / nprof for k in ksum) if counters else None)
+    if args.full:
+        ksum = {k: v[0] / v[1] for k, v in prof.items()}           # average ms per launch
+        per_step_ms = {k: v[0] / nprof for k, v in prof.items()}   # ms per step (a kernel may launch more than once)
+        dom = max(ksum, key=ksum.get)
+        step_ms_kernels = sum(per_step_ms.values())
+        counters, counters_src = measured_traffic(T, info["block"], N, K) if info["engine"] == H.ENGINE_WAVE else (None, None)
+        model = {k: engine_bytes(k, N, T, info) for k in ksum}
+        dom_counter = counters.get(dom) if counters else None
+        dom_bytes = dom_counter if dom_counter is not None else model.get(dom)
+        bound, peak, unit = "hbm", HBM_PEAK_GBS, "GB/s"
+        achieved = dom_bytes / (ksum[dom] * 1e-3) / 1e9 if dom_bytes else None
+        if dom == "kw_gsum":
+            # the statistics kernel is a Toeplitz matrix product on the fp64 matrix cores: G1/G2[lag][ring] over
+            # all onsets = 2 (G1,G2) x 2 flop x N L T useful flops; fp64 MFMA peak = the fp64 vector rate,
+            # 78.6 TFLOP/s (MI355X spec: FP32 vector 157.3 TF, fp64 at half rate)
+            bound, peak, unit = "mfma", 78.6, "TFLOP/s"
+            achieved = 4.0 * N * (K - 1) * T / (ksum[dom] * 1e-3) / 1e12
+        # the fused backward sweep (3-4 rings, <= 64 states) is not bound by one pipe: besides its HBM streams it
+        # issues the statistics product on the fp64 matrix cores and ~60 k vector instructions per wave
+        other_roofs = None
+        if dom == "kw_bwd" and info["engine"] == H.ENGINE_WAVE and N in (3, 4) and K - 1 <= 64:
+            other_roofs = {"mfma_fp64": {"achieved": 2.0 * N * (K - 1) * T / (ksum[dom] * 1e-3) / 1e12, "peak": 78.6,
+                                         "unit": "TFLOP/s (useful flops of G1)"}}
+            raw = measured_traffic.raw
+            if counters and raw and raw.get(dom, {}).get("valu_insts_per_wave"):
+                lane_ops = raw[dom]["valu_insts_per_wave"] * 64.0 * info["nchains"]
+                other_roofs["valu_fp64"] = {"achieved": lane_ops / ksum[dom] / 1e9, "peak": 35.0,
+                                            "unit": "G lane-instructions per ms (peak measured: scripts/micro/fma_probe.hip)"}
+            for v in other_roofs.values():
+                v["frac"] = v["achieved"] / v["peak"]
+        step_bytes_model = sum(v for v in model.values() if v)
+        step_bytes_counters = (sum(counters.get(k, 0.0) * prof[k][1] / nprof for k in ksum) if counters else None)
 
-    # split timings (untimed region): Viterbi only / E-step only
-    def timed(fn, n=3):
-        fence()
-        t = time.perf_counter()
-        for _ in range(n):
-            fn()
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t) / n
-    plan.unbind()
-    t_vit = timed(lambda: plan.viterbi(dy, dx, dll, stream))       # each incl. its own pre-pass
-    t_est = timed(lambda: (plan.estep(dy, stats, stream), plan.mstep(stats, out, stream)))
+        # split timings (untimed region): Viterbi only / E-step only
+        def timed(fn, n=3):
+            fence()
+            t = time.perf_counter()
+            for _ in range(n):
+                fn()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t) / n
+        plan.unbind()
+        t_vit = timed(lambda: plan.viterbi(dy, dx, dll, stream))       # each incl. its own pre-pass
+        t_est = timed(lambda: (plan.estep(dy, stats, stream), plan.mstep(stats, out, stream)))
 
-    # ---- BASELINE config 3: full Baum-Welch EM, 10 iterations, device-resident (untimed extra) ----
-    # every iteration = E-step + M-step on the GPU, then the host part the reference also has:
-    # read back mu/sigma/lp (K*N+1+N doubles), rebuild the transition list, upload the new model
-    def em_iterations(n_iter=10):
-        rng = np.random.default_rng(7)
-        sig0 = float(np.std(y, ddof=1))
-        mu0 = np.ones((K, N), order="F")
-        for i in range(N):  # the reference's random start, baumwelch.jl:311-322
-            mu0[:, i] = H.create_spike_template(K, 3 * sig0 * rng.random(), 0.5 + 0.1 * rng.standard_normal(),
-                                                1.5 * rng.random())
-        mu0[0, :] = 0.0
-        sm_i = H.StateMatrix.create(N, K, np.log(np.full(N, 2.0 ** (-3 * K / 2))), False)
-        em = H.Plan(T, sm_i, mu0, sig0)
-        torch.cuda.synchronize()
-        t = time.perf_counter()
-        for _ in range(n_iter):
-            em.estep(dy, stats, stream)
-            em.mstep(stats, out, stream)
-            o = out.cpu().numpy()
-            mu_i = np.asfortranarray(o[:K * N].reshape((K, N), order="F"))
-            sm_i = H.StateMatrix.from_states(sm_i.states, o[K * N + 1 + N:], K, o[K * N + 1:K * N + 1 + N], False)
-            em.set_model(sm_i, mu_i, float(o[K * N]))
-        torch.cuda.synchronize()
-        per = (time.perf_counter() - t) / n_iter
-        em.close()
-        return per * 1e3, float(o[K * N])
-    try:
-        em_ms, em_sigma = em_iterations() if not (args.time_sharded or args.quick) else (None, None)
-    except H.HmmsortError as exc:
-        # a template whose firing probability reaches 0 loses its entry transitions (the reference
-        # keeps finite entries only, types.jl:121): the list length changes and the plan must be
-        # rebuilt by the host, which this fixed-shape loop does not do
-        em_ms, em_sigma = None, "stopped: %s" % exc
+        # ---- BASELINE config 3: full Baum-Welch EM, 10 iterations, device-resident (untimed extra) ----
+        # every iteration = E-step + M-step on the GPU, then the host part the reference also has:
+        # read back mu/sigma/lp (K*N+1+N doubles), rebuild the transition list, upload the new model
+        def em_iterations(n_iter=10):
+            rng = np.random.default_rng(7)
+            sig0 = float(np.std(y, ddof=1))
+            mu0 = np.ones((K, N), order="F")
+            for i in range(N):  # the reference's random start, baumwelch.jl:311-322
+                mu0[:, i] = H.create_spike_template(K, 3 * sig0 * rng.random(), 0.5 + 0.1 * rng.standard_normal(),
+                                                    1.5 * rng.random())
+            mu0[0, :] = 0.0
+            sm_i = H.StateMatrix.create(N, K, np.log(np.full(N, 2.0 ** (-3 * K / 2))), False)
+            em = H.Plan(T, sm_i, mu0, sig0)
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            for _ in range(n_iter):
+                em.estep(dy, stats, stream)
+                em.mstep(stats, out, stream)
+                o = out.cpu().numpy()
+                mu_i = np.asfortranarray(o[:K * N].reshape((K, N), order="F"))
+                sm_i = H.StateMatrix.from_states(sm_i.states, o[K * N + 1 + N:], K, o[K * N + 1:K * N + 1 + N], False)
+                em.set_model(sm_i, mu_i, float(o[K * N]))
+            torch.cuda.synchronize()
+            per = (time.perf_counter() - t) / n_iter
+            em.close()
+            return per * 1e3, float(o[K * N])
+        try:
+            em_ms, em_sigma = em_iterations() if not (args.time_sharded or args.quick) else (None, None)
+        except H.HmmsortError as exc:
+            # a template whose firing probability reaches 0 loses its entry transitions (the reference
+            # keeps finite entries only, types.jl:121): the list length changes and the plan must be
+            # rebuilt by the host, which this fixed-shape loop does not do
+            em_ms, em_sigma = None, "stopped: %s" % exc
 
-    # ---- several channels per GPU through ONE batched plan (hmmsort_plan_create_batched: chains =
-    # channels x chains per channel, per-channel models; the shape of BASELINE config 4's per-GPU share;
-    # untimed extra, reported in detail only) ----
-    def multi_channel(nchan, Nc=N, Kc=K, Tc=T, steps=3):
-        if (Nc, Kc) == (N, K):
-            tm, ppc, smc = temps, pp, sm
-        else:
-            tm = np.asfortranarray(np.stack([H.create_spike_template(Kc, *amps_for(Nc)[i]) for i in range(Nc)], 1))
-            ppc = [[0.003, 0.001, 0.002, 0.0015][i % 4] * (60.0 / Kc) for i in range(Nc)]
-            smc = H.StateMatrix.create(Nc, Kc, np.log(ppc), False)
-        pl = H.Plan.batched(Tc, [smc] * nchan, [tm] * nchan, [sigma] * nchan)
-        yy = torch.empty((nchan, Tc), dtype=torch.float64, device=dev)
-        for ch in range(nchan):
-            yy[ch] = torch.from_numpy(H.create_signal(Tc, sigma, ppc, tm, seed=seed + 100 + ch)).to(dev)
-        xx = torch.zeros((nchan, Tc), dtype=torch.int16, device=dev)
-        ll_ = torch.zeros(nchan, dtype=torch.float64, device=dev)
-        ss = torch.zeros((nchan, pl.stats_len()), dtype=torch.float64, device=dev)
-        oo = torch.zeros((nchan, pl.mstep_len()), dtype=torch.float64, device=dev)
-        def go():
-            pl.bind(yy, stream); pl.decode_estep(yy, xx, ll_, ss, stream); pl.mstep(ss, oo, stream); pl.unbind()
-        go(); torch.cuda.synchronize()
-        t = time.perf_counter()
-        for _ in range(steps):
-            go()
-        torch.cuda.synchronize()
-        per = (time.perf_counter() - t) / steps
-        dg = pl.diagnostics(stream)
-        io = pl.info()
-        io["ring_len"] = Kc - 1
-        roof = shape_roofline(pl, io, Nc, Kc, Tc, nchan, per, stream,
-                              lambda: (pl.bind(yy, stream), pl.viterbi(yy, xx, ll_, stream), pl.estep(yy, ss, stream),
-                                       pl.mstep(ss, oo, stream), pl.unbind())) if (Nc, Kc) != (N, K) else None
-        ties = pl.tie_stats(stream)
-        pl.close()
-        return {"channels_per_gpu": nchan, "model": "N=%d K=%d" % (Nc, Kc), "samples_per_channel": Tc,
-                "Msamples_s": nchan * Tc / per / 1e6, "ms_per_step": per * 1e3, "block": io["block"],
-                "chains": io["nchains"], "boundary_check_fails": [dg[0], dg[3], dg[5]], "near_ties_unresolved": dg[7],
-                "near_ties_resolved": ties["decided"], "workspace_GB": io["workspace_bytes"] / 1e9, "roofline": roof}
+        # ---- several channels per GPU through ONE batched plan (hmmsort_plan_create_batched: chains =
+        # channels x chains per channel, per-channel models; the shape of BASELINE config 4's per-GPU share;
+        # untimed extra, reported in detail only) ----
+        def multi_channel(nchan, Nc=N, Kc=K, Tc=T, steps=3):
+            if (Nc, Kc) == (N, K):
+                tm, ppc, smc = temps, pp, sm
+            else:
+                tm = np.asfortranarray(np.stack([H.create_spike_template(Kc, *amps_for(Nc)[i]) for i in range(Nc)], 1))
+                ppc = [[0.003, 0.001, 0.002, 0.0015][i % 4] * (60.0 / Kc) for i in range(Nc)]
+                smc = H.StateMatrix.create(Nc, Kc, np.log(ppc), False)
+            pl = H.Plan.batched(Tc, [smc] * nchan, [tm] * nchan, [sigma] * nchan)
+            yy = torch.empty((nchan, Tc), dtype=torch.float64, device=dev)
+            for ch in range(nchan):
+                yy[ch] = torch.from_numpy(H.create_signal(Tc, sigma, ppc, tm, seed=seed + 100 + ch)).to(dev)
+            xx = torch.zeros((nchan, Tc), dtype=torch.int16, device=dev)
+            ll_ = torch.zeros(nchan, dtype=torch.float64, device=dev)
+            ss = torch.zeros((nchan, pl.stats_len()), dtype=torch.float64, device=dev)
+            oo = torch.zeros((nchan, pl.mstep_len()), dtype=torch.float64, device=dev)
+            def go():
+                pl.bind(yy, stream); pl.decode_estep(yy, xx, ll_, ss, stream); pl.mstep(ss, oo, stream); pl.unbind()
+            go(); torch.cuda.synchronize()
+            t = time.perf_counter()
+            for _ in range(steps):
+                go()
+            torch.cuda.synchronize()
+            per = (time.perf_counter() - t) / steps
+            dg = pl.diagnostics(stream)
+            io = pl.info()
+            io["ring_len"] = Kc - 1
+            roof = shape_roofline(pl, io, Nc, Kc, Tc, nchan, per, stream,
+                                  lambda: (pl.bind(yy, stream), pl.viterbi(yy, xx, ll_, stream), pl.estep(yy, ss, stream),
+                                           pl.mstep(ss, oo, stream), pl.unbind())) if (Nc, Kc) != (N, K) else None
+            ties = pl.tie_stats(stream)
+            pl.close()
+            return {"channels_per_gpu": nchan, "model": "N=%d K=%d" % (Nc, Kc), "samples_per_channel": Tc,
+                    "Msamples_s": nchan * Tc / per / 1e6, "ms_per_step": per * 1e3, "block": io["block"],
+                    "chains": io["nchains"], "boundary_check_fails": [dg[0], dg[3], dg[5]], "near_ties_unresolved": dg[7],
+                    "near_ties_resolved": ties["decided"], "workspace_GB": io["workspace_bytes"] / 1e9, "roofline": roof}
 
-    def amps_for(Nc):
-        base_ = [(3.0, 0.8, 0.2), (4.0, 0.3, 0.2), (2.5, 0.6, 0.25), (3.5, 0.5, 0.15)]
-        return [(base_[i % 4][0] * (1 + 0.13 * (i // 4)), base_[i % 4][1] + 0.03 * (i // 4), base_[i % 4][2])
-                for i in range(Nc)]
-    extras = args.channels > 1 and not args.time_sharded and not args.quick and world == 1
-    mc = multi_channel(args.channels) if extras else None
-    # BASELINE config 4 (per-GPU share: 8 channels x 10 M, N=8, K=128) and config 5 (N=16, K=256; one
-    # 40 M-sample channel here, the 100 M-sample run is tests/test_gpu_configs.py) -- untimed extras
-    cfg4 = multi_channel(8, 8, 128, 10_000_000, steps=2) if (extras and (N, K) == (4, 60)) else None
-    cfg5 = multi_channel(1, 16, 256, 40_000_000, steps=2) if (extras and (N, K) == (4, 60)) else None
+        def amps_for(Nc):
+            base_ = [(3.0, 0.8, 0.2), (4.0, 0.3, 0.2), (2.5, 0.6, 0.25), (3.5, 0.5, 0.15)]
+            return [(base_[i % 4][0] * (1 + 0.13 * (i // 4)), base_[i % 4][1] + 0.03 * (i // 4), base_[i % 4][2])
+                    for i in range(Nc)]
+        extras = args.channels > 1 and not args.time_sharded and not args.quick and world == 1
+        mc = multi_channel(args.channels) if extras else None
+        # BASELINE config 4 (per-GPU share: 8 channels x 10 M, N=8, K=128) and config 5 (N=16, K=256; one
+        # 40 M-sample channel here, the 100 M-sample run is tests/test_gpu_configs.py) -- untimed extras
+        cfg4 = multi_channel(8, 8, 128, 10_000_000, steps=2) if (extras and (N, K) == (4, 60)) else None
+        cfg5 = multi_channel(1, 16, 256, 40_000_000, steps=2) if (extras and (N, K) == (4, 60)) else None
 
-    # ---- overlap-resolving decode: the reference's own Viterbi-test model,
-    # test/runtests.jl:17-34 -- 2 templates, K=60, allow_overlaps=true, 3600 states -- through the
-    # blocked engine, device-resident (untimed extra, rank 0 of a 1-GPU run only) ----
-    def overlap_decode(To=10_000_000, No=2):
-        Ko = 60
-        shapes = [(3.0, 0.8, 0.2), (4.0, 0.3, 0.2), (2.5, 0.6, 0.25), (3.5, 0.5, 0.15)]
-        t2 = np.asfortranarray(np.stack([H.create_spike_template(Ko, *shapes[i]) for i in range(No)], 1))
-        ppo = [0.003, 0.001, 0.002, 0.0015][:No]
-        smo = H.StateMatrix.create(No, Ko, np.log(ppo), True)
-        yo = torch.from_numpy(H.create_signal(To, sigma, ppo, t2, seed=seed + 7)).to(dev)
-        xo = torch.zeros(To, dtype=torch.int16, device=dev)
-        po = H.Plan(To, smo, t2, sigma)
-        io = po.info()
-        po.viterbi(yo, xo, dll, stream); torch.cuda.synchronize()
-        t = time.perf_counter()
-        for _ in range(3):
-            po.viterbi(yo, xo, dll, stream)
-        torch.cuda.synchronize()
-        per = (time.perf_counter() - t) / 3
-        d = po.diagnostics(stream)
-        po.close()
-        sweep = ("pair sweep: pair runs as delays, lanes = phases" if No == 2 else
-                 "multi sweep: one wavefront per template, pair runs as delays, compressed entry FIFOs")
-        return {"model": "N=%d K=%d allow_overlaps=true, %d states" % (No, Ko, smo.nstates), "samples": To,
-                "engine": {1: "strict", 2: "ring", 3: "blocked (%s)" % sweep}.get(io["engine"], io["engine"]),
-                "block": io["block"], "halo": io["halo"], "Msamples_s": To / per / 1e6,
-                "boundary_check_fails": d[0], "max_boundary_spread": d[2], "near_ties_on_path": d[7]}
-    ov = overlap_decode() if (rank == 0 and world == 1 and not args.quick) else None
-    # the largest model the reference's CLI builds (hmmsort.jl:50-54): 4 templates, 21 123 states
-    ov4 = overlap_decode(10_000_000, 4) if (rank == 0 and world == 1 and not args.quick) else None
+        # ---- overlap-resolving decode: the reference's own Viterbi-test model,
+        # test/runtests.jl:17-34 -- 2 templates, K=60, allow_overlaps=true, 3600 states -- through the
+        # blocked engine, device-resident (untimed extra, rank 0 of a 1-GPU run only) ----
+        def overlap_decode(To=10_000_000, No=2):
+            Ko = 60
+            shapes = [(3.0, 0.8, 0.2), (4.0, 0.3, 0.2), (2.5, 0.6, 0.25), (3.5, 0.5, 0.15)]
+            t2 = np.asfortranarray(np.stack([H.create_spike_template(Ko, *shapes[i]) for i in range(No)], 1))
+            ppo = [0.003, 0.001, 0.002, 0.0015][:No]
+            smo = H.StateMatrix.create(No, Ko, np.log(ppo), True)
+            yo = torch.from_numpy(H.create_signal(To, sigma, ppo, t2, seed=seed + 7)).to(dev)
+            xo = torch.zeros(To, dtype=torch.int16, device=dev)
+            po = H.Plan(To, smo, t2, sigma)
+            io = po.info()
+            po.viterbi(yo, xo, dll, stream); torch.cuda.synchronize()
+            t = time.perf_counter()
+            for _ in range(3):
+                po.viterbi(yo, xo, dll, stream)
+            torch.cuda.synchronize()
+            per = (time.perf_counter() - t) / 3
+            d = po.diagnostics(stream)
+            po.close()
+            sweep = ("pair sweep: pair runs as delays, lanes = phases" if No == 2 else
+                     "multi sweep: one wavefront per template, pair runs as delays, compressed entry FIFOs")
+            return {"model": "N=%d K=%d allow_overlaps=true, %d states" % (No, Ko, smo.nstates), "samples": To,
+                    "engine": {1: "strict", 2: "ring", 3: "blocked (%s)" % sweep}.get(io["engine"], io["engine"]),
+                    "block": io["block"], "halo": io["halo"], "Msamples_s": To / per / 1e6,
+                    "boundary_check_fails": d[0], "max_boundary_spread": d[2], "near_ties_on_path": d[7]}
+        ov = overlap_decode() if (rank == 0 and world == 1 and not args.quick) else None
+        # the largest model the reference's CLI builds (hmmsort.jl:50-54): 4 templates, 21 123 states
+        ov4 = overlap_decode(10_000_000, 4) if (rank == 0 and world == 1 and not args.quick) else None
 
     ms = dt / args.steps * 1e3
     if rank == 0:
@@ -683,38 +751,42 @@ def main():
                        "engine": engine_name, "block": info["block"], "halo": info["halo"],
                        "chains": info["nchains"], "seed": 1234, "pooled_allreduce": bool(args.pooled),
                        "time_sharded": bool(args.time_sharded)},
-            "roofline": {"bound": bound, "kernel": dom, "achieved": achieved, "peak": peak,
-                         "unit": unit, "frac": (achieved / peak) if achieved else None,
-                         "traffic": dom_counter,
-                         "traffic_source": counters_src if dom_counter is not None else
-                         "none committed for these kernel sources: achieved/frac use the engine's design bytes",
-                         "traffic_model": model.get(dom),
-                         "avg_launch_ms": ksum[dom],
-                         "frac_contract": contract_bytes(S, T) / (dt / args.steps) / 1e9 / HBM_PEAK_GBS,
-                         "other_roofs": other_roofs,
-                         "step": {"ms": ms, "bytes_model": step_bytes_model, "bytes_counters": step_bytes_counters,
-                                  "frac": (step_bytes_counters or step_bytes_model) / (dt / args.steps) / 1e9 / HBM_PEAK_GBS},
-                         "note": "frac = HBM bytes of the dominant kernel per launch (rocprofv3 FETCH_SIZE x2 + "
-                                 "WRITE_SIZE of a committed profile of these exact kernel sources, else the bytes "
-                                 "the kernel moves by design) / its HIP-event launch time / 8 TB/s; step.frac = "
-                                 "the same over all kernels of one step and the wall time per step; "
-                                 "frac_contract = SURVEY 8(d) trellis-materialising bytes (18 S + 28 per sample) "
-                                 "/ step time / peak: > 1 because no engine here writes the trellis; other_roofs = "
-                                 "the dominant kernel against the pipes it also loads (fused backward sweep)"},
-            "detail": {"viterbi_Msamples_s": T / t_vit / 1e6, "estep_Msamples_s": T / t_est / 1e6,
-                       "kernel_ms": {k: round(v, 4) for k, v in sorted(ksum.items(), key=lambda kv: -kv[1])},
-                       "sum_kernel_ms_per_step": step_ms_kernels,
-                       "em_iteration_ms": em_ms, "em_sigma_after_10": em_sigma,
-                       "multi_channel": mc, "config4_share": cfg4, "config5_shape": cfg5,
-                       "overlap_decode": ov, "overlap_decode_4_templates": ov4,
-                       "diag": diag[:7], "workspace_GB": info["workspace_bytes"] / 1e9,
-                       "near_ties": plan.tie_stats(stream)},
         }
-        if world == 1 and not args.no_cpu_baseline and not args.quick:
-            res["cpu_baseline"] = cpu_baseline(H, N, K, temps, pp, sigma)
+        if args.full:
+            res.update({
+                "roofline": {"bound": bound, "kernel": dom, "achieved": achieved, "peak": peak,
+                             "unit": unit, "frac": (achieved / peak) if achieved else None,
+                             "traffic": dom_counter,
+                             "traffic_source": counters_src if dom_counter is not None else
+                             "none committed for these kernel sources: achieved/frac use the engine's design bytes",
+                             "traffic_model": model.get(dom),
+                             "avg_launch_ms": ksum[dom],
+                             "frac_contract": contract_bytes(S, T) / (dt / args.steps) / 1e9 / HBM_PEAK_GBS,
+                             "other_roofs": other_roofs,
+                             "step": {"ms": ms, "bytes_model": step_bytes_model, "bytes_counters": step_bytes_counters,
+                                      "frac": (step_bytes_counters or step_bytes_model) / (dt / args.steps) / 1e9 / HBM_PEAK_GBS},
+                             "note": "frac = HBM bytes of the dominant kernel per launch (rocprofv3 FETCH_SIZE x2 + "
+                                     "WRITE_SIZE of a committed profile of these exact kernel sources, else the bytes "
+                                     "the kernel moves by design) / its HIP-event launch time / 8 TB/s; step.frac = "
+                                     "the same over all kernels of one step and the wall time per step; "
+                                     "frac_contract = SURVEY 8(d) trellis-materialising bytes (18 S + 28 per sample) "
+                                     "/ step time / peak: > 1 because no engine here writes the trellis; other_roofs = "
+                                     "the dominant kernel against the pipes it also loads (fused backward sweep)"},
+                "detail": {"viterbi_Msamples_s": T / t_vit / 1e6, "estep_Msamples_s": T / t_est / 1e6,
+                           "kernel_ms": {k: round(v, 4) for k, v in sorted(ksum.items(), key=lambda kv: -kv[1])},
+                           "sum_kernel_ms_per_step": step_ms_kernels,
+                           "em_iteration_ms": em_ms, "em_sigma_after_10": em_sigma,
+                           "multi_channel": mc, "config4_share": cfg4, "config5_shape": cfg5,
+                           "overlap_decode": ov, "overlap_decode_4_templates": ov4,
+                           "diag": diag[:7], "workspace_GB": info["workspace_bytes"] / 1e9,
+                           "near_ties": plan.tie_stats(stream)},
+            })
+            if world == 1 and not args.no_cpu_baseline and not args.quick:
+                res["cpu_baseline"] = cpu_baseline(H, N, K, temps, pp, sigma)
         # a step whose chain boundaries are not all certified is not a measurement of the metric
         res["valid"] = bool(diag[0] == 0 and diag[3] == 0 and diag[5] == 0)
-        res["detail"]["near_ties_on_path"] = diag[7] if len(diag) > 7 else None
+        if args.full:
+            res["detail"]["near_ties_on_path"] = diag[7] if len(diag) > 7 else None
         print(json.dumps(res))
         if not res["valid"]:
             print("bench: boundary certificates failed (diag %s): the line above is INVALID" % (diag,), file=sys.stderr)

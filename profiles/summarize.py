@@ -84,7 +84,7 @@ def main():
             d["valu_insts_per_wave"] = round(sq["SQ_INSTS_VALU"].get(name, 0) / max(1.0, sq["SQ_WAVES"].get(name, 1)), 1)
         out[name] = d
     meta = {"kernel_sources": kernel_sources_hash(),
-            "command": "scripts/profile_bench.sh %s (python3 bench.py --quick --steps 5 --warmup 2 ...)" % tag}
+            "command": "scripts/profile_bench.sh %s (python3 bench.py --full --quick --steps 5 --warmup 2 ...)" % tag}
     if len(sys.argv) >= 6:
         meta.update(samples=int(sys.argv[3]), block=int(sys.argv[4]), halo=int(sys.argv[5]))
     if len(sys.argv) >= 9:   # model shape and channels per plan (default: the headline's 4 x 60, one channel)

@@ -9,7 +9,7 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="$ROOT/bench.py --quick --steps 5 --warmup 2 $@"
+ARGS="$ROOT/bench.py --full --quick --steps 5 --warmup 2 $@"
 rocprofv3 --kernel-trace --stats -d $OUT/trace -o b --output-format csv -- python3 $ARGS > $OUT/trace.log 2>&1
 rocprofv3 --pmc FETCH_SIZE -d $OUT/pmc_fetch -o b --output-format csv -- python3 $ARGS > $OUT/fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE -d $OUT/pmc_write -o b --output-format csv -- python3 $ARGS > $OUT/write.log 2>&1

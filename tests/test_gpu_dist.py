@@ -36,7 +36,7 @@ def _bench_line(p):
 
 @pytest.mark.parametrize("mode", ["config4_pooled", "config4", "config5", "time_sharded"])
 def test_bench_multi_gpu_modes_two_ranks(mode):
-    common = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--backend", "gloo", "--quick"]
+    common = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--backend", "gloo", "--full", "--quick"]
     if mode.startswith("config4"):
         args = ["--config", "4", "--total-channels", "4", "--batch", "2", "--samples", "400000"]
         if mode.endswith("pooled"):
