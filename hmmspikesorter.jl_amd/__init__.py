@@ -7,9 +7,9 @@ import it through the root-level shim:  `import hmmsort_amd`.
 from . import _lib, dist, synth
 from ._lib import (ENGINE_AUTO, ENGINE_BLOCKED, ENGINE_RING, ENGINE_STRICT, ENGINE_WAVE, HmmsortError, device_count,
                    get_option, set_option, shutdown)
-from .api import (HMMSpikeTemplateModel, HMMSpikingModel, StateMatrix, backward, extract_spiketimes,
+from .api import (HMMSpikeTemplateModel, HMMSpikingModel, Posteriors, StateMatrix, backward, extract_spiketimes,
                   fit, forward,
-                  predict, reconstruct_signal, train_model, train_step, unroll_mlseq, update,
+                  posterior_decode, posteriors, predict, reconstruct_signal, spike_confidence, train_model, train_step, unroll_mlseq, update,
                   viterbi)
 from .device import Plan
 from .postprocess import (condense_candidates, condense_templates, find_best_overlap, match_templates,
@@ -23,4 +23,4 @@ __all__ = ["StateMatrix", "HMMSpikeTemplateModel", "HMMSpikingModel", "forward",
            "set_option", "get_option", "shutdown", "device_count", "ENGINE_AUTO", "ENGINE_STRICT",
            "ENGINE_RING", "ENGINE_BLOCKED", "ENGINE_WAVE", "get_lp", "sort_data", "find_best_overlap",
            "condense_candidates", "condense_templates", "remove_sparse", "remove_small", "prune_templates",
-           "match_templates"]
+           "match_templates", "Posteriors", "posteriors", "posterior_decode", "spike_confidence"]

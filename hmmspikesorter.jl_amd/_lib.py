@@ -76,6 +76,12 @@ SIGNATURES = {
     "hmmsort_plan_extract_spiketimes": (_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
     "hmmsort_plan_reconstruct": (_int, [_vp, _vp, _vp, _vp]),
     "hmmsort_plan_unroll_mlseq": (_int, [_vp, _vp, _vp, _vp]),
+    "hmmsort_plan_posteriors": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hmmsort_plan_posterior_decode": (_int, [_vp, _vp, _vp]),
+    "hmmsort_plan_spike_confidence": (_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "hmmsort_plan_expected_counts": (_int, [_vp, _vp, _vp]),
+    "hmmsort_posteriors": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _f64, _vp, _vp, _vp, _vp,
+                                  _vp]),
     "hmmsort_plan_profile": (_int, [_vp, _int]),
     "hmmsort_plan_profile_read": (_int, [_vp, _vp, C.c_char_p, _i64, C.POINTER(_f64), _pi64, _i64,
                                          _pi64]),

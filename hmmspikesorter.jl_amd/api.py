@@ -13,6 +13,7 @@ Reference methods mirrored (file:line relative to the reference root):
   reconstruct_signal                                                  src/reconstruction.jl:1
   unroll_mlseq                                                        src/extraction.jl:4
   fit(HMMSpikingModel, templates, X, chunksize)                       src/fit.jl:11-42
+Extensions (no counterpart in the reference): posteriors, posterior_decode, spike_confidence.
 """
 import ctypes as C
 from dataclasses import dataclass
@@ -436,3 +437,76 @@ def extract_spiketimes(model):
         if counts.max(initial=0) <= cap:
             return [times[i, :counts[i]].copy() for i in range(lA.N)]
         cap = int(counts.max())
+
+
+@dataclass
+class Posteriors:
+    """Smoothed state posteriors gamma_t(s) = P(state s at sample t | whole recording), reduced per template
+    (INTEGRATION.md "Posteriors"; the reference keeps the decoded path only)."""
+    onset: np.ndarray    # N x T: template a at its first phase (states[a, s] == 2)
+    occ: np.ndarray      # N x T: template a mid-spike (states[a, s] > 1)
+    silent: np.ndarray   # T: state 1
+    logz: float          # log-likelihood of the recording
+
+
+def _posteriors_host(y, lA, mu, sigma, want_xm, want_marginals=True):
+    y = _signal(y)
+    keep, margs = _model_args(lA, mu, sigma)
+    T = len(y)
+    onset = np.zeros((lA.N, T)) if want_marginals else None
+    occ = np.zeros((lA.N, T)) if want_marginals else None
+    silent = np.zeros(T) if want_marginals else None
+    xm = np.zeros(T, dtype=np.int16) if want_xm else None
+    logz = np.zeros(1)
+    check(lib().hmmsort_posteriors(ptr(y), T, *margs, ptr(onset), ptr(occ), ptr(silent), ptr(xm), ptr(logz)))
+    return onset, occ, silent, xm, float(logz[0])
+
+
+def posteriors(y, lA, mu, sigma):
+    """posteriors(y, lA, mu, sigma) -> Posteriors.  Ring models (no overlaps, up to 16 templates) run on the wave
+    engine; any other model on the strict engine from materialised alpha/beta (2 x S x T doubles on the
+    device: short signals only)."""
+    onset, occ, silent, _, logz = _posteriors_host(y, lA, mu, sigma, False)
+    return Posteriors(onset, occ, silent, logz)
+
+
+def posterior_decode(y, lA, mu, sigma):
+    """Maximum-posterior-marginal decode: x[t] = arg max_s gamma_t(s), 1-based like viterbi's path, ties to the
+    lower state number."""
+    return _posteriors_host(y, lA, mu, sigma, True, False)[3]
+
+
+def _posterior_plan(T, lA, mu, sigma):
+    """a plan that serves posteriors: the wave engine when it takes the model, else the strict engine"""
+    from .device import Plan
+    plan = Plan(T, lA, mu, sigma)
+    if plan.info()["engine"] in (_lib.ENGINE_WAVE, _lib.ENGINE_STRICT):
+        return plan
+    plan.close()
+    prev = _lib.get_option("engine")
+    _lib.set_option("engine", _lib.ENGINE_STRICT)
+    try:
+        return Plan(T, lA, mu, sigma)
+    finally:
+        _lib.set_option("engine", prev)
+
+
+def spike_confidence(model, jitter=2):
+    """spike_confidence(model::HMMSpikingModel, jitter=2) -> per template (times, confidence), aligned element for
+    element with extract_spiketimes(model): the posterior probability that the template fired (was in its trough
+    state) within +-jitter samples of where the decoded path put the spike."""
+    import torch
+    tm = model.template_model
+    y = np.ascontiguousarray(model.y, dtype=np.float64)
+    x = np.ascontiguousarray(model.ml_seq, dtype=np.int16)
+    plan = _posterior_plan(len(y), tm.state_matrix, tm.mu, tm.sigma)
+    try:
+        dy, dx = torch.from_numpy(y).cuda(), torch.from_numpy(x).cuda()
+        plan.posteriors(dy)
+        d = plan.diagnostics()
+        if d[3] != 0 or d[5] != 0:
+            raise HmmsortError(_lib.ENOCONV, "spike_confidence: %d chain boundaries fail the warm-up check; set "
+                               "option \"halo\" wider" % (d[3] + d[5]))
+        return plan.spike_confidence(dx, jitter)
+    finally:
+        plan.close()

@@ -21,6 +21,11 @@ struct hmmsort_plan {
     WaveDev *wave = nullptr;
     int64_t C = 1;                      // channels (batched wave plans)
     std::vector<HostModel> models;      // per-channel models of a batched plan (models[0] == model)
+    // strict-path posteriors of the last hmmsort_plan_posteriors (the wave engine keeps its own): onset and
+    // trough-state mass (N x T each), arg-max state (T), partial sums for the expected counts
+    double *post_on = nullptr, *post_tq = nullptr, *post_part = nullptr;
+    int16_t *post_xm = nullptr;
+    bool post_valid = false;
 };
 
 namespace {
@@ -238,7 +243,7 @@ int plan_create_engine(hmmsort_plan **out, int64_t T, const int16_t *states, int
 extern "C" {
 
 const char *hmmsort_last_error(void) { return last_error(); }
-int hmmsort_version(void) { return 100; /* 0.1.0 */ }
+int hmmsort_version(void) { return 110; /* 0.1.1: posteriors */ }
 
 int hmmsort_device_count(int *count)
 {
@@ -419,6 +424,8 @@ int hmmsort_plan_destroy(hmmsort_plan *p)
     if (p->gen) generic_destroy(p->gen);
     if (p->ring) ring_destroy(p->ring);
     if (p->wave) wave_destroy(p->wave);
+    for (void *q : {(void *)p->post_on, (void *)p->post_tq, (void *)p->post_part, (void *)p->post_xm})
+        if (q) (void)hipFree(q);
     delete p;
     return HMMSORT_OK;
 }
@@ -991,7 +998,7 @@ int hmmsort_unroll_mlseq(const int16_t *mlseq, int64_t T, const int16_t *states,
 // extract_spiketimes on a path that already lives in device memory
 static int extract_from_device(const int16_t *d_x, int64_t T, const int16_t *states, int64_t N,
                                int64_t S, const double *mu, int64_t K, int64_t *times_out,
-                               int64_t cap, int64_t *counts_out, hipStream_t st)
+                               int64_t cap, int64_t *counts_out, hipStream_t st, DevBuf *dt_keep = nullptr)
 {
     // indmin(mu[:,i]): first minimum (extraction.jl:18); match table per state
     std::vector<uint32_t> match(S, 0u);
@@ -1003,7 +1010,8 @@ static int extract_from_device(const int16_t *d_x, int64_t T, const int16_t *sta
             if (states[i + N * j] == q + 1) match[j] |= (1u << i);
     }
     const int64_t nb = (T + kSpikeChunkHost - 1) / kSpikeChunkHost;
-    DevBuf dm, dcnt, doff, dt;
+    DevBuf dm, dcnt, doff, dt_own;
+    DevBuf &dt = dt_keep ? *dt_keep : dt_own;   // compacted times [N][cap] stay on the device for the caller
     int rc;
     if ((rc = dm.alloc(S * sizeof(uint32_t))) || (rc = dcnt.alloc(nb * N * sizeof(int64_t))) ||
         (rc = doff.alloc(nb * N * sizeof(int64_t))) ||
@@ -1095,6 +1103,203 @@ int hmmsort_plan_extract_spiketimes(hmmsort_plan *p, const int16_t *d_x, int64_t
     for (int64_t i = 0; i < m.N; i++) counts_out[i] = 0;
     return extract_from_device(d_x, p->T, m.states.data(), m.N, m.S, m.mu.data(), m.K, times_out, cap,
                                counts_out, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+// ---- posteriors (INTEGRATION.md "Posteriors") -------------------------------------------------
+
+// trough state value of template i: indmin(mu[:,i]) + 1 as in extract_from_device (extraction.jl:18)
+static int32_t trough_value(const HostModel &m, int64_t i)
+{
+    int64_t q = 0;
+    for (int64_t k = 1; k < m.K; k++)
+        if (m.mu[k + m.K * i] < m.mu[q + m.K * i]) q = k;
+    return (int32_t)(q + 1);
+}
+
+static int strict_posteriors(hmmsort_plan *p, const double *d_y, double *d_onset, double *d_occ, double *d_silent,
+                             double *d_logz, hipStream_t st)
+{
+    const HostModel &m = p->model;
+    const int64_t T = p->T, S = m.S, N = m.N;
+    p->post_valid = false;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
+    const Options opt = options_get();
+    const double need = 2.0 * (double)S * (double)T * 8.0;
+    const double limit = opt.strict_limit_mb > 0 ? (double)opt.strict_limit_mb * 1048576.0 : 0.9 * (double)free_b;
+    if (need > limit) {
+        set_error("plan_posteriors: the strict path needs %.2f GB for alpha and beta (%lld states x %lld samples), "
+                  "limit %.2f GB (option \"strict_limit_mb\", 0 = free device memory)", need / 1e9, (long long)S,
+                  (long long)T, limit / 1e9);
+        return HMMSORT_ENOMEM;
+    }
+    auto own = [&](auto **q, size_t n) -> int {
+        if (*q) return HMMSORT_OK;
+        if (hipMalloc((void **)q, n) != hipSuccess) {
+            (void)hipGetLastError();
+            *q = nullptr;
+            set_error("plan_posteriors: hipMalloc of %zu bytes failed", n);
+            return HMMSORT_ENOMEM;
+        }
+        return HMMSORT_OK;
+    };
+    int rc;
+    if ((rc = own(&p->post_on, (size_t)N * T * 8)) || (rc = own(&p->post_tq, (size_t)N * T * 8)) ||
+        (rc = own(&p->post_xm, (size_t)T * 2)) || (rc = own(&p->post_part, (size_t)N * kPostParts * 8)))
+        return rc;
+    DevBuf da, db, dst, dq, docc, dsil, dz;
+    if ((rc = da.alloc((size_t)S * T * 8)) || (rc = db.alloc((size_t)S * T * 8)) ||
+        (rc = dst.alloc((size_t)N * S * sizeof(int16_t))) || (rc = dq.alloc((size_t)N * sizeof(int32_t))) ||
+        (rc = dz.alloc(8)))
+        return rc;
+    if (!d_occ) { if ((rc = docc.alloc((size_t)N * T * 8))) return rc; d_occ = docc.as<double>(); }
+    if (!d_silent) { if ((rc = dsil.alloc((size_t)T * 8))) return rc; d_silent = dsil.as<double>(); }
+    if (!d_logz) d_logz = dz.as<double>();
+    std::vector<int32_t> qv(N);
+    for (int64_t i = 0; i < N; i++) qv[i] = trough_value(m, i);
+    HS_HIP(hipMemcpyAsync(dst.p, m.states.data(), (size_t)N * S * sizeof(int16_t), hipMemcpyHostToDevice, st));
+    HS_HIP(hipMemcpyAsync(dq.p, qv.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if ((rc = generic_forward(p->gen, d_y, da.as<double>(), st))) return rc;
+    if ((rc = generic_backward(p->gen, d_y, db.as<double>(), st))) return rc;
+    if ((rc = generic_posteriors(da.as<double>(), db.as<double>(), T, S, N, dst.as<int16_t>(), dq.as<int32_t>(),
+                                 d_logz, p->post_on, d_occ, d_silent, p->post_tq, p->post_xm, st)))
+        return rc;
+    if (d_onset) HS_HIP(hipMemcpyAsync(d_onset, p->post_on, (size_t)N * T * 8, hipMemcpyDeviceToDevice, st));
+    HS_HIP(hipStreamSynchronize(st));   // the temporaries die with this frame
+    p->post_valid = true;
+    return HMMSORT_OK;
+}
+
+extern "C" {
+
+int hmmsort_plan_posteriors(hmmsort_plan *p, const double *d_y, double *d_onset, double *d_occ, double *d_silent,
+                            double *d_logz, void *stream)
+{
+    HS_CHECK(p && d_y, HMMSORT_EINVAL, "plan_posteriors: null argument");
+    if (p->wave) return wave_posteriors(p->wave, d_y, d_onset, d_occ, d_silent, d_logz, (hipStream_t)stream);
+    HS_CHECK(p->gen && p->engine == HMMSORT_ENGINE_STRICT, HMMSORT_EUNSUP,
+             "plan_posteriors: needs a wave plan (ring models) or a strict plan (any model); this plan runs engine %lld",
+             (long long)p->engine);
+    return strict_posteriors(p, d_y, d_onset, d_occ, d_silent, d_logz, (hipStream_t)stream);
+}
+
+int hmmsort_plan_posterior_decode(hmmsort_plan *p, int16_t *d_xm, void *stream)
+{
+    HS_CHECK(p && d_xm, HMMSORT_EINVAL, "plan_posterior_decode: null argument");
+    if (p->wave) return wave_post_decode(p->wave, d_xm, (hipStream_t)stream);
+    HS_CHECK(p->post_valid, HMMSORT_EINVAL, "plan_posterior_decode: call hmmsort_plan_posteriors first");
+    HS_HIP(hipMemcpyAsync(d_xm, p->post_xm, (size_t)p->T * sizeof(int16_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return HMMSORT_OK;
+}
+
+int hmmsort_plan_spike_confidence(hmmsort_plan *p, const int16_t *d_x, int64_t jitter, int64_t *times_out,
+                                  double *conf_out, int64_t cap, int64_t *counts_out, void *stream)
+{
+    HS_CHECK(p && d_x && counts_out && cap >= 0 && (cap == 0 || (times_out && conf_out)), HMMSORT_EINVAL,
+             "plan_spike_confidence: bad argument");
+    HS_CHECK(jitter >= 0, HMMSORT_EINVAL, "plan_spike_confidence: jitter must be >= 0 (got %lld)", (long long)jitter);
+    HS_CHECK(p->wave ? p->wave->post_valid : p->post_valid, HMMSORT_EINVAL,
+             "plan_spike_confidence: call hmmsort_plan_posteriors first");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t N = p->model.N, T = p->T;
+    HS_CHECK(N <= 32, HMMSORT_EINVAL, "plan_spike_confidence: more than 32 neurons");
+    for (int64_t ch = 0; ch < p->C; ch++) {
+        const HostModel &m = p->C > 1 ? p->models[ch] : p->model;
+        int64_t *cnt = counts_out + ch * N;
+        for (int64_t i = 0; i < N; i++) cnt[i] = 0;
+        DevBuf dt, dc;
+        int rc = extract_from_device(d_x + ch * T, T, m.states.data(), N, m.S, m.mu.data(), m.K,
+                                     times_out ? times_out + ch * N * cap : nullptr, cap, cnt, st, &dt);
+        if (rc) return rc;
+        if (cap == 0) continue;
+        if ((rc = dc.alloc((size_t)N * cap * sizeof(double)))) return rc;
+        for (int64_t i = 0; i < N; i++) {
+            const int64_t n = std::min(cnt[i], cap);
+            if (n == 0) continue;
+            const int32_t qv = trough_value(m, i);
+            if (p->wave)
+                rc = wave_spike_conf(p->wave, (int)ch, (int)i, qv, jitter, dt.as<int64_t>() + i * cap, n,
+                                     dc.as<double>() + i * cap, st);
+            else
+                rc = dev_spike_conf(p->post_tq + i * T, nullptr, T, 0, jitter, dt.as<int64_t>() + i * cap, n,
+                                    dc.as<double>() + i * cap, st);
+            if (rc) return rc;
+            HS_HIP(hipMemcpyAsync(conf_out + (ch * N + i) * cap, dc.as<double>() + i * cap, n * sizeof(double),
+                                  hipMemcpyDeviceToHost, st));
+        }
+        HS_HIP(hipStreamSynchronize(st));
+    }
+    return HMMSORT_OK;
+}
+
+int hmmsort_plan_expected_counts(hmmsort_plan *p, double *counts_out, void *stream)
+{
+    HS_CHECK(p && counts_out, HMMSORT_EINVAL, "plan_expected_counts: null argument");
+    if (p->wave) return wave_expected_counts(p->wave, counts_out, (hipStream_t)stream);
+    HS_CHECK(p->post_valid, HMMSORT_EINVAL, "plan_expected_counts: call hmmsort_plan_posteriors first");
+    return dev_row_sums(p->post_on, p->model.N, p->T, p->post_part, counts_out, (hipStream_t)stream);
+}
+
+int hmmsort_posteriors(const double *y, int64_t T, const int16_t *states, int64_t N, int64_t K, int64_t S,
+                       const hmm_trans *tr, int64_t R, const double *mu, double sigma, double *onset, double *occ,
+                       double *silent, int16_t *xm, double *logz)
+{
+    HS_CHECK(y && states && tr && mu, HMMSORT_EINVAL, "posteriors: null argument");
+    HS_CHECK(T >= 2, HMMSORT_EINVAL, "posteriors: need T >= 2");
+    int rc;
+    if ((rc = need_device())) return rc;
+    const Options opt = options_get();
+    last_escalations() = 0;
+    std::unique_ptr<HostSlot> slot = take_slot(T, states, N, K, S, opt);
+    if (!slot) slot = new_slot(T, opt);
+    HostSlot &h = *slot;
+    if ((rc = h.dy.ensure(T * sizeof(double)))) return rc;
+    HS_HIP(hipMemcpyAsync(h.dy.p, y, T * sizeof(double), hipMemcpyHostToDevice, h.st));
+    if (h.plan && hmmsort_plan_set_model(h.plan, tr, R, mu, sigma)) h.drop_plan();
+    DevBuf don, docc, dsil, dxm, dz;
+    if ((onset && (rc = don.alloc((size_t)N * T * 8))) || (occ && (rc = docc.alloc((size_t)N * T * 8))) ||
+        (silent && (rc = dsil.alloc((size_t)T * 8))) || (xm && (rc = dxm.alloc((size_t)T * 2))) || (rc = dz.alloc(8)))
+        return rc;
+    bool keep = true;
+    int64_t halo = -1, engine = opt.engine;
+    for (int attempt = 0;; attempt++) {
+        if (!h.plan) {
+            rc = plan_create_engine(&h.plan, T, states, N, K, S, tr, R, mu, sigma, engine, halo);
+            if (rc) return rc;
+        }
+        if (!h.plan->wave && h.plan->engine != HMMSORT_ENGINE_STRICT) {
+            keep = false;                    // what the wave engine does not take: materialised alpha/beta
+            engine = HMMSORT_ENGINE_STRICT;
+            h.drop_plan();
+            continue;
+        }
+        if ((rc = hmmsort_plan_posteriors(h.plan, h.dy.as<double>(), don.as<double>(), docc.as<double>(),
+                                          dsil.as<double>(), dz.as<double>(), h.st)))
+            return rc;
+        if (xm && (rc = hmmsort_plan_posterior_decode(h.plan, dxm.as<int16_t>(), h.st))) return rc;
+        HS_HIP(hipStreamSynchronize(h.st));
+        int64_t diag[8];
+        if ((rc = hmmsort_plan_diagnostics(h.plan, h.st, diag))) return rc;
+        if (!h.plan->wave || (diag[3] == 0 && diag[5] == 0) || !opt.escalate) break;
+        last_escalations() = attempt + 1;
+        halo = next_halo(h.plan);
+        if (attempt >= 3 || halo > T) {
+            HS_CHECK(opt.engine != HMMSORT_ENGINE_WAVE, HMMSORT_ENOCONV,
+                     "posteriors: %lld chain boundaries still fail the warm-up check", (long long)(diag[3] + diag[5]));
+            engine = HMMSORT_ENGINE_STRICT;
+        }
+        h.drop_plan();
+        keep = false;
+    }
+    if (onset) HS_HIP(hipMemcpy(onset, don.p, (size_t)N * T * 8, hipMemcpyDeviceToHost));
+    if (occ) HS_HIP(hipMemcpy(occ, docc.p, (size_t)N * T * 8, hipMemcpyDeviceToHost));
+    if (silent) HS_HIP(hipMemcpy(silent, dsil.p, (size_t)T * 8, hipMemcpyDeviceToHost));
+    if (xm) HS_HIP(hipMemcpy(xm, dxm.p, (size_t)T * 2, hipMemcpyDeviceToHost));
+    if (logz) HS_HIP(hipMemcpy(logz, dz.p, 8, hipMemcpyDeviceToHost));
+    if (keep) give_slot(std::move(slot), opt);
+    return HMMSORT_OK;
 }
 
 }  // extern "C"

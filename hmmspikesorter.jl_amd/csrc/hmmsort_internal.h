@@ -110,6 +110,11 @@ int generic_backward(GenericDev *g, const double *d_y, double *d_beta, hipStream
 int generic_update(GenericDev *g, const double *d_alpha, const double *d_beta, const double *d_y,
                    double *d_out, hipStream_t st);
 int64_t generic_n_lp(const GenericDev *g);
+// smoothed posteriors from materialised alpha/beta (generic_post.hip): per sample, gamma reduced over the state
+// table into onset / occ / trough-state mass (N x T each), silent (T), arg-max state (1-based) and logz
+int generic_posteriors(const double *d_alpha, const double *d_beta, int64_t T, int64_t S, int64_t N,
+                       const int16_t *d_states, const int32_t *d_qv, double *d_logz, double *d_onset,
+                       double *d_occ, double *d_silent, double *d_tq, int16_t *d_xm, hipStream_t st);
 // time-parallel E-step of the blocked generic engine (generic_estep.hip): sufficient statistics without
 // S x T arrays.  stats = [G0 (S) | G1 (S) | X (n_lp + 1) | Gamma0 | sum y^2]
 bool blocked_estep_supported(const GenericDev *g);

@@ -110,6 +110,13 @@ struct WaveDev {
     int64_t *diag = nullptr;          // 8
     double *trash = nullptr;          // 64 x 64 doubles: where idle lanes of a partial super-step store (branch-free stores)
     double *dbg = nullptr;            // 64 doubles: debug record of the first failing certificate
+    // posterior calls (wave_post.hip); the buffers are allocated by the first such call
+    bool keep_post = false;           // this launch keeps rho and gamma(silent) of every sample (unfused backward sweep, no statistics)
+    bool post_valid = false;          // rho / gsil / phead / plogz hold the posteriors of the last hmmsort_plan_posteriors
+    double *gsil = nullptr;           // C x T   gamma_t(silent)
+    double *phead = nullptr;          // C x N x L posteriors of the virtual onsets t' = -j ([a*L + j], j = 1..L-1; [a*L] = 0)
+    double *plogz = nullptr;          // C       log-likelihood of the recording
+    double *pcnt = nullptr;           // C*N x kPostParts partial sums of rho (expected spike counts)
     // exact near-tie resolver (wave_ties.hip)
     int64_t *tie_cnt = nullptr;       // C x 8 counters (kTie* below)
     int64_t *tie_list = nullptr;      // C x kTieCap flagged decisions on the decoded path: t * 32 + entry, time order
@@ -401,5 +408,20 @@ int wave_estep(WaveDev *r, const double *d_y, double *d_stats, hipStream_t st);
 int wave_mstep(WaveDev *r, const double *d_stats, double *d_out, hipStream_t st);
 int wave_decode_estep(WaveDev *r, const double *d_y, int16_t *d_x, double *d_ll, double *d_stats,
                       hipStream_t st);
+int wave_post_sweeps(WaveDev *r, const double *d_y, hipStream_t st);
+// wave_post.hip: posterior marginals, posterior decode, spike confidence
+constexpr int kPostParts = 256;
+int wave_posteriors(WaveDev *r, const double *d_y, double *d_onset, double *d_occ, double *d_silent, double *d_logz,
+                    hipStream_t st);
+int wave_post_decode(WaveDev *r, int16_t *d_xm, hipStream_t st);
+// confidences of n events of template a on channel ch (1-based times in device memory), see dev_spike_conf
+int wave_spike_conf(WaveDev *r, int ch, int a, int qv, int64_t jitter, const int64_t *d_times, int64_t n,
+                    double *d_conf, hipStream_t st);
+int wave_expected_counts(WaveDev *r, double *counts_out, hipStream_t st);
+// shared by the strict path (capi.cpp): sum_{|d| <= J} src[t + d - shift] (head[-index] for a negative index when
+// head is given, 0 otherwise and outside [0, T)), capped at 1; sums over time of n rows of length T
+int dev_spike_conf(const double *d_src, const double *d_head, int64_t T, int64_t shift, int64_t jitter,
+                   const int64_t *d_times, int64_t n, double *d_conf, hipStream_t st);
+int dev_row_sums(const double *d_rows, int64_t nrows, int64_t T, double *d_part, double *out_host, hipStream_t st);
 
 }  // namespace hmmsort

@@ -333,7 +333,7 @@ void wave_destroy(WaveDev *r)
                     r->psi, r->vpre, r->vend, r->vfail, r->bstate, r->redo, r->final_state, r->part, r->FA0,
                     r->FV, r->FREF, r->fpre, r->bpre, r->bown, r->rho, r->Zc, r->partS, r->partG, r->yhead,
                     r->extra, r->pp, r->diag, r->dbg, r->trash, r->tie_cnt, r->tie_list, r->tie_off, r->tie_walk, r->tie_guess,
-                    r->tie_c, r->tie_ok, r->tie_v};
+                    r->tie_c, r->tie_ok, r->tie_v, r->gsil, r->phead, r->plogz, r->pcnt};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (r->ev_fork) (void)hipEventDestroy(r->ev_fork);

@@ -318,7 +318,9 @@ constexpr int bwd_yring(int ft) { return ft <= 2 ? 256 : 512; }
 #ifndef HS_BWD_W4
 #define HS_BWD_W4 2   // waves per SIMD asked of the compiler for up to 4 rings (3, with a one-deep input pipeline and chains of 3 264 samples: 18 spilled registers, 0.382 against 0.369 ms)
 #endif
-template <int N, bool UC, int FT = 0>
+// GS (posterior calls, wave_post.hip): the sweep also stores gamma_t(silent) of every owned sample; the
+// default instantiations (GS = false) compile to what they were.
+template <int N, bool UC, int FT = 0, bool GS = false>
 __global__ __launch_bounds__(64, N <= 4 ? HS_BWD_W4 : 1) void kw_bwd(WaveGeom g, const WaveConst *__restrict__ cst,
                                                             const double *__restrict__ y,
                                                             const double *__restrict__ Rf,
@@ -330,9 +332,11 @@ __global__ __launch_bounds__(64, N <= 4 ? HS_BWD_W4 : 1) void kw_bwd(WaveGeom g,
                                                             double *__restrict__ rho, double *__restrict__ partS,
                                                             double *__restrict__ Zc, double *__restrict__ bpre,
                                                             double *__restrict__ bown, double *__restrict__ yhead,
-                                                            double *__restrict__ trash, double *__restrict__ partG)
+                                                            double *__restrict__ trash, double *__restrict__ partG,
+                                                            double *__restrict__ gsil)
 {
     constexpr bool FUSE = FT > 0;
+    static_assert(!GS || !FUSE, "the silent posterior is stored by the unfused sweep");
     static_assert(!FUSE || (N >= 3 && N <= 8), "the fused statistics are written for delayed copies of 3-8 rings");
     static_assert(!FUSE || N > 4 || FT == 1, "3-4 rings: one tile of 64 lags");
     constexpr int NPc = N <= 4 ? 4 : 8, NSc = 16 / NPc, LPT = 16 * NSc;   // ring columns per copy, copies, lags per tile
@@ -555,6 +559,7 @@ __global__ __launch_bounds__(64, N <= 4 ? HS_BWD_W4 : 1) void kw_bwd(WaveGeom g,
                 if (!g.last || t < T - 1) s_m += ga;             // :257 bb, t = 1..T-1 of the recording
                 s_y2 = __builtin_fma(ga, d.y0 * d.y0, s_y2);     // :302 with the new silent mean (= 0)
             }
+            if (GS) *(live && t >= tc ? gsil + (int64_t)ch * T + t : trash + 64 * N + lane) = xt * gg[0];
             const bool own1 = live && t1 >= g.own_lo && t1 < g.own_hi;
             const bool bulk = !(g.last && t1 > T - L);           // truncated rings: summed per phase in kw_stats_final
 #pragma unroll
@@ -635,6 +640,7 @@ __global__ __launch_bounds__(64, N <= 4 ? HS_BWD_W4 : 1) void kw_bwd(WaveGeom g,
         z = zmax + flog(zs);
         if (lane == 0) {
             Zc[cg] = z;
+            if (GS) gsil[(int64_t)ch * T + tstar] = xb * fexp((la + Mb) - z);
             if (tstar >= g.own_lo && tstar < g.own_hi) {
                 const double ga = xb * fexp((la + Mb) - z);
                 s_all += ga;
@@ -1093,6 +1099,7 @@ static int wave_estep_sweeps(WaveDev *r, const double *d_y, double *d_stats, hip
     const WaveGeom &g = r->g;
     const int N = g.N, L = g.L, NL = N * L;
     const int nchT = g.C * g.nch;
+    if (!r->keep_post) r->post_valid = false;   // the fused sweep does not keep rho
     int rowsG = 0;
     int rc = dispatch_N(N, [&](auto n) {
         constexpr int NN = decltype(n)::value;
@@ -1101,7 +1108,8 @@ static int wave_estep_sweeps(WaveDev *r, const double *d_y, double *d_stats, hip
         // 3-4 rings of at most 64 states, 5-8 rings of at most 128 (uniform exit -> entry values): the backward
         // sweep accumulates G1 itself (matrix cores, LDS rings)
         constexpr bool kFuse4 = NN == 3 || NN == 4, kFuse8 = NN >= 5 && NN <= 8;
-        const bool sep = generic || getenv("HMMSORT_GSUM_SEPARATE") != nullptr;
+        // posterior calls (wave_post.hip) keep rho of every sample: the unfused sweep
+        const bool sep = generic || r->keep_post || getenv("HMMSORT_GSUM_SEPARATE") != nullptr;
         const int ft = sep ? 0 : (kFuse4 && L <= 64) ? 1 : (kFuse8 && r->uniform_cx && L <= 64) ? 2
                        : (kFuse8 && r->uniform_cx && L <= 128) ? 4 : 0;
         const bool fuse = ft > 0;
@@ -1112,6 +1120,12 @@ static int wave_estep_sweeps(WaveDev *r, const double *d_y, double *d_stats, hip
         auto kb = kw_bwd<NN, true>;
         if constexpr (NN <= 8) {   // per-source exit -> entry values: up to 8 rings (wave_supported)
             if (!r->uniform_cx) { kf = kw_fwd<NN, false>; kb = kw_bwd<NN, false>; }
+        }
+        if (r->keep_post) {
+            kb = kw_bwd<NN, true, 0, true>;
+            if constexpr (NN <= 8) {
+                if (!r->uniform_cx) kb = kw_bwd<NN, false, 0, true>;
+            }
         }
         if constexpr (kFuse4) {
             if (ft == 1) kb = r->uniform_cx ? kw_bwd<NN, true, 1> : kw_bwd<NN, false, 1>;
@@ -1125,9 +1139,10 @@ static int wave_estep_sweeps(WaveDev *r, const double *d_y, double *d_stats, hip
         { WPROF(r, "kw_fwd", st);
           hipLaunchKernelGGL(kf, dim3(nchT), dim3(64), ldsf, st, g, r->d_cst, d_y, r->Rf, r->virt, r->FA0,
                              r->FV, r->FREF, r->fpre, r->trash); }
-        { WPROF(r, "kw_bwd", st);
+        { WPROF(r, r->keep_post ? "kw_bwd_post" : "kw_bwd", st);
           hipLaunchKernelGGL(kb, dim3(nchT), dim3(64), ldsb, st, g, r->d_cst, d_y, r->Rf, r->FA0, r->FV,
-                             r->FREF, r->fpre, r->W2, r->rho, r->partS, r->Zc, r->bpre, r->bown, r->yhead, r->trash, r->partG); }
+                             r->FREF, r->fpre, r->W2, r->rho, r->partS, r->Zc, r->bpre, r->bown, r->yhead, r->trash, r->partG,
+                             r->gsil); }
         HS_HIP(hipGetLastError());
         // the certificate runs beside the statistics / final assembly
         HS_HIP(hipEventRecord(r->ev_a, st));
@@ -1138,6 +1153,7 @@ static int wave_estep_sweeps(WaveDev *r, const double *d_y, double *d_stats, hip
                                r->bpre, r->bown, r->rho, r->diag, r->dbg);
         }
         HS_HIP(hipEventRecord(r->ev_c, r->side));   // the certificate only has to be done when the call's work is
+        if (r->keep_post) return HMMSORT_OK;        // posterior-only call: no statistics
         constexpr int NPx = NN <= 1 ? 1 : (NN <= 2 ? 2 : (NN <= 4 ? 4 : (NN <= 8 ? 8 : 16)));
         constexpr int LPTx = 16 * (16 / NPx), HSx = LPTx - 16;
         const int ntx = (L + LPTx - 1) / LPTx;
@@ -1179,6 +1195,10 @@ static int wave_estep_sweeps(WaveDev *r, const double *d_y, double *d_stats, hip
         return HMMSORT_OK;
     });
     if (rc) return rc;
+    if (r->keep_post) {
+        HS_HIP(hipStreamWaitEvent(st, r->ev_c, 0));
+        return HMMSORT_OK;
+    }
     const int total = 3 * NL + N + 4;
     { WPROF(r, "kw_stats_final", st);
       hipLaunchKernelGGL(kw_stats_final, dim3(total, g.C), dim3(64), 0, st, g, rowsG, r->partG, r->partS, d_y, r->Rf,
@@ -1190,12 +1210,26 @@ static int wave_estep_sweeps(WaveDev *r, const double *d_y, double *d_stats, hip
 
 int wave_estep(WaveDev *r, const double *d_y, double *d_stats, hipStream_t st)
 {
+    r->post_valid = false;
     return wave_graphed(r, 2, d_y, d_stats, nullptr, nullptr, st, [&](hipStream_t s) -> int {
         int rc;
         HS_HIP(hipMemsetAsync(r->diag, 0, 8 * sizeof(int64_t), s));
         if ((rc = wave_prepare(r, d_y, s))) return rc;
         return wave_estep_sweeps(r, d_y, d_stats, s);
     });
+}
+
+// forward + backward sweeps of a posterior call (wave_post.hip): rho and gamma(silent) of every sample, the chain
+// normalisers and the head record; the warm-up certificates run and count as in an E-step, no statistics
+int wave_post_sweeps(WaveDev *r, const double *d_y, hipStream_t st)
+{
+    int rc;
+    HS_HIP(hipMemsetAsync(r->diag, 0, 8 * sizeof(int64_t), st));
+    if ((rc = wave_prepare(r, d_y, st))) return rc;
+    r->keep_post = true;
+    rc = wave_estep_sweeps(r, d_y, nullptr, st);
+    r->keep_post = false;
+    return rc;
 }
 
 int wave_mstep(WaveDev *r, const double *d_stats, double *d_out, hipStream_t st)
@@ -1210,6 +1244,7 @@ int wave_mstep(WaveDev *r, const double *d_stats, double *d_out, hipStream_t st)
 // runs on the plan's second internal stream beside the forward/backward sweeps
 int wave_decode_estep(WaveDev *r, const double *d_y, int16_t *d_x, double *d_ll, double *d_stats, hipStream_t st)
 {
+    r->post_valid = false;
     return wave_graphed(r, 3, d_y, d_x, d_ll, d_stats, st, [&](hipStream_t s) -> int {
         int rc;
         HS_HIP(hipMemsetAsync(r->diag, 0, 8 * sizeof(int64_t), s));

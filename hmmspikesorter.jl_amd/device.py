@@ -162,6 +162,42 @@ class Plan:
                                                         ptr(counts), C.c_void_p(stream)))
         return [times[i, :counts[i]].copy() for i in range(self.N)]
 
+    def posteriors(self, d_y, d_onset=None, d_occ=None, d_silent=None, d_logz=None, stream=0):
+        """smoothed state posteriors of d_y under the plan's model, device to device (hmmsort_plan_posteriors):
+        onset / occ [C][N][T], silent [C][T], logz [C] doubles; None skips an output.  Wave plans (ring models)
+        and strict plans (any model); the plan keeps the posteriors for posterior_decode / spike_confidence /
+        expected_counts until its next E-step or posterior call."""
+        check(lib().hmmsort_plan_posteriors(self._h, _dptr(d_y), _dptr(d_onset), _dptr(d_occ), _dptr(d_silent),
+                                            _dptr(d_logz), C.c_void_p(stream)))
+
+    def posterior_decode(self, d_xm, stream=0):
+        """arg max_s gamma_t(s) per sample ([C][T] int16, 1-based states), after posteriors()"""
+        check(lib().hmmsort_plan_posterior_decode(self._h, _dptr(d_xm), C.c_void_p(stream)))
+
+    def spike_confidence(self, d_x, jitter=2, stream=0):
+        """per template (times, confidence) of the events extract_spiketimes reports on the decoded path d_x,
+        after posteriors(): confidence = posterior probability that the template was in its trough state within
+        +-jitter samples of the event.  A batched plan returns one such list per channel."""
+        nC = getattr(self, "C", 1)
+        counts = np.zeros((nC, self.N), dtype=np.int64)
+        check(lib().hmmsort_plan_spike_confidence(self._h, _dptr(d_x), int(jitter), None, None, 0, ptr(counts),
+                                                  C.c_void_p(stream)))
+        cap = max(int(counts.max()) if counts.size else 0, 1)
+        times = np.zeros((nC, self.N, cap), dtype=np.int64)
+        conf = np.zeros((nC, self.N, cap), dtype=np.float64)
+        check(lib().hmmsort_plan_spike_confidence(self._h, _dptr(d_x), int(jitter), ptr(times), ptr(conf), cap,
+                                                  ptr(counts), C.c_void_p(stream)))
+        out = [[(times[c, i, :counts[c, i]].copy(), conf[c, i, :counts[c, i]].copy()) for i in range(self.N)]
+               for c in range(nC)]
+        return out if hasattr(self, "C") else out[0]
+
+    def expected_counts(self, stream=0):
+        """expected number of spikes per template, sum_t onset[a, t] ([C][N]; [N] for a single-channel plan)"""
+        nC = getattr(self, "C", 1)
+        out = np.zeros((nC, self.N), dtype=np.float64)
+        check(lib().hmmsort_plan_expected_counts(self._h, ptr(out), C.c_void_p(stream)))
+        return out if hasattr(self, "C") else out[0]
+
     def profile(self, enable=True):
         check(lib().hmmsort_plan_profile(self._h, int(bool(enable))))
 

@@ -53,12 +53,34 @@ def load_data(path, name="data"):
     return d[name]
 
 
+def _chunk_confidence(templates, dataf, ml_seq, chunksize, jitter):
+    """spike times and confidences of the decoded path, chunk by chunk of the chunked fit, on the strict path"""
+    n, N = len(ml_seq), templates.state_matrix.N
+    times, conf = [[] for _ in range(N)], [[] for _ in range(N)]
+    for lo in range(0, n, chunksize):
+        hi = min(lo + chunksize, n)
+        if hi - lo < 2:
+            continue
+        part = api.HMMSpikingModel(templates, ml_seq[lo:hi], 0.0, np.asarray(dataf[lo:hi], dtype=np.float64))
+        for a, (t, c) in enumerate(api.spike_confidence(part, jitter)):
+            times[a].append(t + lo)
+            conf[a].append(c)
+    cat = lambda parts, dt: [np.concatenate(q) if q else np.zeros(0, dtype=dt) for q in parts]  # noqa: E731
+    return cat(times, np.int64), cat(conf, np.float64)
+
+
 def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_templates=4,
-              chunksize=100_000):
+              chunksize=100_000, confidence=False, jitter=2):
     """sort_data(inputfile, datafile, outputfile; dosave, max_templates)   hmmsort.jl:36-104.
 
     Returns the reference's output dictionary; {} when there are more templates than
-    `max_templates` (hmmsort.jl:49-52, 57-59)."""
+    `max_templates` (hmmsort.jl:49-52, 57-59).
+
+    `confidence=True` (an extension; default off, output unchanged) adds "spiketimes" (per template, 1-based
+    samples as extract_spiketimes) and "confidence" (per spike, api.spike_confidence with `jitter`), computed per
+    chunk of the chunked fit from the chunk's own posteriors.  The decode model resolves overlaps, so this runs
+    on the strict path (alpha and beta materialised, 2 x S x chunksize doubles): slow, and for the 3- and
+    4-template overlap models only feasible with a small `chunksize`."""
     spike_forms = np.asarray(spike_forms, dtype=np.float64)
     nstates, _nchannels, ntemplates = spike_forms.shape
     pp = np.atleast_1d(np.asarray(p, dtype=np.float64))
@@ -77,6 +99,11 @@ def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_temp
     modelf = api.fit(templates, dataf, chunksize)                              # :90
     mlseq = api.unroll_mlseq(modelf.ml_seq, sm)                                # :92
     out = {"mlseq": mlseq, "ll": modelf.ll, "waveforms": templates.mu, "lp": lp, "sigma": sigma}
+    if confidence:
+        st, cf = _chunk_confidence(templates, dataf, modelf.ml_seq, chunksize or len(dataf), jitter)
+        out["spiketimes"], out["confidence"] = np.empty(len(st), dtype=object), np.empty(len(cf), dtype=object)
+        for a in range(len(st)):
+            out["spiketimes"][a], out["confidence"][a] = st[a], cf[a]
     if dosave and outputfile is not None:
         from scipy.io import savemat
         savemat(outputfile, out)                                               # MAT.matwrite :100

@@ -289,6 +289,40 @@ int hmmsort_plan_unroll_mlseq(hmmsort_plan *plan, const int16_t *d_x, int16_t *d
 int hmmsort_plan_extract_spiketimes(hmmsort_plan *plan, const int16_t *d_x, int64_t *times_out,
                                     int64_t cap, int64_t *counts_out, void *stream);
 
+/* Smoothed state posteriors gamma_t(s) = P(state s at sample t | whole recording) of the plan's current
+ * model(s), left in device memory (definitions: INTEGRATION.md "Posteriors"; an extension, the reference keeps
+ * the decoded path only).  Per channel of a batched plan (channel-major like every plan buffer):
+ *   d_onset  [C][N][T]  mass of the states in which template a is at its first phase (states[a,s] == 2)
+ *   d_occ    [C][N][T]  mass of the states in which template a is mid-spike (states[a,s] > 1)
+ *   d_silent [C][T]     mass of state 1
+ *   d_logz   [C]        log-likelihood of the recording, logsumexp_s alpha_{T-1}(s)
+ * Any output may be NULL.  Wave plans (ring models, up to 16 templates) run the forward sweep, the unfused
+ * backward sweep and one streaming pass; strict plans (any model; option "engine" = HMMSORT_ENGINE_STRICT)
+ * materialise alpha and beta (2 x S x T doubles, bounded by "strict_limit_mb": HMMSORT_ENOMEM beyond it) and
+ * synchronise the stream.  Other plans: HMMSORT_EUNSUP.  A time shard (hmmsort_plan_set_shard): HMMSORT_EINVAL.
+ * The warm-up certificates of a wave plan run and count into hmmsort_plan_diagnostics as in an E-step.
+ * The plan keeps the posteriors for the three calls below until its next E-step or posterior call. */
+int hmmsort_plan_posteriors(hmmsort_plan *plan, const double *d_y, double *d_onset, double *d_occ,
+                            double *d_silent, double *d_logz, void *stream);
+/* Maximum-posterior-marginal decode: d_xm[t] = arg max_s gamma_t(s), 1-based like the Viterbi path, ties to
+ * the lower state number.  [C][T] Int16 in device memory. */
+int hmmsort_plan_posterior_decode(hmmsort_plan *plan, int16_t *d_xm, void *stream);
+/* Confidence of every spike of a decoded path d_x ([C][T], normally hmmsort_plan_viterbi's): for each event
+ * hmmsort_plan_extract_spiketimes reports for template a at sample t, the posterior probability that template a
+ * was in its trough state within +-jitter samples of t, min(1, sum_{|d| <= jitter} gamma_{t+d}(trough of a)).
+ * times_out / conf_out: [C][N][cap] on the host, counts_out [C][N]; protocol of hmmsort_extract_spiketimes
+ * (cap = 0 counts only).  Synchronises the stream. */
+int hmmsort_plan_spike_confidence(hmmsort_plan *plan, const int16_t *d_x, int64_t jitter, int64_t *times_out,
+                                  double *conf_out, int64_t cap, int64_t *counts_out, void *stream);
+/* Expected number of spikes per template, sum_t onset[a,t] (events whose first phase falls inside the
+ * recording).  counts_out: [C][N] on the host.  Synchronises the stream. */
+int hmmsort_plan_expected_counts(hmmsort_plan *plan, double *counts_out, void *stream);
+/* Host-buffer form (model arguments as hmmsort_em_step, same plan cache and escalation): onset / occ (N x T,
+ * template-major), silent (T), xm (T), logz (1); NULL skips an output. */
+int hmmsort_posteriors(const double *y, int64_t T, const int16_t *states, int64_t N, int64_t K, int64_t S,
+                       const hmm_trans *tr, int64_t R, const double *mu, double sigma, double *onset,
+                       double *occ, double *silent, int16_t *xm, double *logz);
+
 /* Widening of raw samples already in device memory into the fp64 signal the plan calls take
  * (src/hmmsort.jl:79-88: `view(data, :, 1)` of the acquisition array, converted to Float64): element i
  * of the output is d_in[i * stride] (stride in elements: 1 for a channel stored contiguously, the

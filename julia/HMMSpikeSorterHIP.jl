@@ -93,6 +93,27 @@ function reconstruct_signal(x::Array{T,1}, lA::StateMatrix, μ::Array{Float64,2}
     Y2
 end
 
+"""
+    posteriors(y, lA, μ, σ; decode=false) -> (onset, occ, silent, xm, logz)
+
+Smoothed state posteriors (an extension, no counterpart in the reference; INTEGRATION.md "Posteriors"):
+`onset[t, a]` / `occ[t, a]` = posterior that template `a` is at its first phase / mid-spike at sample `t`,
+`silent[t]` that of the silent state, `logz` the log-likelihood of the recording; with `decode=true`, `xm[t]` =
+the state of largest posterior (1-based, like `viterbi`'s path), else `xm` is empty.
+"""
+function posteriors(y::AbstractArray{Float64,1}, lA::StateMatrix, μ::Array{Float64,2}, σ::Float64; decode=false)
+    yv = y isa Array ? y : collect(y)
+    T = length(yv)
+    onset = zeros(Float64, T, lA.N); occ = zeros(Float64, T, lA.N); silent = zeros(Float64, T)
+    xm = zeros(Int16, decode ? T : 0); logz = Ref{Float64}(0.0)
+    check(ccall((:hmmsort_posteriors, lib), Cint,
+        (Ptr{Float64}, Int64, Ptr{Int16}, Int64, Int64, Int64, Ptr{Cvoid}, Int64, Ptr{Float64}, Float64,
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int16}, Ref{Float64}),
+        yv, T, lA.states, lA.N, lA.K, lA.nstates, lA.transitions, length(lA.transitions), μ, σ,
+        onset, occ, silent, decode ? pointer(xm) : Ptr{Int16}(C_NULL), logz))
+    onset, occ, silent, xm, logz[]
+end
+
 "Free the plans and device buffers the library keeps between host-buffer calls."
 shutdown() = check(ccall((:hmmsort_shutdown, lib), Cint, ()))
 set_option(key::String, value::Integer) = check(ccall((:hmmsort_set_option, lib), Cint, (Cstring, Int64), key, value))
