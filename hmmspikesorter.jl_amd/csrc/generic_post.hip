@@ -1,6 +1,10 @@
 // Smoothed state posteriors of an ARBITRARY transition list from the strict engine's materialised alpha/beta
-// (reference src/baumwelch.jl:25-51, :73-98): gamma_t(s) = exp(alpha_t(s) + beta_t(s) - z), z = logsumexp_s
-// alpha_{T-1}(s), reduced per sample over the state table into the outputs of hmmsort_plan_posteriors.  Serves
+// (reference src/baumwelch.jl:25-51, :73-98): gamma_t(s) = exp(alpha_t(s) + beta_t(s) - z_t), z_t = logsumexp_s
+// (alpha_t(s) + beta_t(s)) -- every column normalised by its own sum, as the reference's update does
+// (baumwelch.jl:216-224).  z_t equals z = logsumexp_s alpha_{T-1}(s) (the logz output) in exact arithmetic, but the
+// unscaled log alpha/beta have magnitude O(t) and their rounding reaches 1e-7 of z at 200 000 samples: dividing by
+// the one global z put that error into every probability.  Reduced per sample over the state table into the
+// outputs of hmmsort_plan_posteriors.  Serves
 // the models the wave engine does not take (overlap models) and is the second, independent implementation the
 // wave path is checked against.  Slow by design: it reads S x T doubles twice.
 #include <cmath>
@@ -42,13 +46,11 @@ constexpr int kPostMaxN = 16;
 // one wavefront per sample; states: N x S (1-based phases, 1 = silent), qv[a] = trough phase of template a
 __global__ __launch_bounds__(64) void kg_post(const double *__restrict__ alpha, const double *__restrict__ beta,
                                               int64_t T, int S, int N, const int16_t *__restrict__ states,
-                                              const int32_t *__restrict__ qv, const double *__restrict__ logz,
-                                              double *__restrict__ onset, double *__restrict__ occ,
-                                              double *__restrict__ silent, double *__restrict__ tq,
-                                              int16_t *__restrict__ xm)
+                                              const int32_t *__restrict__ qv, double *__restrict__ onset,
+                                              double *__restrict__ occ, double *__restrict__ silent,
+                                              double *__restrict__ tq, int16_t *__restrict__ xm)
 {
     const int lane = threadIdx.x;
-    const double z = logz[0];
     int q[kPostMaxN];
 #pragma unroll
     for (int a = 0; a < kPostMaxN; a++) q[a] = a < N ? qv[a] : 0;
@@ -57,6 +59,16 @@ __global__ __launch_bounds__(64) void kg_post(const double *__restrict__ alpha, 
         double on[kPostMaxN], oc[kPostMaxN], tr[kPostMaxN];
 #pragma unroll
         for (int a = 0; a < kPostMaxN; a++) { on[a] = 0.0; oc[a] = 0.0; tr[a] = 0.0; }
+        double m = -INFINITY, sum = 0.0;
+        for (int s = lane; s < S; s += 64) m = fmax(m, al[s] + be[s]);
+        for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o));
+        for (int s = lane; s < S; s += 64) {
+            const double v = al[s] + be[s];
+            // a state the reference's logsumexpl(-Inf, -Inf) left NaN stays out of the normaliser only: below, its
+            // NaN still goes into the marginals of the templates that own it, as it did with the global z
+            if (v == v) sum += exp(v - m);
+        }
+        const double z = m + log(pw_sum(sum));
         double bv = -1.0;
         int bs = 0;
         for (int s = lane; s < S; s += 64) {
@@ -102,7 +114,7 @@ int generic_posteriors(const double *d_alpha, const double *d_beta, int64_t T, i
     HS_CHECK(N <= kPostMaxN, HMMSORT_EUNSUP, "posteriors (strict path): more than %d templates", kPostMaxN);
     hipLaunchKernelGGL(kg_post_logz, dim3(1), dim3(256), 0, st, d_alpha, T, (int)S, d_logz);
     const unsigned nb = (unsigned)(T < 65536 ? T : 65536);
-    hipLaunchKernelGGL(kg_post, dim3(nb), dim3(64), 0, st, d_alpha, d_beta, T, (int)S, (int)N, d_states, d_qv, d_logz,
+    hipLaunchKernelGGL(kg_post, dim3(nb), dim3(64), 0, st, d_alpha, d_beta, T, (int)S, (int)N, d_states, d_qv,
                        d_onset, d_occ, d_silent, d_tq, d_xm);
     HS_HIP(hipGetLastError());
     return HMMSORT_OK;

@@ -4,6 +4,9 @@ The reference (Julia) cannot run in the build image and holds no golden alpha/be
 of its own, so these fixtures pin the oracle's current behaviour (regression guard) and give the
 GPU tests fixed inputs/outputs; they are NOT outputs of the reference ("parity unpinned" for
 these numerics).  Usage:  python tests/golden/make_golden.py
+
+The fixtures of the E-step at 1 M and 10 M samples (tests/golden/estep_at_size/) come from another generator,
+make_estep_at_size.py, and another checker: the extended-precision reference oracle/hp_estep.c.
 """
 import os
 import sys
