@@ -7,6 +7,8 @@ these numerics).  Usage:  python tests/golden/make_golden.py
 
 The fixtures of the E-step at 1 M and 10 M samples (tests/golden/estep_at_size/) come from another generator,
 make_estep_at_size.py, and another checker: the extended-precision reference oracle/hp_estep.c.
+The reference paths of the Viterbi decode at up to 10 M samples (tests/golden/viterbi_at_size/) come from
+make_viterbi_at_size.py and the extended-precision MAP reference oracle/hp_viterbi.c.
 """
 import os
 import sys
