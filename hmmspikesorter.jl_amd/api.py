@@ -465,7 +465,9 @@ def _posteriors_host(y, lA, mu, sigma, want_xm, want_marginals=True):
 def posteriors(y, lA, mu, sigma):
     """posteriors(y, lA, mu, sigma) -> Posteriors.  Ring models (no overlaps, up to 16 templates) run on the wave
     engine; any other model on the strict engine from materialised alpha/beta (2 x S x T doubles on the
-    device: short signals only)."""
+    device: short signals only).  With option "engine" set to ENGINE_BLOCKED an overlap model whose two state
+    columns fit the LDS (up to 4 templates) runs on the blocked engine instead: time-parallel, no S x T array,
+    boundaries certified and escalated like em_step's."""
     onset, occ, silent, _, logz = _posteriors_host(y, lA, mu, sigma, False)
     return Posteriors(onset, occ, silent, logz)
 
@@ -477,10 +479,15 @@ def posterior_decode(y, lA, mu, sigma):
 
 
 def _posterior_plan(T, lA, mu, sigma):
-    """a plan that serves posteriors: the wave engine when it takes the model, else the strict engine"""
+    """a plan that serves posteriors: the wave engine when it takes the model, else the strict engine -- or the
+    blocked engine when option "engine" names it and the model fits (the blocked E-step's LDS limit, 4 templates)"""
     from .device import Plan
     plan = Plan(T, lA, mu, sigma)
-    if plan.info()["engine"] in (_lib.ENGINE_WAVE, _lib.ENGINE_STRICT):
+    engine = plan.info()["engine"]
+    if engine in (_lib.ENGINE_WAVE, _lib.ENGINE_STRICT):
+        return plan
+    if (engine == _lib.ENGINE_BLOCKED and _lib.get_option("engine") == _lib.ENGINE_BLOCKED
+            and plan.stats_len() > 0 and lA.N <= 4):
         return plan
     plan.close()
     prev = _lib.get_option("engine")

@@ -21,8 +21,8 @@ struct hmmsort_plan {
     WaveDev *wave = nullptr;
     int64_t C = 1;                      // channels (batched wave plans)
     std::vector<HostModel> models;      // per-channel models of a batched plan (models[0] == model)
-    // strict-path posteriors of the last hmmsort_plan_posteriors (the wave engine keeps its own): onset and
-    // trough-state mass (N x T each), arg-max state (T), partial sums for the expected counts
+    // strict- and blocked-path posteriors of the last hmmsort_plan_posteriors (the wave engine keeps its own): onset
+    // and trough-state mass (N x T each), arg-max state (T), partial sums for the expected counts
     double *post_on = nullptr, *post_tq = nullptr, *post_part = nullptr;
     int16_t *post_xm = nullptr;
     bool post_valid = false;
@@ -412,6 +412,7 @@ int hmmsort_plan_set_model(hmmsort_plan *p, const hmm_trans *tr, int64_t R, cons
         rc = ring_set_model(p->ring, m);
     } else {
         rc = generic_set_model(p->gen, m);
+        p->post_valid = false;
     }
     if (rc) return rc;
     p->model = std::move(m);
@@ -551,7 +552,10 @@ int hmmsort_plan_estep(hmmsort_plan *p, const double *d_y, double *d_stats, void
 {
     HS_CHECK(p && d_y && d_stats, HMMSORT_EINVAL, "plan_estep: null argument");
     if (p->wave) return wave_estep(p->wave, d_y, d_stats, (hipStream_t)stream);
-    if (p->gen && blocked_estep_supported(p->gen)) return blocked_estep(p->gen, d_y, d_stats, (hipStream_t)stream);
+    if (p->gen && blocked_estep_supported(p->gen)) {
+        p->post_valid = false;   // the posterior sweep shares the E-step's window and boundary records
+        return blocked_estep(p->gen, d_y, d_stats, (hipStream_t)stream);
+    }
     HS_CHECK(p->ring, HMMSORT_EUNSUP,
              "plan_estep: sufficient-statistics E-step needs the wave, ring or blocked engine (use hmmsort_em_step)");
     return ring_estep(p->ring, d_y, d_stats, (hipStream_t)stream);
@@ -1172,6 +1176,38 @@ static int strict_posteriors(hmmsort_plan *p, const double *d_y, double *d_onset
     return HMMSORT_OK;
 }
 
+// Blocked plan: the time-parallel E-step's sweep with the per-sample marginals kept (generic_estep.hip).  Nothing
+// of size S x T exists; the call only enqueues work on the caller's stream.
+static int blocked_plan_posteriors(hmmsort_plan *p, const double *d_y, double *d_onset, double *d_occ,
+                                   double *d_silent, double *d_logz, hipStream_t st)
+{
+    const HostModel &m = p->model;
+    const int64_t T = p->T, N = m.N;
+    p->post_valid = false;
+    auto own = [&](auto **q, size_t n) -> int {
+        if (*q) return HMMSORT_OK;
+        if (hipMalloc((void **)q, n) != hipSuccess) {
+            (void)hipGetLastError();
+            *q = nullptr;
+            set_error("plan_posteriors: hipMalloc of %zu bytes failed", n);
+            return HMMSORT_ENOMEM;
+        }
+        return HMMSORT_OK;
+    };
+    int rc;
+    if ((rc = own(&p->post_on, (size_t)N * T * 8)) || (rc = own(&p->post_tq, (size_t)N * T * 8)) ||
+        (rc = own(&p->post_xm, (size_t)T * 2)) || (rc = own(&p->post_part, (size_t)N * kPostParts * 8)))
+        return rc;
+    std::vector<int32_t> qv(N);
+    for (int64_t i = 0; i < N; i++) qv[i] = trough_value(m, i);
+    if ((rc = blocked_posteriors(p->gen, d_y, qv.data(), p->post_on, d_occ, d_silent, p->post_tq, p->post_xm, d_logz,
+                                 st)))
+        return rc;
+    if (d_onset) HS_HIP(hipMemcpyAsync(d_onset, p->post_on, (size_t)N * T * 8, hipMemcpyDeviceToDevice, st));
+    p->post_valid = true;
+    return HMMSORT_OK;
+}
+
 extern "C" {
 
 int hmmsort_plan_posteriors(hmmsort_plan *p, const double *d_y, double *d_onset, double *d_occ, double *d_silent,
@@ -1179,8 +1215,11 @@ int hmmsort_plan_posteriors(hmmsort_plan *p, const double *d_y, double *d_onset,
 {
     HS_CHECK(p && d_y, HMMSORT_EINVAL, "plan_posteriors: null argument");
     if (p->wave) return wave_posteriors(p->wave, d_y, d_onset, d_occ, d_silent, d_logz, (hipStream_t)stream);
+    if (p->gen && p->engine == HMMSORT_ENGINE_BLOCKED)
+        return blocked_plan_posteriors(p, d_y, d_onset, d_occ, d_silent, d_logz, (hipStream_t)stream);
     HS_CHECK(p->gen && p->engine == HMMSORT_ENGINE_STRICT, HMMSORT_EUNSUP,
-             "plan_posteriors: needs a wave plan (ring models) or a strict plan (any model); this plan runs engine %lld",
+             "plan_posteriors: needs a wave plan (ring models), a blocked plan (overlap models within the LDS limit) or "
+             "a strict plan (any model); this plan runs engine %lld",
              (long long)p->engine);
     return strict_posteriors(p, d_y, d_onset, d_occ, d_silent, d_logz, (hipStream_t)stream);
 }
@@ -1269,8 +1308,12 @@ int hmmsort_posteriors(const double *y, int64_t T, const int16_t *states, int64_
             rc = plan_create_engine(&h.plan, T, states, N, K, S, tr, R, mu, sigma, engine, halo);
             if (rc) return rc;
         }
-        if (!h.plan->wave && h.plan->engine != HMMSORT_ENGINE_STRICT) {
-            keep = false;                    // what the wave engine does not take: materialised alpha/beta
+        // what the wave engine does not take goes to the strict engine (materialised alpha/beta) unless the
+        // caller asked for the blocked engine by name and the model fits its LDS columns
+        const bool blocked_post = !h.plan->wave && h.plan->engine == HMMSORT_ENGINE_BLOCKED &&
+                                  opt.engine == HMMSORT_ENGINE_BLOCKED && blocked_post_supported(h.plan->gen);
+        if (!h.plan->wave && h.plan->engine != HMMSORT_ENGINE_STRICT && !blocked_post) {
+            keep = false;
             engine = HMMSORT_ENGINE_STRICT;
             h.drop_plan();
             continue;
@@ -1282,7 +1325,7 @@ int hmmsort_posteriors(const double *y, int64_t T, const int16_t *states, int64_
         HS_HIP(hipStreamSynchronize(h.st));
         int64_t diag[8];
         if ((rc = hmmsort_plan_diagnostics(h.plan, h.st, diag))) return rc;
-        if (!h.plan->wave || (diag[3] == 0 && diag[5] == 0) || !opt.escalate) break;
+        if (!(h.plan->wave || blocked_post) || (diag[3] == 0 && diag[5] == 0) || !opt.escalate) break;
         last_escalations() = attempt + 1;
         halo = next_halo(h.plan);
         if (attempt >= 3 || halo > T) {

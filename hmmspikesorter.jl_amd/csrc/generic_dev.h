@@ -50,6 +50,7 @@ struct GenericDev {
     double *d_es_win = nullptr, *d_es_rec = nullptr, *d_es_partG = nullptr, *d_es_partX = nullptr;
     double *d_es_inw = nullptr, *d_es_outw = nullptr, *d_es_tmp = nullptr;
     unsigned long long *d_es_diag = nullptr;
+    double *d_es_lls = nullptr, *d_es_partL = nullptr;   // posterior sweep: column sums of a block, log-likelihood terms
     int es_grid = 0;
     int64_t upd_bytes = 0;
     int threads = 256;

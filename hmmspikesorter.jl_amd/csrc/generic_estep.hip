@@ -25,6 +25,11 @@
 // X_i = sum_{t<T-1} xi_i(t) for the transitions i leaving the silent state (:229-261, normalised by the
 // all-transition total, which equals the gamma normaliser);  Gamma0 = sum_{t<T-1} gamma_1(t);  sum y^2.
 // sigma follows from  sum_t sum_j (y_t - m_j)^2 gamma_j(t) = sum y^2 - 2 sum_j m_j G1_j + sum_j m_j^2 G0_j.
+//
+// Posteriors (hmmsort_plan_posteriors on a blocked plan, DESIGN 3.5 "Blocked path"): the same sweep in a second
+// instantiation, bes_block_post, reduces the gamma of every owned sample over the workgroup into per-template
+// onset / occupancy / trough mass, the silent state's gamma and the arg-max state, and sums the log-likelihood in
+// the forward sweep.  The kernel body is generic_estep_block.inc, included once for each of the two kernels.
 #include <cmath>
 
 #include "fastmath.h"
@@ -52,6 +57,20 @@ struct BesArgs {
     double *partX;  // [nblk][nsrc1 + 2]: X_i | Gamma0 | sum y^2
 };
 
+// Outputs of the posterior instantiation (bes_block_post): the per-sample marginals of hmmsort_plan_posteriors
+// instead of the block statistics.  Reduction slots of a step: [0..2] as below, then 3 per template (onset,
+// occupancy, trough), the silent state's gamma, the arg-max value and its state.
+constexpr int kPostMaxN = 4;   // templates the posterior instantiations hold partial sums for
+struct BesPost {
+    const int16_t *states;   // [S][N] phases, 1 = silent
+    int qv[kPostMaxN];       // trough phase of each template
+    int N, nred;             // nred = 3 + 3 N + 3
+    double *onset, *occ, *tq, *silent;   // [N][T] x 3, [T]; occ and silent may be null
+    int16_t *xm;             // [T]
+    double *lls;             // [gridDim.x][B] column sums of the owned samples (forward sweep)
+    double *partL;           // [nblk] sum over the owned samples of log(column sum) + emission shift
+};
+
 __device__ __forceinline__ double wsum(double v)
 {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -66,290 +85,21 @@ __device__ __forceinline__ double wmax(double v)
 // red[par][slot][wave]: slot 0 column sum, 1 emission exponent maximum of the NEXT column, 2 gamma normaliser
 constexpr int kRedW = 16;
 
-// NTH = threads per workgroup (the launch bound decides the register budget: 512 threads leave 256 VGPRs per
-// lane, which the per-state constants of 8 states per thread need; under a 1024-thread bound they spill 776 B)
-template <int SPT, int NTH>
-__global__ __launch_bounds__(NTH) void bes_block(BesArgs a)
+#define BES_POST 0
+#include "generic_estep_block.inc"
+#undef BES_POST
+#define BES_POST 1
+#include "generic_estep_block.inc"
+#undef BES_POST
+
+// logz = sum of the blocks' terms in block order + T (-log(sigma sqrt(2 pi)))
+__global__ __launch_bounds__(64) void bes_logz(int nblk, const double *__restrict__ partL, double c0T,
+                                               double *__restrict__ logz)
 {
-    extern __shared__ double sh[];
-    const int S = a.S, B = a.B, H = a.H, tid = threadIdx.x, nt = blockDim.x;
-    const int wv = tid >> 6, nw = nt >> 6;
-    double *col[2] = {sh, sh + S};
-    double *red = sh + 2 * S;                      // [2][3][kRedW]
-    double *xterm = red + 2 * 3 * kRedW;           // [2][nsrc1]
-    double *xw = xterm + 2 * a.nsrc1, *xd = xw + a.nsrc1;   // the silent state's outgoing transitions: weight, destination
-    for (int i = tid; i < a.nsrc1; i += nt) { xw[i] = a.out_w[i]; xd[i] = (double)a.out_dst[i]; }
-    const int64_t T = a.T;
-    // per-thread constants of its SPT states.  93 % of the states of an overlap model have ONE incoming and one
-    // outgoing transition (the interior of the pair lattice): the first edge of each list lives in registers, the
-    // rest of a list is read from the (L2-resident) CSR arrays -- one dependent global load per edge and step was
-    // what bounded the first version (98 -> see DESIGN 3.1c)
-    double m[SPT], en[SPT], wi0[SPT], wo0[SPT];
-    int p0[SPT], p1[SPT], q0[SPT], q1[SPT], si0[SPT], do0[SPT];
-#pragma unroll
-    for (int k = 0; k < SPT; k++) {
-        const int j = tid + k * nt;
-        const bool ok = j < S;
-        m[k] = ok ? a.mean[j] : 0.0;
-        p0[k] = ok ? a.in_ptr[j] : 0;  p1[k] = ok ? a.in_ptr[j + 1] : 0;
-        q0[k] = ok ? a.out_ptr[j] : 0; q1[k] = ok ? a.out_ptr[j + 1] : 0;
-        const bool hi = p1[k] > p0[k], ho = q1[k] > q0[k];
-        si0[k] = hi ? a.in_src[p0[k]] : 0;  wi0[k] = hi ? a.in_w[p0[k]] : 0.0;
-        do0[k] = ho ? a.out_dst[q0[k]] : 0; wo0[k] = ho ? a.out_w[q0[k]] : 0.0;
-        p0[k] += hi; q0[k] += ho;             // the lists now start at their second edge
-    }
-    double *win = a.win + (size_t)blockIdx.x * B * S;
-
-    auto reduce3 = [&](int par, double s, double mx, double z) {
-        s = wsum(s); mx = wmax(mx); z = wsum(z);
-        if ((tid & 63) == 0) {
-            red[(par * 3 + 0) * kRedW + wv] = s;
-            red[(par * 3 + 1) * kRedW + wv] = mx;
-            red[(par * 3 + 2) * kRedW + wv] = z;
-        }
-    };
-    auto read3 = [&](int par, double &s, double &mx, double &z) {
-        s = 0.0; mx = -INFINITY; z = 0.0;
-        for (int w = 0; w < nw; w++) {
-            s += red[(par * 3 + 0) * kRedW + w];
-            mx = fmax(mx, red[(par * 3 + 1) * kRedW + w]);
-            z += red[(par * 3 + 2) * kRedW + w];
-        }
-    };
-
-    for (int blk = blockIdx.x; blk < a.nblk; blk += gridDim.x) {
-        const int64_t lo = (int64_t)blk * B, hi = (lo + B) < T ? (lo + B) : T;
-        double *rec = a.rec + (size_t)blk * 6 * S;
-        // ------------------------------------------------------------------ forward
-        {
-            const int64_t t0 = lo > H ? lo - H : 0;   // a warm-up reaching the start of the data is the exact sweep
-            // column t0 = shifted emissions (baumwelch.jl:36 at the start of the data; a flat start elsewhere)
-            const double y0 = a.y[t0];
-            double pm = -INFINITY;
-#pragma unroll
-            for (int k = 0; k < SPT; k++) {
-                const double d = y0 - m[k];
-                en[k] = -(d * d) * a.rden;
-                if (tid + k * nt < S) pm = fmax(pm, en[k]);
-            }
-            __syncthreads();                       // previous block is done with red / col
-            reduce3(0, 0.0, pm, 0.0);
-            __syncthreads();
-            double s, emax, z;
-            read3(0, s, emax, z);
-            __syncthreads();
-            const double y1 = a.y[(t0 + 1) < T ? (t0 + 1) : t0];
-            double ps = 0.0;
-            pm = -INFINITY;
-#pragma unroll
-            for (int k = 0; k < SPT; k++) {
-                const int j = tid + k * nt;
-                if (j < S) {
-                    const double v = fexp(en[k] - emax);
-                    col[0][j] = v;
-                    ps += v;
-                    if (t0 >= lo) win[j] = v;
-                    const double d = y1 - m[k];
-                    en[k] = -(d * d) * a.rden;
-                    pm = fmax(pm, en[k]);
-                }
-            }
-            reduce3(0, ps, pm, 0.0);
-            int par = 0;
-            double ynext = a.y[(t0 + 2) < T ? (t0 + 2) : T - 1];   // global loads run one step ahead of their use
-            for (int64_t t = t0 + 1; t < hi; t++) {
-                const double yn = ynext;                            // y[t + 1]
-                ynext = a.y[(t + 2) < T ? (t + 2) : T - 1];
-                __syncthreads();
-                read3(par, s, emax, z);
-                const double inv = 1.0 / s;
-                const double *prev = col[par];
-                double *cur = col[par ^ 1];
-                ps = 0.0; pm = -INFINITY;
-#pragma unroll
-                for (int k = 0; k < SPT; k++) {
-                    const int j = tid + k * nt;
-                    if (j < S) {
-                        double acc = prev[si0[k]] * wi0[k];
-                        for (int e = p0[k]; e < p1[k]; e++) acc += prev[a.in_src[e]] * a.in_w[e];   // :47
-                        const double v = (acc * inv) * fexp(en[k] - emax);
-                        cur[j] = v;
-                        ps += v;
-                        if (t >= lo) win[(size_t)(t - lo) * S + j] = v;
-                        if (t == lo - 1) rec[j] = v;
-                        if (t == hi - 1) rec[S + j] = v;
-                        const double d = yn - m[k];
-                        en[k] = -(d * d) * a.rden;
-                        pm = fmax(pm, en[k]);
-                    }
-                }
-                par ^= 1;
-                reduce3(par, ps, pm, 0.0);
-            }
-        }
-        // ------------------------------------------------------------------ backward + statistics
-        {
-            const int64_t te = (hi - 1 + H) < (T - 1) ? (hi - 1 + H) : (T - 1);
-            double g[SPT], G0[SPT], G1[SPT];
-#pragma unroll
-            for (int k = 0; k < SPT; k++) { g[k] = 0.0; G0[k] = 0.0; G1[k] = 0.0; }
-            double X = 0.0, Gam0 = 0.0;            // X: thread i < nsrc1 owns transition i; Gam0: thread 0
-            // emission exponents of column te and their maximum
-            const double ye = a.y[te];
-            double pm = -INFINITY;
-#pragma unroll
-            for (int k = 0; k < SPT; k++) {
-                const double d = ye - m[k];
-                en[k] = -(d * d) * a.rden;
-                if (tid + k * nt < S) pm = fmax(pm, en[k]);
-            }
-            __syncthreads();
-            reduce3(0, 0.0, pm, 0.0);
-            __syncthreads();
-            double s, emax, z;
-            read3(0, s, emax, z);
-            __syncthreads();
-            // column te: beta = 1 (:80 at the end of the data; a flat start elsewhere).  nxt = b(te) * beta(te)
-            double ps = 0.0, pz = 0.0;
-            pm = -INFINITY;
-            {
-                const double yp = a.y[te > 0 ? te - 1 : 0];
-#pragma unroll
-                for (int k = 0; k < SPT; k++) {
-                    const int j = tid + k * nt;
-                    if (j < S) {
-                        const double cur = 1.0;
-                        ps += cur;
-                        if (te < hi) {             // the last sample of the data is an owned sample
-                            const double al = win[(size_t)(te - lo) * S + j];
-                            g[k] = al * cur;
-                            pz += g[k];
-                            if (te == lo) rec[4 * S + j] = cur;
-                        }
-                        if (te == hi) rec[3 * S + j] = cur;
-                        col[0][j] = cur * fexp(en[k] - emax);
-                        const double d = yp - m[k];
-                        en[k] = -(d * d) * a.rden;
-                        pm = fmax(pm, en[k]);
-                    }
-                }
-            }
-            reduce3(0, ps, pm, pz);
-            int par = 0;
-            int64_t tprev = te;                    // time whose g[] / xterm wait for their normaliser
-            // global loads one step ahead: y[t-1] for the next emissions, alpha(t) of the owned samples
-            double y_cur = a.y[te], y_m1 = a.y[te > 0 ? te - 1 : 0], y_m2 = a.y[te > 1 ? te - 2 : 0];
-            double alc[SPT];
-#pragma unroll
-            for (int k = 0; k < SPT; k++) {
-                const int j = tid + k * nt;
-                alc[k] = (j < S && te - 1 < hi && te - 1 >= lo) ? win[(size_t)(te - 1 - lo) * S + j] : 0.0;
-            }
-            for (int64_t t = te - 1; t >= lo; t--) {
-                // y_cur = y[t+1], y_m1 = y[t], y_m2 = y[t-1]; alc = alpha(t)
-                const double yv = y_cur, yp = y_m2;
-                y_cur = y_m1; y_m1 = y_m2;
-                y_m2 = a.y[t > 1 ? t - 2 : 0];
-                double aln[SPT];
-                const bool own_next = t - 1 < hi && t - 1 >= lo;
-#pragma unroll
-                for (int k = 0; k < SPT; k++) {
-                    const int j = tid + k * nt;
-                    aln[k] = (j < S && own_next) ? win[(size_t)(t - 1 - lo) * S + j] : 0.0;
-                }
-                __syncthreads();
-                read3(par, s, emax, z);
-                const double inv = 1.0 / s;
-                // lagged statistics of time tprev = t + 1 (its normaliser z has just arrived)
-                if (tprev < hi) {
-                    const double rz = 1.0 / z;
-#pragma unroll
-                    for (int k = 0; k < SPT; k++) {
-                        const int j = tid + k * nt;
-                        if (j < S) {
-                            const double gm = g[k] * rz;
-                            G0[k] += gm;
-                            G1[k] += gm * yv;
-                            if (tprev == hi - 1) rec[2 * S + j] = gm;
-                        }
-                    }
-                    if (tprev <= T - 2) {
-                        if (tid < a.nsrc1) X += xterm[par * a.nsrc1 + tid] * rz;
-                        if (tid == 0) Gam0 += g[0] * rz;
-                    }
-                }
-                const double *nxt = col[par];
-                double *out = col[par ^ 1];
-                const bool own = t < hi;
-                ps = 0.0; pz = 0.0; pm = -INFINITY;
-#pragma unroll
-                for (int k = 0; k < SPT; k++) {
-                    const int j = tid + k * nt;
-                    if (j < S) {
-                        double cur = nxt[do0[k]] * wo0[k];
-                        for (int e = q0[k]; e < q1[k]; e++) cur += nxt[a.out_dst[e]] * a.out_w[e];   // :94
-                        ps += cur;
-                        if (own) {
-                            const double al = alc[k];
-                            g[k] = al * cur;
-                            pz += g[k];
-                            if (t == lo) rec[4 * S + j] = cur;
-                            if (j == 0 && t <= T - 2)
-                                for (int i = 0; i < a.nsrc1; i++)   // :240  alpha_1(t) a_1j b_j(t+1) beta_j(t+1)
-                                    xterm[(par ^ 1) * a.nsrc1 + i] = al * (nxt[(int)xd[i]] * xw[i]);
-                        }
-                        if (t == hi) rec[3 * S + j] = cur;
-                        out[j] = (cur * inv) * fexp(en[k] - emax);
-                        const double d = yp - m[k];
-                        en[k] = -(d * d) * a.rden;
-                        pm = fmax(pm, en[k]);
-                    }
-                }
-                par ^= 1;
-                reduce3(par, ps, pm, pz);
-                tprev = t;
-#pragma unroll
-                for (int k = 0; k < SPT; k++) alc[k] = aln[k];
-            }
-            // flush the statistics of the block's first sample
-            __syncthreads();
-            read3(par, s, emax, z);
-            if (tprev < hi) {
-                const double rz = 1.0 / z, yv = y_cur;              // y[tprev]
-#pragma unroll
-                for (int k = 0; k < SPT; k++) {
-                    const int j = tid + k * nt;
-                    if (j < S) {
-                        const double gm = g[k] * rz;
-                        G0[k] += gm;
-                        G1[k] += gm * yv;
-                        if (tprev == hi - 1) rec[2 * S + j] = gm;
-                        if (tprev == lo) rec[5 * S + j] = gm;
-                    }
-                }
-                if (tprev <= T - 2) {
-                    if (tid < a.nsrc1) X += xterm[par * a.nsrc1 + tid] * rz;
-                    if (tid == 0) Gam0 += g[0] * rz;
-                }
-            }
-            double *pG = a.partG + (size_t)blk * 2 * S;
-#pragma unroll
-            for (int k = 0; k < SPT; k++) {
-                const int j = tid + k * nt;
-                if (j < S) { pG[j] = G0[k]; pG[S + j] = G1[k]; }
-            }
-            double *pX = a.partX + (size_t)blk * (a.nsrc1 + 2);
-            if (tid < a.nsrc1) pX[tid] = X;
-            if (tid == 0) pX[a.nsrc1] = Gam0;
-            double y2 = 0.0;
-            for (int64_t t = lo + tid; t < hi; t += nt) { const double v = a.y[t]; y2 += v * v; }
-            __syncthreads();
-            reduce3(0, y2, 0.0, 0.0);
-            __syncthreads();
-            read3(0, s, emax, z);
-            if (tid == 0) pX[a.nsrc1 + 1] = s;
-        }
-    }
+    double acc = 0.0;
+    for (int b = threadIdx.x; b < nblk; b += 64) acc += partL[b];
+    acc = wsum(acc);
+    if (threadIdx.x == 0) logz[0] = acc + c0T;
 }
 
 // Boundary certificates.  Boundary c (between blocks c and c+1, samples hi-1 | hi):
@@ -480,7 +230,20 @@ bool blocked_estep_supported(const GenericDev *g)
 
 int64_t blocked_stats_len(const GenericDev *g) { return 2 * g->S + g->nsrc1 + 2; }
 
-int blocked_estep(GenericDev *g, const double *d_y, double *d_stats, hipStream_t st)
+// LDS of the posterior instantiation: the E-step's plus 3 N + 3 reduction slots per parity.  The E-step's bound of
+// 156 KB leaves 4 KB of the CU's 160 KB: enough for 4 templates (3 840 B more)
+static size_t post_lds_bytes(const GenericDev *g)
+{
+    return (2 * (size_t)g->S + 2 * (size_t)(3 + 3 * g->N + 3) * kRedW + 4 * (size_t)g->nsrc1) * sizeof(double);
+}
+
+bool blocked_post_supported(const GenericDev *g)
+{
+    return blocked_estep_supported(g) && g->N <= kPostMaxN && post_lds_bytes(g) <= 160 * 1024;
+}
+
+// the E-step (pp == nullptr) or the posterior sweep over the same blocks
+static int bes_run(GenericDev *g, const double *d_y, double *d_stats, BesPost *pp, hipStream_t st)
 {
     HS_CHECK(blocked_estep_supported(g), HMMSORT_EUNSUP, "blocked E-step: model too large for the LDS columns");
     const size_t S = (size_t)g->S, nb = (size_t)g->nblk;
@@ -489,7 +252,7 @@ int blocked_estep(GenericDev *g, const double *d_y, double *d_stats, hipStream_t
     int dev = 0, ncu = 256;
     HS_HIP(hipGetDevice(&dev));
     HS_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-    const size_t lds = (2 * S + 2 * 3 * kRedW + 4 * (size_t)g->nsrc1) * sizeof(double);
+    const size_t lds = pp ? post_lds_bytes(g) : (2 * S + 2 * 3 * kRedW + 4 * (size_t)g->nsrc1) * sizeof(double);
     const int per_cu = lds <= 76 * 1024 && nt <= 512 ? 2 : 1;
     const int grid = (int)std::min<size_t>(nb, (size_t)ncu * per_cu);
     int rc;
@@ -499,6 +262,9 @@ int blocked_estep(GenericDev *g, const double *d_y, double *d_stats, hipStream_t
         (rc = balloc(&g->d_es_partX, nb * (g->nsrc1 + 2), &g->bytes)) ||
         (rc = balloc(&g->d_es_inw, (size_t)g->R, &g->bytes)) || (rc = balloc(&g->d_es_outw, (size_t)g->R, &g->bytes)) ||
         (rc = balloc(&g->d_es_diag, 4, &g->bytes)) || (rc = balloc(&g->d_es_tmp, 2 * S + g->K * g->N, &g->bytes)))
+        return rc;
+    if (pp && ((rc = balloc(&g->d_es_lls, (size_t)grid * g->B, &g->bytes)) ||
+               (rc = balloc(&g->d_es_partL, nb + 1, &g->bytes))))
         return rc;
     g->es_grid = grid;
     hipLaunchKernelGGL(bes_weights, dim3((unsigned)((g->R + 255) / 256)), dim3(256), 0, st, g->d_in_lp, (int)g->R, g->d_es_inw);
@@ -521,7 +287,23 @@ int blocked_estep(GenericDev *g, const double *d_y, double *d_stats, hipStream_t
     // register budget by launch bound: 1-2 states per thread fit 128 VGPRs (bound 1024: more waves per SIMD,
     // S = 900: 15.5 against 22 ms per 10^6 samples); 4-8 states per thread need the 256 of a 512-thread bound
     // (S = 3600: 54 against 96 ms)
-    if (nt <= 512) rc = spt <= 1 ? launch(bes_block<1, 1024>) : spt <= 2 ? launch(bes_block<2, 1024>)
+    if (pp) {
+        BesPost po = *pp;
+        po.lls = g->d_es_lls; po.partL = g->d_es_partL;
+        auto launch_post = [&](auto kern) -> int {
+            if (lds > 64 * 1024)
+                HS_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(nt), lds, st, a, po);
+            return HMMSORT_OK;
+        };
+        // the same thread counts and launch bounds as the E-step; partial sums for 2 or 4 templates
+#define BES_LAUNCH_POST(NP)                                                                                              \
+    (nt <= 512 ? (spt <= 1 ? launch_post(bes_block_post<1, 1024, NP>) : spt <= 2 ? launch_post(bes_block_post<2, 1024, NP>) \
+                  : spt <= 4 ? launch_post(bes_block_post<4, 512, NP>) : launch_post(bes_block_post<8, 512, NP>))  \
+               : (spt <= 8 ? launch_post(bes_block_post<8, 1024, NP>) : launch_post(bes_block_post<16, 1024, NP>)))
+        rc = po.N <= 2 ? BES_LAUNCH_POST(2) : BES_LAUNCH_POST(4);
+#undef BES_LAUNCH_POST
+    } else if (nt <= 512) rc = spt <= 1 ? launch(bes_block<1, 1024>) : spt <= 2 ? launch(bes_block<2, 1024>)
                         : spt <= 4 ? launch(bes_block<4, 512>) : launch(bes_block<8, 512>);
     else rc = spt <= 8 ? launch(bes_block<8, 1024>) : launch(bes_block<16, 1024>);
     if (rc) return rc;
@@ -529,9 +311,41 @@ int blocked_estep(GenericDev *g, const double *d_y, double *d_stats, hipStream_t
     if (nb > 1)
         hipLaunchKernelGGL(bes_check, dim3((unsigned)(nb - 1), 2), dim3(256), 0, st, (int)S, (int)nb, 1e-9, g->d_es_rec,
                            g->d_es_diag);
-    hipLaunchKernelGGL(bes_reduce, dim3((unsigned)blocked_stats_len(g)), dim3(64), 0, st, (int)S, (int)nb, g->nsrc1,
-                       g->d_es_partG, g->d_es_partX, d_stats);
+    if (!pp)
+        hipLaunchKernelGGL(bes_reduce, dim3((unsigned)blocked_stats_len(g)), dim3(64), 0, st, (int)S, (int)nb, g->nsrc1,
+                           g->d_es_partG, g->d_es_partX, d_stats);
     HS_HIP(hipGetLastError());
+    return HMMSORT_OK;
+}
+
+int blocked_estep(GenericDev *g, const double *d_y, double *d_stats, hipStream_t st)
+{
+    return bes_run(g, d_y, d_stats, nullptr, st);
+}
+
+int blocked_posteriors(GenericDev *g, const double *d_y, const int32_t *trough, double *d_onset, double *d_occ,
+                       double *d_silent, double *d_tq, int16_t *d_xm, double *d_logz, hipStream_t st)
+{
+    HS_CHECK(blocked_estep_supported(g), HMMSORT_EUNSUP,
+             "plan_posteriors: the blocked path holds two columns of S doubles in LDS (156 KB: %d states at most, this "
+             "model has %lld); use the strict engine (option \"engine\" = HMMSORT_ENGINE_STRICT)",
+             (int)((156 * 1024 / 8 - 2 * 3 * kRedW - 4 * g->nsrc1) / 2), (long long)g->S);
+    HS_CHECK(blocked_post_supported(g), HMMSORT_EUNSUP,
+             "plan_posteriors: the blocked path takes up to %d templates within 160 KB of LDS (this model: %lld templates, "
+             "%zu bytes); use the strict engine", kPostMaxN, (long long)g->N, post_lds_bytes(g));
+    BesPost po;
+    po.states = g->d_states;
+    for (int l = 0; l < kPostMaxN; l++) po.qv[l] = l < g->N ? trough[l] : 0;
+    po.N = (int)g->N; po.nred = 3 + 3 * (int)g->N + 3;
+    po.onset = d_onset; po.occ = d_occ; po.tq = d_tq; po.silent = d_silent; po.xm = d_xm;
+    po.lls = nullptr; po.partL = nullptr;
+    int rc = bes_run(g, d_y, nullptr, &po, st);
+    if (rc) return rc;
+    if (d_logz) {
+        hipLaunchKernelGGL(bes_logz, dim3(1), dim3(64), 0, st, (int)g->nblk, g->d_es_partL,
+                           (double)g->T * (-kLog2Pi - g->lsig), d_logz);
+        HS_HIP(hipGetLastError());
+    }
     return HMMSORT_OK;
 }
 
@@ -561,7 +375,7 @@ int blocked_estep_diagnostics(GenericDev *g, hipStream_t st, int64_t diag[8])
 void blocked_estep_destroy(GenericDev *g)
 {
     void *ptrs[] = {g->d_es_win, g->d_es_rec, g->d_es_partG, g->d_es_partX, g->d_es_inw, g->d_es_outw,
-                    g->d_es_diag, g->d_es_tmp};
+                    g->d_es_diag, g->d_es_tmp, g->d_es_lls, g->d_es_partL};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
 }

@@ -121,6 +121,11 @@ bool blocked_estep_supported(const GenericDev *g);
 int64_t blocked_stats_len(const GenericDev *g);
 int blocked_estep(GenericDev *g, const double *d_y, double *d_stats, hipStream_t st);
 int blocked_mstep(GenericDev *g, const double *d_stats, double *d_out, hipStream_t st);
+// the E-step's sweep with the per-sample marginals kept (generic_estep.hip, bes_block_post): onset, occ, tq [N][T],
+// silent [T], arg-max state xm [T], logz; d_occ, d_silent and d_logz may be null.  trough: N phases (host)
+bool blocked_post_supported(const GenericDev *g);
+int blocked_posteriors(GenericDev *g, const double *d_y, const int32_t *trough, double *d_onset, double *d_occ,
+                       double *d_silent, double *d_tq, int16_t *d_xm, double *d_logz, hipStream_t st);
 
 // ring (time-parallel) engine
 int ring_create(RingDev **r, const HostModel &m, int64_t T, int64_t block_req, int64_t halo_req);

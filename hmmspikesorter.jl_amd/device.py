@@ -164,9 +164,11 @@ class Plan:
 
     def posteriors(self, d_y, d_onset=None, d_occ=None, d_silent=None, d_logz=None, stream=0):
         """smoothed state posteriors of d_y under the plan's model, device to device (hmmsort_plan_posteriors):
-        onset / occ [C][N][T], silent [C][T], logz [C] doubles; None skips an output.  Wave plans (ring models)
-        and strict plans (any model); the plan keeps the posteriors for posterior_decode / spike_confidence /
-        expected_counts until its next E-step or posterior call."""
+        onset / occ [C][N][T], silent [C][T], logz [C] doubles; None skips an output.  Wave plans (ring models),
+        blocked plans (overlap models within the blocked E-step's LDS limit, up to 4 templates; asynchronous,
+        no S x T workspace) and strict plans (any model, 2 x S x T doubles); the plan keeps the posteriors for
+        posterior_decode / spike_confidence / expected_counts until its next E-step, set_model or posterior
+        call."""
         check(lib().hmmsort_plan_posteriors(self._h, _dptr(d_y), _dptr(d_onset), _dptr(d_occ), _dptr(d_silent),
                                             _dptr(d_logz), C.c_void_p(stream)))
 

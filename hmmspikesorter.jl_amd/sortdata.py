@@ -54,7 +54,8 @@ def load_data(path, name="data"):
 
 
 def _chunk_confidence(templates, dataf, ml_seq, chunksize, jitter):
-    """spike times and confidences of the decoded path, chunk by chunk of the chunked fit, on the strict path"""
+    """spike times and confidences of the decoded path, chunk by chunk of the chunked fit, on the strict path (the
+    blocked path under option "engine" = ENGINE_BLOCKED)"""
     n, N = len(ml_seq), templates.state_matrix.N
     times, conf = [[] for _ in range(N)], [[] for _ in range(N)]
     for lo in range(0, n, chunksize):
@@ -78,9 +79,12 @@ def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_temp
 
     `confidence=True` (an extension; default off, output unchanged) adds "spiketimes" (per template, 1-based
     samples as extract_spiketimes) and "confidence" (per spike, api.spike_confidence with `jitter`), computed per
-    chunk of the chunked fit from the chunk's own posteriors.  The decode model resolves overlaps, so this runs
-    on the strict path (alpha and beta materialised, 2 x S x chunksize doubles): slow, and for the 3- and
-    4-template overlap models only feasible with a small `chunksize`."""
+    chunk of the chunked fit from the chunk's own posteriors.  The decode model resolves overlaps, so by default
+    this runs on the strict path (alpha and beta materialised, 2 x S x chunksize doubles): slow, and for the 3-
+    and 4-template overlap models only feasible with a small `chunksize`.  With option "engine" set to
+    ENGINE_BLOCKED the posteriors of a model within the blocked E-step's LDS limit come from the time-parallel
+    blocked sweep instead (no S x chunksize array; 2 x 60 at the default chunksize is routine); larger models
+    still take the strict path."""
     spike_forms = np.asarray(spike_forms, dtype=np.float64)
     nstates, _nchannels, ntemplates = spike_forms.shape
     pp = np.atleast_1d(np.asarray(p, dtype=np.float64))

@@ -297,11 +297,17 @@ int hmmsort_plan_extract_spiketimes(hmmsort_plan *plan, const int16_t *d_x, int6
  *   d_silent [C][T]     mass of state 1
  *   d_logz   [C]        log-likelihood of the recording, logsumexp_s alpha_{T-1}(s)
  * Any output may be NULL.  Wave plans (ring models, up to 16 templates) run the forward sweep, the unfused
- * backward sweep and one streaming pass; strict plans (any model; option "engine" = HMMSORT_ENGINE_STRICT)
- * materialise alpha and beta (2 x S x T doubles, bounded by "strict_limit_mb": HMMSORT_ENOMEM beyond it) and
- * synchronise the stream.  Other plans: HMMSORT_EUNSUP.  A time shard (hmmsort_plan_set_shard): HMMSORT_EINVAL.
- * The warm-up certificates of a wave plan run and count into hmmsort_plan_diagnostics as in an E-step.
- * The plan keeps the posteriors for the three calls below until its next E-step or posterior call. */
+ * backward sweep and one streaming pass.  Blocked plans (overlap models; option "engine" =
+ * HMMSORT_ENGINE_BLOCKED, or AUTO from 4 096 samples) run the time-parallel E-step's sweep with the per-sample
+ * marginals kept: no S x T array, asynchronous on `stream`; the model must fit the blocked E-step (two columns
+ * of S doubles within 156 KB of LDS, about 9 900 states) and have at most 4 templates, else HMMSORT_EUNSUP
+ * naming the limit.  Strict plans (any model; option "engine" = HMMSORT_ENGINE_STRICT) materialise alpha and
+ * beta (2 x S x T doubles, bounded by "strict_limit_mb": HMMSORT_ENOMEM beyond it) and synchronise the stream.
+ * Ring-engine plans: HMMSORT_EUNSUP.  A time shard (hmmsort_plan_set_shard; wave plans only): HMMSORT_EINVAL.
+ * The warm-up certificates of a wave or blocked plan run and count into hmmsort_plan_diagnostics (diag[3..6])
+ * as in an E-step; a caller that sees diag[3] or diag[5] != 0 widens option "halo" and repeats the call.
+ * The plan keeps the posteriors for the three calls below until its next E-step, hmmsort_plan_set_model or
+ * posterior call. */
 int hmmsort_plan_posteriors(hmmsort_plan *plan, const double *d_y, double *d_onset, double *d_occ,
                             double *d_silent, double *d_logz, void *stream);
 /* Maximum-posterior-marginal decode: d_xm[t] = arg max_s gamma_t(s), 1-based like the Viterbi path, ties to
@@ -318,7 +324,10 @@ int hmmsort_plan_spike_confidence(hmmsort_plan *plan, const int16_t *d_x, int64_
  * recording).  counts_out: [C][N] on the host.  Synchronises the stream. */
 int hmmsort_plan_expected_counts(hmmsort_plan *plan, double *counts_out, void *stream);
 /* Host-buffer form (model arguments as hmmsort_em_step, same plan cache and escalation): onset / occ (N x T,
- * template-major), silent (T), xm (T), logz (1); NULL skips an output. */
+ * template-major), silent (T), xm (T), logz (1); NULL skips an output.  A model the wave engine does not take
+ * runs on the strict engine, unless option "engine" is HMMSORT_ENGINE_BLOCKED and the model fits the blocked
+ * posterior path: then on the blocked engine, whose failed certificates widen the warm-up (counted in option
+ * "last_escalations") and finally fall back to the strict engine. */
 int hmmsort_posteriors(const double *y, int64_t T, const int16_t *states, int64_t N, int64_t K, int64_t S,
                        const hmm_trans *tr, int64_t R, const double *mu, double sigma, double *onset,
                        double *occ, double *silent, int16_t *xm, double *logz);
