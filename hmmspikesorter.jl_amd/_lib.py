@@ -17,6 +17,11 @@ assert TRANS_DTYPE.itemsize == 24
 
 OK, EINVAL, ENOMEM, EHIP, ENOCONV, EUNSUP = 0, -1, -2, -3, -4, -5
 ENGINE_AUTO, ENGINE_STRICT, ENGINE_RING, ENGINE_BLOCKED, ENGINE_WAVE = 0, 1, 2, 3, 4
+# option "blocked_hbm_columns": the blocked E-step / posteriors with their state columns in device memory.  OFF
+# (default): models past the LDS limit (~9 900 states) are refused as before; AUTO: they take the device-memory
+# kernels; FORCE: every blocked plan does (cross-checks).  A plan keeps the value it was created under.
+OPT_BLOCKED_HBM_COLUMNS = "blocked_hbm_columns"
+HBM_COLUMNS_OFF, HBM_COLUMNS_AUTO, HBM_COLUMNS_FORCE = 0, 1, 2
 
 
 class HmmsortError(RuntimeError):

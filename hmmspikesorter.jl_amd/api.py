@@ -467,7 +467,8 @@ def posteriors(y, lA, mu, sigma):
     engine; any other model on the strict engine from materialised alpha/beta (2 x S x T doubles on the
     device: short signals only).  With option "engine" set to ENGINE_BLOCKED an overlap model whose two state
     columns fit the LDS (up to 4 templates) runs on the blocked engine instead: time-parallel, no S x T array,
-    boundaries certified and escalated like em_step's."""
+    boundaries certified and escalated like em_step's.  With option "blocked_hbm_columns" = 1 as well, so does a
+    model past that limit (3 x 60 and 4 x 60 with overlaps): its columns live in device memory."""
     onset, occ, silent, _, logz = _posteriors_host(y, lA, mu, sigma, False)
     return Posteriors(onset, occ, silent, logz)
 
@@ -480,7 +481,8 @@ def posterior_decode(y, lA, mu, sigma):
 
 def _posterior_plan(T, lA, mu, sigma):
     """a plan that serves posteriors: the wave engine when it takes the model, else the strict engine -- or the
-    blocked engine when option "engine" names it and the model fits (the blocked E-step's LDS limit, 4 templates)"""
+    blocked engine when option "engine" names it and the model fits (4 templates; the blocked E-step's LDS limit,
+    or any size under option "blocked_hbm_columns": stats_len() > 0 says which)"""
     from .device import Plan
     plan = Plan(T, lA, mu, sigma)
     engine = plan.info()["engine"]

@@ -74,7 +74,7 @@ struct PlanGuard {
 struct HostSlot {
     hmmsort_plan *plan = nullptr;
     DevBuf dy, dx, dll, dstats, dout;
-    int64_t T = 0, engine_opt = 0, block = 0, halo = 0;
+    int64_t T = 0, engine_opt = 0, block = 0, halo = 0, hbm_cols = 0;
     int device = 0;
     // every slot works on a stream of its own and waits for that stream only: host threads that decode or
     // train at the same time overlap on the device instead of meeting in hipDeviceSynchronize
@@ -116,7 +116,7 @@ std::unique_ptr<HostSlot> take_slot(int64_t T, const int16_t *states, int64_t N,
         HostSlot &h = *g_slots[i];
         const HostModel &m = h.plan->model;
         if (h.T != T || h.device != dev || h.engine_opt != opt.engine || h.block != opt.block ||
-            h.halo != opt.halo || m.N != N || m.K != K || m.S != S)
+            h.halo != opt.halo || h.hbm_cols != opt.blocked_hbm_columns || m.N != N || m.K != K || m.S != S)
             continue;
         if (memcmp(m.states.data(), states, m.states.size() * sizeof(int16_t))) continue;
         std::unique_ptr<HostSlot> out = std::move(g_slots[i]);
@@ -143,6 +143,7 @@ std::unique_ptr<HostSlot> new_slot(int64_t T, const Options &opt)
     h->engine_opt = opt.engine;
     h->block = opt.block;
     h->halo = opt.halo;
+    h->hbm_cols = opt.blocked_hbm_columns;
     if (hipGetDevice(&h->device) != hipSuccess) (void)hipGetLastError();
     if (hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) != hipSuccess) {
         (void)hipGetLastError();
@@ -222,6 +223,7 @@ int plan_create_engine(hmmsort_plan **out, int64_t T, const int16_t *states, int
         // overlap models and other lists the ring engine does not take: blocked sweep
         p->engine = HMMSORT_ENGINE_BLOCKED;
         rc = generic_create(&p->gen, p->model, T, true, opt.block, halo_req >= 0 ? halo_req : opt.halo);
+        if (!rc) blocked_set_hbm_columns(p->gen, opt.blocked_hbm_columns);
         if (rc == HMMSORT_EUNSUP && engine_req == HMMSORT_ENGINE_AUTO) {
             // a list the blocked sweep does not take (in-degree > 256): op-for-op single sweep
             p->engine = HMMSORT_ENGINE_STRICT;
@@ -280,6 +282,9 @@ int hmmsort_set_option(const char *key, int64_t value)
     } else if (!strcmp(key, "strict_limit_mb")) {
         HS_CHECK(value >= 0, HMMSORT_EINVAL, "set_option: strict_limit_mb must be >= 0");
         options_modify([&](Options &o) { o.strict_limit_mb = value; });
+    } else if (!strcmp(key, "blocked_hbm_columns")) {
+        HS_CHECK(value >= 0 && value <= 2, HMMSORT_EINVAL, "set_option: blocked_hbm_columns must be 0..2");
+        options_modify([&](Options &o) { o.blocked_hbm_columns = value; });
     } else if (!strcmp(key, "tie_scale")) {
         HS_CHECK(value >= 1, HMMSORT_EINVAL, "set_option: tie_scale must be >= 1");
         options_modify([&](Options &o) { o.tie_scale = value; });
@@ -307,6 +312,7 @@ int hmmsort_get_option(const char *key, int64_t *value)
     else if (!strcmp(key, "escalate")) *value = o.escalate;
     else if (!strcmp(key, "plan_cache")) *value = o.plan_cache;
     else if (!strcmp(key, "strict_limit_mb")) *value = o.strict_limit_mb;
+    else if (!strcmp(key, "blocked_hbm_columns")) *value = o.blocked_hbm_columns;
     else if (!strcmp(key, "tie_scale")) *value = o.tie_scale;
     else if (!strcmp(key, "tie_debug")) *value = o.tie_debug;
     else if (!strcmp(key, "last_escalations")) *value = last_escalations();

@@ -52,6 +52,11 @@ struct GenericDev {
     unsigned long long *d_es_diag = nullptr;
     double *d_es_lls = nullptr, *d_es_partL = nullptr;   // posterior sweep: column sums of a block, log-likelihood terms
     int es_grid = 0;
+    // the same sweeps with the columns in device memory (generic_estep_big.hip): option "blocked_hbm_columns" as it
+    // stood when the plan was created, the column scratch [es_grid][2][S] and the packed per-state records
+    int hbm_cols = 0;
+    double *d_es_cols = nullptr;
+    unsigned char *d_es_srec = nullptr;
     int64_t upd_bytes = 0;
     int threads = 256;
     int64_t bytes = 0;
@@ -78,6 +83,17 @@ int blocked_estep(GenericDev *g, const double *d_y, double *d_stats, hipStream_t
 int blocked_mstep(GenericDev *g, const double *d_stats, double *d_out, hipStream_t st);
 int blocked_estep_diagnostics(GenericDev *g, hipStream_t st, int64_t diag[8]);
 void blocked_estep_destroy(GenericDev *g);
+// the plan takes the device-memory-column kernels (option "blocked_hbm_columns"; generic_estep.hip)
+bool blocked_estep_big(const GenericDev *g);
+// generic_estep_big.hip: their grid, window and column scratch / one sweep over buffers generic_estep.hip prepared;
+// post == nullptr: the E-step
+struct BigPost {
+    int qv[4];                               // trough phase of each template
+    double *onset, *occ, *tq, *silent;
+    int16_t *xm;
+};
+int blocked_big_prepare(GenericDev *g);
+int blocked_big_launch(GenericDev *g, const double *d_y, const BigPost *post, hipStream_t st);
 void blocked_geometry(int64_t T, int64_t L, int64_t block_req, int64_t halo_req, int64_t *B,
                       int64_t *H, int64_t *nblk);
 

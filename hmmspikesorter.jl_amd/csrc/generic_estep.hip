@@ -35,55 +35,11 @@
 #include "fastmath.h"
 #include "generic_dev.h"
 #include "hmmsort_internal.h"
+#include "generic_estep_common.h"
 
 namespace hmmsort {
 
 namespace {
-
-struct BesArgs {
-    const double *y;
-    int64_t T;
-    int S, B, H, nblk, nsrc1;
-    const double *mean;
-    const int32_t *in_ptr, *in_src;
-    const double *in_w;
-    const int32_t *out_ptr, *out_dst;
-    const double *out_w;
-    double rden;
-    double *win;    // [gridDim.x][B][S] scaled alpha of the owned samples
-    double *rec;    // [nblk][6][S]  0 alpha warm (lo-1)  1 alpha exact (hi-1)  2 gamma (hi-1)
-                    //               3 beta warm (hi)     4 beta exact (lo)     5 gamma (lo)
-    double *partG;  // [nblk][2 S]
-    double *partX;  // [nblk][nsrc1 + 2]: X_i | Gamma0 | sum y^2
-};
-
-// Outputs of the posterior instantiation (bes_block_post): the per-sample marginals of hmmsort_plan_posteriors
-// instead of the block statistics.  Reduction slots of a step: [0..2] as below, then 3 per template (onset,
-// occupancy, trough), the silent state's gamma, the arg-max value and its state.
-constexpr int kPostMaxN = 4;   // templates the posterior instantiations hold partial sums for
-struct BesPost {
-    const int16_t *states;   // [S][N] phases, 1 = silent
-    int qv[kPostMaxN];       // trough phase of each template
-    int N, nred;             // nred = 3 + 3 N + 3
-    double *onset, *occ, *tq, *silent;   // [N][T] x 3, [T]; occ and silent may be null
-    int16_t *xm;             // [T]
-    double *lls;             // [gridDim.x][B] column sums of the owned samples (forward sweep)
-    double *partL;           // [nblk] sum over the owned samples of log(column sum) + emission shift
-};
-
-__device__ __forceinline__ double wsum(double v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ double wmax(double v)
-{
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    return v;
-}
-
-// red[par][slot][wave]: slot 0 column sum, 1 emission exponent maximum of the NEXT column, 2 gamma normaliser
-constexpr int kRedW = 16;
 
 #define BES_POST 0
 #include "generic_estep_block.inc"
@@ -206,27 +162,26 @@ __global__ void bes_weights(const double *__restrict__ lp, int n, double *__rest
     if (i < n) w[i] = exp(lp[i]);
 }
 
-template <typename Tv>
-int balloc(Tv **p, size_t n, int64_t *bytes)
-{
-    if (*p) return HMMSORT_OK;
-    if (hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(Tv)) != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("blocked E-step: hipMalloc of %.2f GB failed", (double)n * sizeof(Tv) / 1e9);
-        return HMMSORT_ENOMEM;
-    }
-    *bytes += (int64_t)(n * sizeof(Tv));
-    return HMMSORT_OK;
-}
-
 }  // namespace
 
-bool blocked_estep_supported(const GenericDev *g)
+// two columns of S doubles + reduction scratch in LDS; 16 states per thread at 1024 threads
+static bool lds_columns_fit(const GenericDev *g)
 {
-    // two columns of S doubles + reduction scratch in LDS; 16 states per thread at 1024 threads
     return g->blocked && g->nsrc1 >= 1 && g->nsrc1 <= 256 && g->T >= 2 &&
            (2 * (size_t)g->S + 2 * 3 * kRedW + 4 * (size_t)g->nsrc1) * 8 <= 156 * 1024 && g->S <= 16 * 1024;
 }
+
+// option "blocked_hbm_columns" as the plan saw it when it was created: 1 sends a model the LDS test refuses to the
+// device-memory-column kernels (generic_estep_big.hip), 2 every model
+bool blocked_estep_big(const GenericDev *g)
+{
+    return g->blocked && g->nsrc1 >= 1 && g->nsrc1 <= 256 && g->T >= 2 &&
+           (g->hbm_cols == 2 || (g->hbm_cols == 1 && !lds_columns_fit(g)));
+}
+
+void blocked_set_hbm_columns(GenericDev *g, int64_t v) { g->hbm_cols = (int)v; }
+
+bool blocked_estep_supported(const GenericDev *g) { return lds_columns_fit(g) || blocked_estep_big(g); }
 
 int64_t blocked_stats_len(const GenericDev *g) { return 2 * g->S + g->nsrc1 + 2; }
 
@@ -239,13 +194,69 @@ static size_t post_lds_bytes(const GenericDev *g)
 
 bool blocked_post_supported(const GenericDev *g)
 {
+    if (blocked_estep_big(g)) return g->N <= kPostMaxN;
     return blocked_estep_supported(g) && g->N <= kPostMaxN && post_lds_bytes(g) <= 160 * 1024;
+}
+
+// buffers every variant of the sweep needs, the weights and the cleared certificates; grid = resident workgroups
+static int bes_prepare(GenericDev *g, int grid, bool post, hipStream_t st)
+{
+    const size_t S = (size_t)g->S, nb = (size_t)g->nblk;
+    int rc;
+    if ((rc = balloc(&g->d_es_win, (size_t)grid * g->B * S, &g->bytes)) ||
+        (rc = balloc(&g->d_es_rec, nb * 6 * S, &g->bytes)) ||
+        (rc = balloc(&g->d_es_partG, nb * 2 * S, &g->bytes)) ||
+        (rc = balloc(&g->d_es_partX, nb * (g->nsrc1 + 2), &g->bytes)) ||
+        (rc = balloc(&g->d_es_inw, (size_t)g->R, &g->bytes)) || (rc = balloc(&g->d_es_outw, (size_t)g->R, &g->bytes)) ||
+        (rc = balloc(&g->d_es_diag, 4, &g->bytes)) || (rc = balloc(&g->d_es_tmp, 2 * S + g->K * g->N, &g->bytes)))
+        return rc;
+    if (post && ((rc = balloc(&g->d_es_lls, (size_t)grid * g->B, &g->bytes)) ||
+                 (rc = balloc(&g->d_es_partL, nb + 1, &g->bytes))))
+        return rc;
+    g->es_grid = grid;
+    hipLaunchKernelGGL(bes_weights, dim3((unsigned)((g->R + 255) / 256)), dim3(256), 0, st, g->d_in_lp, (int)g->R, g->d_es_inw);
+    hipLaunchKernelGGL(bes_weights, dim3((unsigned)((g->R + 255) / 256)), dim3(256), 0, st, g->d_out_lp, (int)g->R, g->d_es_outw);
+    HS_HIP(hipMemsetAsync(g->d_es_diag, 0, 4 * sizeof(unsigned long long), st));
+    HS_HIP(hipMemsetAsync(g->d_es_rec, 0, nb * 6 * S * sizeof(double), st));
+    return HMMSORT_OK;
+}
+
+// certificates of the sweep just launched and, for the E-step, the sum of the block statistics
+static int bes_finish(GenericDev *g, double *d_stats, bool post, hipStream_t st)
+{
+    const size_t nb = (size_t)g->nblk;
+    HS_HIP(hipGetLastError());
+    if (nb > 1)
+        hipLaunchKernelGGL(bes_check, dim3((unsigned)(nb - 1), 2), dim3(256), 0, st, (int)g->S, (int)nb, 1e-9, g->d_es_rec,
+                           g->d_es_diag);
+    if (!post)
+        hipLaunchKernelGGL(bes_reduce, dim3((unsigned)blocked_stats_len(g)), dim3(64), 0, st, (int)g->S, (int)nb, g->nsrc1,
+                           g->d_es_partG, g->d_es_partX, d_stats);
+    HS_HIP(hipGetLastError());
+    return HMMSORT_OK;
 }
 
 // the E-step (pp == nullptr) or the posterior sweep over the same blocks
 static int bes_run(GenericDev *g, const double *d_y, double *d_stats, BesPost *pp, hipStream_t st)
 {
-    HS_CHECK(blocked_estep_supported(g), HMMSORT_EUNSUP, "blocked E-step: model too large for the LDS columns");
+    HS_CHECK(g->hbm_cols != 0 || blocked_estep_supported(g), HMMSORT_EUNSUP,
+             "blocked E-step: model too large for the LDS columns");
+    HS_CHECK(blocked_estep_supported(g), HMMSORT_EUNSUP,
+             "blocked E-step: not a blocked plan of at least 2 samples whose silent state has 1 to 256 transitions");
+    int rc;
+    if (blocked_estep_big(g)) {
+        // columns in device memory (generic_estep_big.hip): its own grid, window, column scratch and block kernel.
+        // BesPost is a type of this translation unit, so the outputs cross in a BigPost
+        BigPost bp;
+        if (pp) {
+            for (int l = 0; l < kPostMaxN; l++) bp.qv[l] = pp->qv[l];
+            bp.onset = pp->onset; bp.occ = pp->occ; bp.tq = pp->tq; bp.silent = pp->silent; bp.xm = pp->xm;
+        }
+        if ((rc = blocked_big_prepare(g)) || (rc = bes_prepare(g, g->es_grid, pp != nullptr, st)) ||
+            (rc = blocked_big_launch(g, d_y, pp ? &bp : nullptr, st)))
+            return rc;
+        return bes_finish(g, d_stats, pp != nullptr, st);
+    }
     const size_t S = (size_t)g->S, nb = (size_t)g->nblk;
     const int nt = g->S <= 256 ? 256 : (g->S <= 4096 ? 512 : 1024);
     const int spt = (int)((S + nt - 1) / nt);
@@ -255,29 +266,9 @@ static int bes_run(GenericDev *g, const double *d_y, double *d_stats, BesPost *p
     const size_t lds = pp ? post_lds_bytes(g) : (2 * S + 2 * 3 * kRedW + 4 * (size_t)g->nsrc1) * sizeof(double);
     const int per_cu = lds <= 76 * 1024 && nt <= 512 ? 2 : 1;
     const int grid = (int)std::min<size_t>(nb, (size_t)ncu * per_cu);
-    int rc;
-    if ((rc = balloc(&g->d_es_win, (size_t)grid * g->B * S, &g->bytes)) ||
-        (rc = balloc(&g->d_es_rec, nb * 6 * S, &g->bytes)) ||
-        (rc = balloc(&g->d_es_partG, nb * 2 * S, &g->bytes)) ||
-        (rc = balloc(&g->d_es_partX, nb * (g->nsrc1 + 2), &g->bytes)) ||
-        (rc = balloc(&g->d_es_inw, (size_t)g->R, &g->bytes)) || (rc = balloc(&g->d_es_outw, (size_t)g->R, &g->bytes)) ||
-        (rc = balloc(&g->d_es_diag, 4, &g->bytes)) || (rc = balloc(&g->d_es_tmp, 2 * S + g->K * g->N, &g->bytes)))
-        return rc;
-    if (pp && ((rc = balloc(&g->d_es_lls, (size_t)grid * g->B, &g->bytes)) ||
-               (rc = balloc(&g->d_es_partL, nb + 1, &g->bytes))))
-        return rc;
-    g->es_grid = grid;
-    hipLaunchKernelGGL(bes_weights, dim3((unsigned)((g->R + 255) / 256)), dim3(256), 0, st, g->d_in_lp, (int)g->R, g->d_es_inw);
-    hipLaunchKernelGGL(bes_weights, dim3((unsigned)((g->R + 255) / 256)), dim3(256), 0, st, g->d_out_lp, (int)g->R, g->d_es_outw);
-    HS_HIP(hipMemsetAsync(g->d_es_diag, 0, 4 * sizeof(unsigned long long), st));
-    HS_HIP(hipMemsetAsync(g->d_es_rec, 0, nb * 6 * S * sizeof(double), st));
+    if ((rc = bes_prepare(g, grid, pp != nullptr, st))) return rc;
     BesArgs a;
-    a.y = d_y; a.T = g->T; a.S = (int)g->S; a.B = (int)g->B; a.H = (int)g->H; a.nblk = (int)g->nblk;
-    a.nsrc1 = g->nsrc1; a.mean = g->d_mean;
-    a.in_ptr = g->d_in_ptr; a.in_src = g->d_in_src; a.in_w = g->d_es_inw;
-    a.out_ptr = g->d_out_ptr; a.out_dst = g->d_out_dst; a.out_w = g->d_es_outw;
-    a.rden = 1.0 / (2.0 * (g->sigma * g->sigma));
-    a.win = g->d_es_win; a.rec = g->d_es_rec; a.partG = g->d_es_partG; a.partX = g->d_es_partX;
+    bes_fill_args(a, g, d_y);
     auto launch = [&](auto kern) -> int {
         if (lds > 64 * 1024)
             HS_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -307,15 +298,7 @@ static int bes_run(GenericDev *g, const double *d_y, double *d_stats, BesPost *p
                         : spt <= 4 ? launch(bes_block<4, 512>) : launch(bes_block<8, 512>);
     else rc = spt <= 8 ? launch(bes_block<8, 1024>) : launch(bes_block<16, 1024>);
     if (rc) return rc;
-    HS_HIP(hipGetLastError());
-    if (nb > 1)
-        hipLaunchKernelGGL(bes_check, dim3((unsigned)(nb - 1), 2), dim3(256), 0, st, (int)S, (int)nb, 1e-9, g->d_es_rec,
-                           g->d_es_diag);
-    if (!pp)
-        hipLaunchKernelGGL(bes_reduce, dim3((unsigned)blocked_stats_len(g)), dim3(64), 0, st, (int)S, (int)nb, g->nsrc1,
-                           g->d_es_partG, g->d_es_partX, d_stats);
-    HS_HIP(hipGetLastError());
-    return HMMSORT_OK;
+    return bes_finish(g, d_stats, pp != nullptr, st);
 }
 
 int blocked_estep(GenericDev *g, const double *d_y, double *d_stats, hipStream_t st)
@@ -330,6 +313,9 @@ int blocked_posteriors(GenericDev *g, const double *d_y, const int32_t *trough, 
              "plan_posteriors: the blocked path holds two columns of S doubles in LDS (156 KB: %d states at most, this "
              "model has %lld); use the strict engine (option \"engine\" = HMMSORT_ENGINE_STRICT)",
              (int)((156 * 1024 / 8 - 2 * 3 * kRedW - 4 * g->nsrc1) / 2), (long long)g->S);
+    HS_CHECK(!blocked_estep_big(g) || g->N <= kPostMaxN, HMMSORT_EUNSUP,
+             "plan_posteriors: the blocked path takes up to %d templates (this model: %lld); use the strict engine",
+             kPostMaxN, (long long)g->N);
     HS_CHECK(blocked_post_supported(g), HMMSORT_EUNSUP,
              "plan_posteriors: the blocked path takes up to %d templates within 160 KB of LDS (this model: %lld templates, "
              "%zu bytes); use the strict engine", kPostMaxN, (long long)g->N, post_lds_bytes(g));
@@ -375,7 +361,7 @@ int blocked_estep_diagnostics(GenericDev *g, hipStream_t st, int64_t diag[8])
 void blocked_estep_destroy(GenericDev *g)
 {
     void *ptrs[] = {g->d_es_win, g->d_es_rec, g->d_es_partG, g->d_es_partX, g->d_es_inw, g->d_es_outw,
-                    g->d_es_diag, g->d_es_tmp, g->d_es_lls, g->d_es_partL};
+                    g->d_es_diag, g->d_es_tmp, g->d_es_lls, g->d_es_partL, g->d_es_cols, g->d_es_srec};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
 }

@@ -42,6 +42,7 @@ struct Options {
     int64_t plan_cache = 4;        // idle plans (+ device buffers) the host-buffer entry points keep
     int64_t strict_limit_mb = 0;   // largest back-pointer table the strict fallback may allocate (0 = what is free)
     int64_t tie_scale = 1;         // test aid: multiplies the wave engine's near-tie threshold (more decisions flagged)
+    int64_t blocked_hbm_columns = 0;   // blocked E-step / posteriors with the state columns in device memory: 0, 1, 2
     int64_t tie_debug = 0;         // test aids: 1 the resolver folds the exact prefix to the end, 2 resolver off
 };
 // process-wide options behind a mutex: entry points work on a snapshot taken when they start
@@ -118,6 +119,8 @@ int generic_posteriors(const double *d_alpha, const double *d_beta, int64_t T, i
 // time-parallel E-step of the blocked generic engine (generic_estep.hip): sufficient statistics without
 // S x T arrays.  stats = [G0 (S) | G1 (S) | X (n_lp + 1) | Gamma0 | sum y^2]
 bool blocked_estep_supported(const GenericDev *g);
+// option "blocked_hbm_columns" (0 off, 1 models the LDS test refuses, 2 every model), fixed when the plan is created
+void blocked_set_hbm_columns(GenericDev *g, int64_t v);
 int64_t blocked_stats_len(const GenericDev *g);
 int blocked_estep(GenericDev *g, const double *d_y, double *d_stats, hipStream_t st);
 int blocked_mstep(GenericDev *g, const double *d_stats, double *d_out, hipStream_t st);

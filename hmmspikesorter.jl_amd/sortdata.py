@@ -55,7 +55,7 @@ def load_data(path, name="data"):
 
 def _chunk_confidence(templates, dataf, ml_seq, chunksize, jitter):
     """spike times and confidences of the decoded path, chunk by chunk of the chunked fit, on the strict path (the
-    blocked path under option "engine" = ENGINE_BLOCKED)"""
+    blocked path under option "engine" = ENGINE_BLOCKED; past its LDS limit with option "blocked_hbm_columns")"""
     n, N = len(ml_seq), templates.state_matrix.N
     times, conf = [[] for _ in range(N)], [[] for _ in range(N)]
     for lo in range(0, n, chunksize):
@@ -83,8 +83,10 @@ def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_temp
     this runs on the strict path (alpha and beta materialised, 2 x S x chunksize doubles): slow, and for the 3-
     and 4-template overlap models only feasible with a small `chunksize`.  With option "engine" set to
     ENGINE_BLOCKED the posteriors of a model within the blocked E-step's LDS limit come from the time-parallel
-    blocked sweep instead (no S x chunksize array; 2 x 60 at the default chunksize is routine); larger models
-    still take the strict path."""
+    blocked sweep instead (no S x chunksize array; 2 x 60 at the default chunksize is routine).  Larger models
+    -- 3 x 60 and 4 x 60, 10 621 and 21 123 states -- take the same sweep with its state columns in device
+    memory when option "blocked_hbm_columns" is 1 as well, at the default chunksize; with that option off (the
+    default) they still take the strict path."""
     spike_forms = np.asarray(spike_forms, dtype=np.float64)
     nstates, _nchannels, ntemplates = spike_forms.shape
     pp = np.atleast_1d(np.asarray(p, dtype=np.float64))

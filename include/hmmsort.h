@@ -70,7 +70,11 @@ int hmmsort_set_device(int device);
  *       "escalate" (host-buffer entry points retry with a wider warm-up / the strict engine when a
  *       boundary certificate or the near-tie guard fires; default 1), "plan_cache" (idle plans the
  *       host-buffer entry points keep between calls, default 4, 0 = none), "strict_limit_mb" (largest
- *       back-pointer table the strict fallback of hmmsort_viterbi may allocate, 0 = what is free); read-only
+ *       back-pointer table the strict fallback of hmmsort_viterbi may allocate, 0 = what is free),
+ *       "blocked_hbm_columns" (the blocked E-step and posteriors with their two state columns in device memory
+ *       instead of LDS: 0, the default, refuses models past the LDS limit of about 9 900 states as before;
+ *       1 sends those models to the device-memory kernels; 2 sends every blocked plan there, for cross-checks.
+ *       A plan keeps the value it was created under; values outside 0..2: HMMSORT_EINVAL); read-only
  *       "last_escalations" (retries of the calling thread's last host-buffer call; NEGATIVE = minus the
  *       number of near-tie decisions on a time-parallel path that was returned because the strict sweep's
  *       S x T back-pointers do not fit: the path can differ from the reference's at those decisions only,
@@ -301,7 +305,11 @@ int hmmsort_plan_extract_spiketimes(hmmsort_plan *plan, const int16_t *d_x, int6
  * HMMSORT_ENGINE_BLOCKED, or AUTO from 4 096 samples) run the time-parallel E-step's sweep with the per-sample
  * marginals kept: no S x T array, asynchronous on `stream`; the model must fit the blocked E-step (two columns
  * of S doubles within 156 KB of LDS, about 9 900 states) and have at most 4 templates, else HMMSORT_EUNSUP
- * naming the limit.  Strict plans (any model; option "engine" = HMMSORT_ENGINE_STRICT) materialise alpha and
+ * naming the limit.  A plan created under option "blocked_hbm_columns" = 1 or 2 keeps the columns in device
+ * memory and takes any number of states (the reference's 3- and 4-template overlap models at K = 60 have
+ * 10 621 and 21 123), still at most 4 templates and 256 transitions out of the silent state; its workspace, a
+ * window of block x S doubles per resident workgroup, is capped at half of the free device memory and reported
+ * by hmmsort_plan_info (HMMSORT_ENOMEM naming the bytes when not even one workgroup fits).  Strict plans (any model; option "engine" = HMMSORT_ENGINE_STRICT) materialise alpha and
  * beta (2 x S x T doubles, bounded by "strict_limit_mb": HMMSORT_ENOMEM beyond it) and synchronise the stream.
  * Ring-engine plans: HMMSORT_EUNSUP.  A time shard (hmmsort_plan_set_shard; wave plans only): HMMSORT_EINVAL.
  * The warm-up certificates of a wave or blocked plan run and count into hmmsort_plan_diagnostics (diag[3..6])
