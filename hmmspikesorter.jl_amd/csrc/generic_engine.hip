@@ -12,6 +12,7 @@
 // Compiled with -ffp-contract=off (Julia does not contract).
 #include <cmath>
 #include <cstdio>
+#include <vector>
 
 #include "generic_dev.h"
 #include "hmmsort_internal.h"
@@ -463,27 +464,7 @@ void generic_destroy(GenericDev *g)
     delete g;
 }
 
-int64_t generic_workspace_bytes(const GenericDev *g) { return g->bytes; }
-int64_t generic_n_lp(const GenericDev *g) { return g->nsrc1 - 1; }
-bool generic_is_blocked(const GenericDev *g) { return g->blocked; }
 int64_t blocked_min_samples() { return 4096; }
-
-void generic_geometry(const GenericDev *g, int64_t *block, int64_t *halo, int64_t *nblocks)
-{
-    *block = g->blocked ? g->B : g->T;
-    *halo = g->blocked ? g->H : 0;
-    *nblocks = g->blocked ? g->nblk : 1;
-}
-
-int generic_diagnostics(GenericDev *g, hipStream_t st, int64_t diag[8])
-{
-    if (g->blocked) {
-        int rc = blocked_diagnostics(g, st, diag);
-        if (rc) return rc;
-        return blocked_estep_diagnostics(g, st, diag);
-    }
-    return HMMSORT_OK;
-}
 
 static int set_lds_limit(const void *fn, size_t bytes)
 {
@@ -559,6 +540,162 @@ int generic_backward(GenericDev *g, const double *d_y, double *d_beta, hipStream
                        (int)g->S, g->d_mean, g->d_out_ptr, g->d_out_dst, g->d_out_lp, c0, den,
                        d_beta, g->use_global ? g->d_gbuf : nullptr);
     HS_HIP(hipGetLastError());
+    return HMMSORT_OK;
+}
+
+// ---- the engine behind a strict or blocked plan (hmmsort_internal.h) ---------------------------
+namespace {
+struct GenericEngine final : Engine {
+    GenericDev *g = nullptr;
+    // posteriors of the last call: onset and trough-state mass (N x T each), arg-max state (T), partial sums for the
+    // expected counts; allocated by the first such call
+    double *post_on = nullptr, *post_tq = nullptr, *post_part = nullptr;
+    int16_t *post_xm = nullptr;
+    bool post_valid = false;
+
+    explicit GenericEngine(bool blocked) : Engine(blocked ? HMMSORT_ENGINE_BLOCKED : HMMSORT_ENGINE_STRICT) {}
+    ~GenericEngine() override
+    {
+        generic_destroy(g);
+        for (void *q : {(void *)post_on, (void *)post_tq, (void *)post_part, (void *)post_xm})
+            if (q) (void)hipFree(q);
+    }
+    int set_model(int64_t, const HostModel &m) override
+    {
+        post_valid = false;
+        return generic_set_model(g, m);
+    }
+    void geometry(int64_t *block, int64_t *halo, int64_t *nblocks) const override
+    {
+        *block = g->blocked ? g->B : g->T;
+        *halo = g->blocked ? g->H : 0;
+        *nblocks = g->blocked ? g->nblk : 1;
+    }
+    int64_t workspace_bytes() const override { return g->bytes; }
+    int viterbi(const double *d_y, int16_t *d_x, double *d_ll, hipStream_t st) override
+    {
+        return generic_viterbi(g, d_y, d_x, d_ll, st);
+    }
+    int64_t stats_len() const override { return blocked_estep_supported(g) ? blocked_stats_len(g) : 0; }
+    int estep(const double *d_y, double *d_stats, hipStream_t st) override
+    {
+        if (!has_estep()) return Engine::estep(d_y, d_stats, st);
+        post_valid = false;   // the posterior sweep shares the E-step's window and boundary records
+        return blocked_estep(g, d_y, d_stats, st);
+    }
+    int mstep(const double *d_stats, double *d_out, hipStream_t st) override
+    {
+        return has_estep() ? blocked_mstep(g, d_stats, d_out, st) : Engine::mstep(d_stats, d_out, st);
+    }
+    // one per transition leaving state 1 except the first (baumwelch.jl:226,264)
+    int64_t n_lp() const override { return g->nsrc1 - 1; }
+    int diagnostics(hipStream_t st, int64_t diag[8]) override
+    {
+        if (!g->blocked) return HMMSORT_OK;
+        int rc = blocked_diagnostics(g, st, diag);
+        return rc ? rc : blocked_estep_diagnostics(g, st, diag);
+    }
+    int64_t overlap_sweep() const override { return generic_overlap_sweep(g); }
+    bool drop_structured_sweep() override
+    {
+        if (!generic_pair_active(g)) return false;
+        generic_pair_disable(g);
+        return true;
+    }
+    int forward(const double *d_y, double *d_alpha, hipStream_t st) override { return generic_forward(g, d_y, d_alpha, st); }
+    int backward(const double *d_y, double *d_beta, hipStream_t st) override { return generic_backward(g, d_y, d_beta, st); }
+    int update(const double *d_alpha, const double *d_beta, const double *d_y, double *d_out, hipStream_t st) override
+    {
+        return generic_update(g, d_alpha, d_beta, d_y, d_out, st);
+    }
+
+    bool has_posteriors() const override { return !g->blocked || blocked_post_supported(g); }
+    bool posteriors_valid() const override { return post_valid; }
+    template <typename Tv> static int own(Tv **q, size_t n)
+    {
+        if (*q) return HMMSORT_OK;
+        if (hipMalloc((void **)q, n) != hipSuccess) {
+            (void)hipGetLastError();
+            *q = nullptr;
+            set_error("plan_posteriors: hipMalloc of %zu bytes failed", n);
+            return HMMSORT_ENOMEM;
+        }
+        return HMMSORT_OK;
+    }
+    int posteriors(const HostModel &m, const double *d_y, double *d_onset, double *d_occ, double *d_silent,
+                   double *d_logz, hipStream_t st) override
+    {
+        const int64_t T = g->T, S = m.S, N = m.N;
+        post_valid = false;
+        if (!g->blocked) {
+            const double need = 2.0 * (double)S * (double)T * 8.0, limit = strict_limit_bytes(options_get());
+            HS_CHECK(need <= limit, HMMSORT_ENOMEM,
+                     "plan_posteriors: the strict path needs %.2f GB for alpha and beta (%lld states x %lld samples), "
+                     "limit %.2f GB (option \"strict_limit_mb\", 0 = free device memory)", need / 1e9, (long long)S,
+                     (long long)T, limit / 1e9);
+        }
+        int rc;
+        if ((rc = own(&post_on, (size_t)N * T * 8)) || (rc = own(&post_tq, (size_t)N * T * 8)) ||
+            (rc = own(&post_xm, (size_t)T * 2)) || (rc = own(&post_part, (size_t)N * kPostParts * 8)))
+            return rc;
+        std::vector<int32_t> qv(N);
+        for (int64_t i = 0; i < N; i++) qv[i] = trough_value(m.mu.data(), m.K, i);
+        if (g->blocked) {
+            // the time-parallel E-step's sweep with the per-sample marginals kept (generic_estep.hip).  Nothing of
+            // size S x T exists; the call only enqueues work on the caller's stream.
+            if ((rc = blocked_posteriors(g, d_y, qv.data(), post_on, d_occ, d_silent, post_tq, post_xm, d_logz, st)))
+                return rc;
+            if (d_onset) HS_HIP(hipMemcpyAsync(d_onset, post_on, (size_t)N * T * 8, hipMemcpyDeviceToDevice, st));
+            post_valid = true;
+            return HMMSORT_OK;
+        }
+        DevBuf da, db, dst, dq, docc, dsil, dz;
+        if ((rc = da.alloc((size_t)S * T * 8)) || (rc = db.alloc((size_t)S * T * 8)) ||
+            (rc = dst.alloc((size_t)N * S * sizeof(int16_t))) || (rc = dq.alloc((size_t)N * sizeof(int32_t))) ||
+            (rc = dz.alloc(8)))
+            return rc;
+        if (!d_occ) { if ((rc = docc.alloc((size_t)N * T * 8))) return rc; d_occ = docc.as<double>(); }
+        if (!d_silent) { if ((rc = dsil.alloc((size_t)T * 8))) return rc; d_silent = dsil.as<double>(); }
+        if (!d_logz) d_logz = dz.as<double>();
+        HS_HIP(hipMemcpyAsync(dst.p, m.states.data(), (size_t)N * S * sizeof(int16_t), hipMemcpyHostToDevice, st));
+        HS_HIP(hipMemcpyAsync(dq.p, qv.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        if ((rc = generic_forward(g, d_y, da.as<double>(), st))) return rc;
+        if ((rc = generic_backward(g, d_y, db.as<double>(), st))) return rc;
+        if ((rc = generic_posteriors(da.as<double>(), db.as<double>(), T, S, N, dst.as<int16_t>(), dq.as<int32_t>(),
+                                     d_logz, post_on, d_occ, d_silent, post_tq, post_xm, st)))
+            return rc;
+        if (d_onset) HS_HIP(hipMemcpyAsync(d_onset, post_on, (size_t)N * T * 8, hipMemcpyDeviceToDevice, st));
+        HS_HIP(hipStreamSynchronize(st));   // the temporaries die with this frame
+        post_valid = true;
+        return HMMSORT_OK;
+    }
+    int posterior_decode(int16_t *d_xm, hipStream_t st) override
+    {
+        if (!post_valid) return Engine::posterior_decode(d_xm, st);
+        HS_HIP(hipMemcpyAsync(d_xm, post_xm, (size_t)g->T * sizeof(int16_t), hipMemcpyDeviceToDevice, st));
+        return HMMSORT_OK;
+    }
+    int spike_conf(int, int a, int, int64_t jitter, const int64_t *d_times, int64_t n, double *d_conf,
+                   hipStream_t st) override
+    {
+        return dev_spike_conf(post_tq + a * g->T, nullptr, g->T, 0, jitter, d_times, n, d_conf, st);
+    }
+    int expected_counts(double *counts_out, hipStream_t st) override
+    {
+        if (!post_valid) return Engine::expected_counts(counts_out, st);
+        return dev_row_sums(post_on, g->N, g->T, post_part, counts_out, st);
+    }
+};
+}  // namespace
+
+int generic_engine_create(std::unique_ptr<Engine> *out, const HostModel &m, int64_t T, bool blocked,
+                          int64_t block_req, int64_t halo_req, int64_t hbm_columns)
+{
+    std::unique_ptr<GenericEngine> e(new GenericEngine(blocked));
+    int rc = generic_create(&e->g, m, T, blocked, block_req, halo_req);
+    if (rc) return rc;
+    if (blocked) blocked_set_hbm_columns(e->g, hbm_columns);
+    *out = std::move(e);
     return HMMSORT_OK;
 }
 

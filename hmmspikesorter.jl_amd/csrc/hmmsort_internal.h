@@ -1,9 +1,10 @@
-// Internal declarations shared by the C ABI (capi.cpp), the host-side state-space code
-// (statespace.cpp) and the two device engines (generic_engine.hip, ring_engine.hip).
+// Internal declarations shared by the C ABI (capi.cpp, host_calls.cpp), the host-side state-space code
+// (statespace.cpp) and the device engines (generic_engine.hip, ring_engine.hip, wave_engine.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <functional>
+#include <memory>
 #include <string>
 #include <vector>
 #include "../../include/hmmsort.h"
@@ -82,6 +83,164 @@ struct HostModel {
 int build_host_model(HostModel &m, const int16_t *states, int64_t N, int64_t K, int64_t S,
                      const hmm_trans *tr, int64_t R, const double *mu, double sigma);
 int analyze_ring(const HostModel &m, RingModel &ring);
+// trough state value of template i: indmin(mu[:,i]) + 1, first minimum (extraction.jl:18)
+inline int32_t trough_value(const double *mu, int64_t K, int64_t i)
+{
+    int64_t q = 0;
+    for (int64_t k = 1; k < K; k++)
+        if (mu[k + K * i] < mu[q + K * i]) q = k;
+    return (int32_t)(q + 1);
+}
+// largest table the strict engine may allocate: option "strict_limit_mb", 0 = 0.9 x the free device memory
+inline double strict_limit_bytes(const Options &opt)
+{
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
+    return opt.strict_limit_mb > 0 ? (double)opt.strict_limit_mb * 1048576.0 : 0.9 * (double)free_b;
+}
+
+struct DevBuf {  // RAII device buffer of the host side
+    void *p = nullptr;
+    size_t cap = 0;
+    ~DevBuf() { release(); }
+    void release()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    int alloc(size_t bytes)
+    {
+        release();
+        bytes = bytes < 8 ? 8 : bytes;
+        if (hipMalloc(&p, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("hipMalloc of %zu bytes failed", bytes);
+            p = nullptr;
+            return HMMSORT_ENOMEM;
+        }
+        cap = bytes;
+        return HMMSORT_OK;
+    }
+    // cached buffers of a host slot: keep when large enough, else replace (a re-armed or rebuilt plan may
+    // need more: blocked statistics grow with the finite entry transitions, a wave plan needs 3NL+N+4)
+    int ensure(size_t bytes) { return (p && cap >= (bytes < 8 ? 8 : bytes)) ? HMMSORT_OK : alloc(bytes); }
+    template <typename Tv> Tv *as() { return static_cast<Tv *>(p); }
+};
+
+// ---- what a plan runs on ---------------------------------------------------------------------
+// One virtual per operation the C ABI forwards (capi.cpp) or a host-buffer entry point runs (host_calls.cpp).
+// The default of an operation an engine does not serve is the refusal the ABI documents, so each such sentence
+// exists here and nowhere else.  Implementations: wave_engine.hip, ring_engine.hip, generic_engine.hip (strict and
+// blocked); the only code that names one is plan creation (capi.cpp).
+class Engine {
+public:
+    const int64_t id;  // HMMSORT_ENGINE_*
+    explicit Engine(int64_t id_) : id(id_) {}
+    virtual ~Engine() = default;
+    Engine(const Engine &) = delete;
+    Engine &operator=(const Engine &) = delete;
+
+    // new numbers for a plan of the same shape (channel 0 unless the plan is batched)
+    virtual int set_model(int64_t channel, const HostModel &m) = 0;
+    // Ring models only.  Such an engine takes the list apart into junction constants, so a list that has lost the
+    // entry transitions of a vanished template (types.jl:121 keeps finite entries only) fits the same plan.
+    virtual bool ring_models_only() const { return false; }
+    virtual void geometry(int64_t *block, int64_t *halo, int64_t *nchains) const = 0;
+    virtual int64_t workspace_bytes() const = 0;
+    virtual int bind(const double *, hipStream_t) { return HMMSORT_OK; }
+    virtual void unbind() {}
+    virtual int viterbi(const double *d_y, int16_t *d_x, double *d_ll, hipStream_t st) = 0;
+    virtual int decode_estep(const double *, int16_t *, double *, double *, hipStream_t)
+    {
+        return refuse(HMMSORT_EUNSUP, "plan_decode_estep: needs the wave or ring engine");
+    }
+    virtual int64_t stats_len() const { return 0; }   // 0: no sufficient-statistics E-step for this plan
+    bool has_estep() const { return stats_len() > 0; }
+    virtual int estep(const double *, double *, hipStream_t)
+    {
+        return refuse(HMMSORT_EUNSUP, "plan_estep: sufficient-statistics E-step needs the wave, ring or blocked "
+                                      "engine (use hmmsort_em_step)");
+    }
+    virtual int mstep(const double *, double *, hipStream_t)
+    {
+        return refuse(HMMSORT_EUNSUP, "plan_mstep: needs the wave, ring or blocked engine");
+    }
+    virtual int64_t n_lp() const = 0;   // entry log-probabilities in the M-step's output
+    virtual int set_shard(int64_t, int64_t, bool, bool)
+    {
+        return refuse(HMMSORT_EUNSUP, "plan_set_shard: needs the wave or ring engine");
+    }
+    virtual int diagnostics(hipStream_t, int64_t[8]) { return HMMSORT_OK; }
+    virtual int tie_stats(hipStream_t, int64_t[8]) { return HMMSORT_OK; }
+    virtual int profile(int) { return HMMSORT_OK; }
+    virtual int profile_read(hipStream_t, std::vector<std::string> &, std::vector<double> &, std::vector<int64_t> &)
+    {
+        return HMMSORT_OK;
+    }
+    // posteriors of the plan's model m; the results of the last call serve the four operations after it
+    virtual bool has_posteriors() const { return false; }
+    virtual int posteriors(const HostModel &, const double *, double *, double *, double *, double *, hipStream_t)
+    {
+        set_error("plan_posteriors: needs a wave plan (ring models), a blocked plan (overlap models within the LDS "
+                  "limit) or a strict plan (any model); this plan runs engine %lld", (long long)id);
+        return HMMSORT_EUNSUP;
+    }
+    virtual bool posteriors_valid() const { return false; }
+    virtual int posterior_decode(int16_t *, hipStream_t)
+    {
+        return refuse(HMMSORT_EINVAL, "plan_posterior_decode: call hmmsort_plan_posteriors first");
+    }
+    // confidences of n events of template a on channel ch (1-based times in device memory, trough value qv)
+    virtual int spike_conf(int, int, int, int64_t, const int64_t *, int64_t, double *, hipStream_t)
+    {
+        return refuse(HMMSORT_EINVAL, "plan_spike_confidence: call hmmsort_plan_posteriors first");
+    }
+    virtual int expected_counts(double *, hipStream_t)
+    {
+        return refuse(HMMSORT_EINVAL, "plan_expected_counts: call hmmsort_plan_posteriors first");
+    }
+    virtual int64_t overlap_sweep() const { return 0; }   // 0 generic sweeps, 2 pair sweep, 3..5 multi sweep
+    // switch the structure-exploiting overlap sweep off for this plan; false: none was in use
+    virtual bool drop_structured_sweep() { return false; }
+    // materialised S x T sweeps and the reference's update() on them: the strict engine's job
+    virtual int forward(const double *, double *, hipStream_t) { return refuse(HMMSORT_EUNSUP, "forward: needs the strict engine"); }
+    virtual int backward(const double *, double *, hipStream_t) { return refuse(HMMSORT_EUNSUP, "backward: needs the strict engine"); }
+    virtual int update(const double *, const double *, const double *, double *, hipStream_t)
+    {
+        return refuse(HMMSORT_EUNSUP, "update: needs the strict engine");
+    }
+    // debugging aids outside the documented ABI
+    virtual int debug_record(double *) { return refuse(HMMSORT_EINVAL, "plan_debug_record: needs a wave plan"); }
+    virtual int debug_array(int, double *, int64_t) { return refuse(HMMSORT_EINVAL, "plan_debug_array: needs a wave plan"); }
+
+protected:
+    static int refuse(int code, const char *msg)
+    {
+        set_error("%s", msg);
+        return code;
+    }
+    // what every engine that takes a time shard asks of it first
+    static int check_shard(int64_t T, int64_t own_lo, int64_t own_hi, bool first, bool last)
+    {
+        HS_CHECK(own_lo >= 0 && own_lo <= own_hi && own_hi <= T, HMMSORT_EINVAL,
+                 "plan_set_shard: owned range [%lld, %lld) outside [0, %lld]", (long long)own_lo,
+                 (long long)own_hi, (long long)T);
+        HS_CHECK((!first || own_lo == 0) && (!last || own_hi == T), HMMSORT_EINVAL,
+                 "plan_set_shard: a first/last shard must own its first/last sample");
+        return HMMSORT_OK;
+    }
+};
+
+// engines behind the interface, for plan creation.  generic: strict, or blocked with option "blocked_hbm_columns"
+// as it stands now (fixed for the life of the plan)
+bool wave_supported(const HostModel &m, int64_t T, std::string *why);
+int wave_engine_create(std::unique_ptr<Engine> *out, const std::vector<HostModel> &models, int64_t T,
+                       int64_t block_req, int64_t halo_req);
+int ring_engine_create(std::unique_ptr<Engine> *out, const HostModel &m, int64_t T, int64_t block_req,
+                       int64_t halo_req);
+int generic_engine_create(std::unique_ptr<Engine> *out, const HostModel &m, int64_t T, bool blocked = false,
+                          int64_t block_req = 0, int64_t halo_req = 0, int64_t hbm_columns = 0);
 
 // ---- device engines ------------------------------------------------------------------------
 struct GenericDev;  // generic_engine.hip
@@ -91,18 +250,14 @@ struct RingDev;     // ring_engine.hip
 // blocked = time-parallel Viterbi over blocks with a certified warm-up (generic_blocked.hip)
 int generic_create(GenericDev **g, const HostModel &m, int64_t T, bool blocked = false,
                    int64_t block_req = 0, int64_t halo_req = 0);
-bool generic_is_blocked(const GenericDev *g);
 // two-template overlap models: the blocked engine's structure-exploiting sweep (pair_sweep.hip) is in use /
 // switch it off for this plan (host fallback to the generic blocked sweep when a near-tie is flagged on the path)
 bool generic_pair_active(const GenericDev *g);
 void generic_pair_disable(GenericDev *g);
 int64_t generic_overlap_sweep(const GenericDev *g);   // 0 generic sweeps, 2 pair sweep, 3..5 multi sweep
-void generic_geometry(const GenericDev *g, int64_t *block, int64_t *halo, int64_t *nblocks);
-int generic_diagnostics(GenericDev *g, hipStream_t st, int64_t diag[8]);
 int64_t blocked_min_samples();
 int generic_set_model(GenericDev *g, const HostModel &m);
 void generic_destroy(GenericDev *g);
-int64_t generic_workspace_bytes(const GenericDev *g);
 int generic_viterbi(GenericDev *g, const double *d_y, int16_t *d_x, double *d_ll,
                     hipStream_t st);
 int generic_forward(GenericDev *g, const double *d_y, double *d_alpha, hipStream_t st);
@@ -110,20 +265,16 @@ int generic_backward(GenericDev *g, const double *d_y, double *d_beta, hipStream
 // update() on device from materialised alpha/beta; d_out = [mu K*N | sigma | lp (nsrc1-1) | pp S]
 int generic_update(GenericDev *g, const double *d_alpha, const double *d_beta, const double *d_y,
                    double *d_out, hipStream_t st);
-int64_t generic_n_lp(const GenericDev *g);
 // smoothed posteriors from materialised alpha/beta (generic_post.hip): per sample, gamma reduced over the state
 // table into onset / occ / trough-state mass (N x T each), silent (T), arg-max state (1-based) and logz
 int generic_posteriors(const double *d_alpha, const double *d_beta, int64_t T, int64_t S, int64_t N,
                        const int16_t *d_states, const int32_t *d_qv, double *d_logz, double *d_onset,
                        double *d_occ, double *d_silent, double *d_tq, int16_t *d_xm, hipStream_t st);
-// time-parallel E-step of the blocked generic engine (generic_estep.hip): sufficient statistics without
-// S x T arrays.  stats = [G0 (S) | G1 (S) | X (n_lp + 1) | Gamma0 | sum y^2]
+// time-parallel E-step of the blocked generic engine (generic_estep.hip; its calls are in generic_dev.h): sufficient
+// statistics without S x T arrays.  stats = [G0 (S) | G1 (S) | X (n_lp + 1) | Gamma0 | sum y^2]
 bool blocked_estep_supported(const GenericDev *g);
 // option "blocked_hbm_columns" (0 off, 1 models the LDS test refuses, 2 every model), fixed when the plan is created
 void blocked_set_hbm_columns(GenericDev *g, int64_t v);
-int64_t blocked_stats_len(const GenericDev *g);
-int blocked_estep(GenericDev *g, const double *d_y, double *d_stats, hipStream_t st);
-int blocked_mstep(GenericDev *g, const double *d_stats, double *d_out, hipStream_t st);
 // the E-step's sweep with the per-sample marginals kept (generic_estep.hip, bes_block_post): onset, occ, tq [N][T],
 // silent [T], arg-max state xm [T], logz; d_occ, d_silent and d_logz may be null.  trough: N phases (host)
 bool blocked_post_supported(const GenericDev *g);
@@ -134,12 +285,6 @@ int blocked_posteriors(GenericDev *g, const double *d_y, const int32_t *trough, 
 int ring_create(RingDev **r, const HostModel &m, int64_t T, int64_t block_req, int64_t halo_req);
 int ring_set_model(RingDev *r, const HostModel &m);
 void ring_destroy(RingDev *r);
-int64_t ring_workspace_bytes(const RingDev *r);
-void ring_geometry(const RingDev *r, int64_t *block, int64_t *halo, int64_t *nchains);
-int ring_viterbi(RingDev *r, const double *d_y, int16_t *d_x, double *d_ll, hipStream_t st);
-int ring_estep(RingDev *r, const double *d_y, double *d_stats, hipStream_t st);
-int ring_mstep(RingDev *r, const double *d_stats, double *d_out, hipStream_t st);
-int64_t ring_stats_len(const RingDev *r);
 int ring_diagnostics(RingDev *r, hipStream_t st, int64_t diag[8]);
 bool ring_supported(const HostModel &m, int64_t T, std::string *why);
 
@@ -153,5 +298,33 @@ int dev_spike_compact(const int16_t *d_x, int64_t T, const uint32_t *d_match, in
                       hipStream_t st);
 int dev_unroll(const int16_t *d_x, int64_t T, const int16_t *d_states, int64_t N, int64_t S,
                int16_t *d_out, hipStream_t st);
+// posterior helpers (wave_post.hip): sum_{|d| <= J} src[t + d - shift] (head[-index] for a negative index when
+// head is given, 0 otherwise and outside [0, T)), capped at 1; sums over time of n rows of length T
+constexpr int kPostParts = 256;
+int dev_spike_conf(const double *d_src, const double *d_head, int64_t T, int64_t shift, int64_t jitter,
+                   const int64_t *d_times, int64_t n, double *d_conf, hipStream_t st);
+int dev_row_sums(const double *d_rows, int64_t nrows, int64_t T, double *d_part, double *out_host, hipStream_t st);
 
+}  // namespace hmmsort
+
+// ---- plans (capi.cpp) and the host-buffer entry points on top of them (host_calls.cpp) ---------
+struct hmmsort_plan {
+    hmmsort::HostModel model;
+    std::vector<hmmsort::HostModel> models;   // per-channel models of a wave plan (models[0] == model)
+    int64_t T = 0;
+    int64_t C = 1;                            // channels (batched wave plans)
+    std::unique_ptr<hmmsort::Engine> eng;     // its id is the engine the plan runs on
+};
+
+namespace hmmsort {
+int need_device();
+// the plan engine_req asks for under the current options; halo_req >= 0 overrides option "halo"
+int plan_create_engine(hmmsort_plan **out, int64_t T, const int16_t *states, int64_t N, int64_t K, int64_t S,
+                       const hmm_trans *tr, int64_t R, const double *mu, double sigma, int64_t engine_req,
+                       int64_t halo_req = -1);
+struct PlanGuard {
+    hmmsort_plan *p = nullptr;
+    ~PlanGuard() { if (p) hmmsort_plan_destroy(p); }
+};
+void host_slots_trim(size_t keep);   // idle plans of the host-buffer entry points: keep the newest `keep`
 }  // namespace hmmsort

@@ -219,7 +219,6 @@ int ring_launch_virtual(RingDev *r, const double *d_y, double *dst_planes, int64
                         hipStream_t st, double *dst_planes2 = nullptr);
 int ring_bind(RingDev *r, const double *d_y, hipStream_t st);
 int ring_prepare(RingDev *r, const double *d_y, hipStream_t st);
-int ring_profile_enable(RingDev *r, int on);
 int ring_profile_read(RingDev *r, hipStream_t st, std::vector<std::string> &names,
                       std::vector<double> &ms, std::vector<int64_t> &calls);
 

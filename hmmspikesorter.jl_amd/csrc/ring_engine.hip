@@ -211,13 +211,6 @@ void ring_destroy(RingDev *r)
     delete r;
 }
 
-int64_t ring_workspace_bytes(const RingDev *r) { return r->bytes; }
-void ring_geometry(const RingDev *r, int64_t *block, int64_t *halo, int64_t *nchains)
-{
-    if (block) *block = r->g.B;
-    if (halo) *halo = r->g.H;
-    if (nchains) *nchains = r->g.nch;
-}
 
 int ring_diagnostics(RingDev *r, hipStream_t st, int64_t diag[8])
 {
@@ -420,12 +413,6 @@ int ring_bind(RingDev *r, const double *d_y, hipStream_t st)
     return HMMSORT_OK;
 }
 
-int ring_profile_enable(RingDev *r, int on)
-{
-    r->prof_on = on != 0;
-    return HMMSORT_OK;
-}
-
 // Synchronises the stream; returns per-kernel-name total milliseconds and call counts since the
 // last read.
 int ring_profile_read(RingDev *r, hipStream_t st, std::vector<std::string> &names,
@@ -448,22 +435,56 @@ int ring_profile_read(RingDev *r, hipStream_t st, std::vector<std::string> &name
     return HMMSORT_OK;
 }
 
-int ring_viterbi(RingDev *r, const double *d_y, int16_t *d_x, double *d_ll, hipStream_t st)
-{
-    return ring_viterbi_launch(r, d_y, d_x, d_ll, st);
-}
-int ring_estep(RingDev *r, const double *d_y, double *d_stats, hipStream_t st)
-{
-    return ring_estep_launch(r, d_y, d_stats, st);
-}
-int ring_mstep(RingDev *r, const double *d_stats, double *d_out, hipStream_t st)
-{
-    return ring_mstep_launch(r, d_stats, d_out, st);
-}
-int64_t ring_stats_len(const RingDev *r)
-{
+// ---- the engine behind a plan (hmmsort_internal.h) ---------------------------------------------
+namespace {
+struct RingEngine final : Engine {
+    RingDev *r = nullptr;
+    RingEngine() : Engine(HMMSORT_ENGINE_RING) {}
+    ~RingEngine() override { ring_destroy(r); }
+    int set_model(int64_t, const HostModel &m) override { return ring_set_model(r, m); }
+    bool ring_models_only() const override { return true; }
+    void geometry(int64_t *b, int64_t *h, int64_t *n) const override { *b = r->g.B; *h = r->g.H; *n = r->g.nch; }
+    int64_t workspace_bytes() const override { return r->bytes; }
+    int bind(const double *d_y, hipStream_t st) override { return ring_bind(r, d_y, st); }
+    void unbind() override { r->bound_y = nullptr; }
+    int viterbi(const double *d_y, int16_t *d_x, double *d_ll, hipStream_t st) override
+    {
+        return ring_viterbi_launch(r, d_y, d_x, d_ll, st);
+    }
+    int decode_estep(const double *d_y, int16_t *d_x, double *d_ll, double *d_stats, hipStream_t st) override
+    {
+        return ring_decode_estep_launch(r, d_y, d_x, d_ll, d_stats, st);
+    }
     // per ring state G0,G1,G2 | per ring: xi-sum | gamma0 sums (all t, t<T-1), gamma0*y^2, loglik
-    return 3 * (int64_t)r->g.N * r->g.L + r->g.N + 4;
+    int64_t stats_len() const override { return 3 * (int64_t)r->g.N * r->g.L + r->g.N + 4; }
+    int estep(const double *d_y, double *d_stats, hipStream_t st) override { return ring_estep_launch(r, d_y, d_stats, st); }
+    int mstep(const double *d_stats, double *d_out, hipStream_t st) override { return ring_mstep_launch(r, d_stats, d_out, st); }
+    int64_t n_lp() const override { return r->g.N; }   // a template whose entries left the list keeps its slot
+    int set_shard(int64_t own_lo, int64_t own_hi, bool first, bool last) override
+    {
+        if (int rc = check_shard(r->g.T, own_lo, own_hi, first, last)) return rc;
+        r->g.own_lo = own_lo; r->g.own_hi = own_hi;
+        r->g.first = first; r->g.last = last;
+        return HMMSORT_OK;
+    }
+    int diagnostics(hipStream_t st, int64_t diag[8]) override { return ring_diagnostics(r, st, diag); }
+    int profile(int enable) override { r->prof_on = enable != 0; return HMMSORT_OK; }
+    int profile_read(hipStream_t st, std::vector<std::string> &names, std::vector<double> &ms,
+                     std::vector<int64_t> &calls) override
+    {
+        return ring_profile_read(r, st, names, ms, calls);
+    }
+};
+}  // namespace
+
+int ring_engine_create(std::unique_ptr<Engine> *out, const HostModel &m, int64_t T, int64_t block_req,
+                       int64_t halo_req)
+{
+    std::unique_ptr<RingEngine> e(new RingEngine());
+    int rc = ring_create(&e->r, m, T, block_req, halo_req);
+    if (rc) return rc;
+    *out = std::move(e);
+    return HMMSORT_OK;
 }
 
 }  // namespace hmmsort

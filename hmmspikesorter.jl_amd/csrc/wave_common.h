@@ -385,7 +385,6 @@ int wave_graphed(WaveDev *r, int kind, const void *p0, const void *p1, const voi
 }
 
 // wave_engine.hip
-bool wave_supported(const HostModel &m, int64_t T, std::string *why);
 int wave_create(WaveDev **out, const std::vector<HostModel> &models, int64_t T, int64_t block_req,
                 int64_t halo_req);
 int wave_set_model(WaveDev *r, int ch, const HostModel &m);
@@ -410,18 +409,13 @@ int wave_decode_estep(WaveDev *r, const double *d_y, int16_t *d_x, double *d_ll,
                       hipStream_t st);
 int wave_post_sweeps(WaveDev *r, const double *d_y, hipStream_t st);
 // wave_post.hip: posterior marginals, posterior decode, spike confidence
-constexpr int kPostParts = 256;
 int wave_posteriors(WaveDev *r, const double *d_y, double *d_onset, double *d_occ, double *d_silent, double *d_logz,
                     hipStream_t st);
 int wave_post_decode(WaveDev *r, int16_t *d_xm, hipStream_t st);
 // confidences of n events of template a on channel ch (1-based times in device memory), see dev_spike_conf
+// (hmmsort_internal.h)
 int wave_spike_conf(WaveDev *r, int ch, int a, int qv, int64_t jitter, const int64_t *d_times, int64_t n,
                     double *d_conf, hipStream_t st);
 int wave_expected_counts(WaveDev *r, double *counts_out, hipStream_t st);
-// shared by the strict path (capi.cpp): sum_{|d| <= J} src[t + d - shift] (head[-index] for a negative index when
-// head is given, 0 otherwise and outside [0, T)), capped at 1; sums over time of n rows of length T
-int dev_spike_conf(const double *d_src, const double *d_head, int64_t T, int64_t shift, int64_t jitter,
-                   const int64_t *d_times, int64_t n, double *d_conf, hipStream_t st);
-int dev_row_sums(const double *d_rows, int64_t nrows, int64_t T, double *d_part, double *out_host, hipStream_t st);
 
 }  // namespace hmmsort

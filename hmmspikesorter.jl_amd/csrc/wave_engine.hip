@@ -563,6 +563,112 @@ int wave_profile_read(WaveDev *r, hipStream_t st, std::vector<std::string> &name
     return HMMSORT_OK;
 }
 
+// ---- the engine behind a plan (hmmsort_internal.h) ---------------------------------------------
+namespace {
+struct WaveEngine final : Engine {
+    WaveDev *w = nullptr;
+    WaveEngine() : Engine(HMMSORT_ENGINE_WAVE) {}
+    ~WaveEngine() override { wave_destroy(w); }
+    int set_model(int64_t ch, const HostModel &m) override { return wave_set_model(w, (int)ch, m); }
+    bool ring_models_only() const override { return true; }
+    void geometry(int64_t *b, int64_t *h, int64_t *n) const override
+    {
+        *b = w->g.B; *h = w->g.Hw - 1; *n = (int64_t)w->g.nch * w->g.C;
+    }
+    int64_t workspace_bytes() const override { return w->bytes; }
+    int bind(const double *d_y, hipStream_t st) override { return wave_bind(w, d_y, st); }
+    void unbind() override { w->bound_y = nullptr; }
+    int viterbi(const double *d_y, int16_t *d_x, double *d_ll, hipStream_t st) override
+    {
+        return wave_viterbi(w, d_y, d_x, d_ll, st);
+    }
+    int decode_estep(const double *d_y, int16_t *d_x, double *d_ll, double *d_stats, hipStream_t st) override
+    {
+        return wave_decode_estep(w, d_y, d_x, d_ll, d_stats, st);
+    }
+    int64_t stats_len() const override { return wave_stats_len(w); }
+    int estep(const double *d_y, double *d_stats, hipStream_t st) override { return wave_estep(w, d_y, d_stats, st); }
+    int mstep(const double *d_stats, double *d_out, hipStream_t st) override { return wave_mstep(w, d_stats, d_out, st); }
+    int64_t n_lp() const override { return w->g.N; }   // a template whose entries left the list keeps its slot
+    int set_shard(int64_t own_lo, int64_t own_hi, bool first, bool last) override
+    {
+        // The slice's own ends are arbitrary starts (emission-only first column, beta = 0 at the end): what
+        // certifies that they have been forgotten where the owned range begins / ends is a certified chain
+        // boundary INSIDE each halo -- kw_fb_check compares, at every chain boundary, a warm-up started from
+        // "silent, rings empty" with the neighbouring chain's own sweep, and the two can only agree when
+        // both have forgotten where they started.  So an interior shard edge must have a chain boundary
+        // between the slice end and the owned range.
+        WaveGeom &g = w->g;
+        if (int rc = check_shard(g.T, own_lo, own_hi, first, last)) return rc;
+        const int64_t B = g.B, last_boundary = (int64_t)(g.nch - 1) * B;
+        HS_CHECK(first || (g.nch > 1 && own_lo >= B), HMMSORT_EINVAL,
+                 "plan_set_shard: no chain boundary inside the leading halo (owned range starts at %lld, chains are "
+                 "%lld samples): widen the halo or set a shorter chain length (option \"block\")",
+                 (long long)own_lo, (long long)B);
+        HS_CHECK(last || (g.nch > 1 && own_hi <= last_boundary), HMMSORT_EINVAL,
+                 "plan_set_shard: no chain boundary inside the trailing halo (owned range ends at %lld, last chain "
+                 "boundary at %lld): widen the halo or set a shorter chain length (option \"block\")",
+                 (long long)own_hi, (long long)last_boundary);
+        g.own_lo = own_lo; g.own_hi = own_hi;
+        g.first = first; g.last = last;
+        return HMMSORT_OK;
+    }
+    int diagnostics(hipStream_t st, int64_t diag[8]) override { return wave_diagnostics(w, st, diag); }
+    int tie_stats(hipStream_t st, int64_t out[8]) override { return wave_tie_stats(w, st, out); }
+    int profile(int enable) override { w->prof_on = enable != 0; return HMMSORT_OK; }
+    int profile_read(hipStream_t st, std::vector<std::string> &names, std::vector<double> &ms,
+                     std::vector<int64_t> &calls) override
+    {
+        return wave_profile_read(w, st, names, ms, calls);
+    }
+    bool has_posteriors() const override { return true; }
+    int posteriors(const HostModel &, const double *d_y, double *d_onset, double *d_occ, double *d_silent,
+                   double *d_logz, hipStream_t st) override
+    {
+        return wave_posteriors(w, d_y, d_onset, d_occ, d_silent, d_logz, st);
+    }
+    bool posteriors_valid() const override { return w->post_valid; }
+    int posterior_decode(int16_t *d_xm, hipStream_t st) override { return wave_post_decode(w, d_xm, st); }
+    int spike_conf(int ch, int a, int qv, int64_t jitter, const int64_t *d_times, int64_t n, double *d_conf,
+                   hipStream_t st) override
+    {
+        return wave_spike_conf(w, ch, a, qv, jitter, d_times, n, d_conf, st);
+    }
+    int expected_counts(double *counts_out, hipStream_t st) override { return wave_expected_counts(w, counts_out, st); }
+    int debug_record(double *out64) override
+    {
+        HS_HIP(hipDeviceSynchronize());
+        HS_HIP(hipMemcpy(out64, w->dbg, 64 * sizeof(double), hipMemcpyDeviceToHost));
+        return HMMSORT_OK;
+    }
+    // which: 0 FA0 (log alpha silent), 1 FREF, 2 FV (N x T), 3 rho (N x T), 4 Rf (N x T), 5 vend, 6 vpre (chain
+    // records), 7 exact trellis values of the decoded path at block starts (wave_ties.hip)
+    int debug_array(int which, double *out, int64_t n) override
+    {
+        HS_HIP(hipDeviceSynchronize());
+        const int64_t CT = (int64_t)w->g.C * w->g.T, NCT = CT * w->g.N;
+        const int64_t rec = (int64_t)w->g.C * w->g.nch * (1 + (int64_t)w->g.N * w->g.L);
+        const double *srcs[8] = {w->FA0, w->FREF, w->FV, w->rho, w->Rf, w->vend, w->vpre, w->tie_v};
+        const int64_t lens[8] = {CT, CT, NCT, NCT, NCT, rec, rec, (int64_t)w->g.C * (w->tie_nblk + 1)};
+        HS_CHECK(which >= 0 && which < 8, HMMSORT_EINVAL, "plan_debug_array: unknown array %d", which);
+        HS_CHECK(n >= 0 && n <= lens[which], HMMSORT_EINVAL, "plan_debug_array: %lld entries asked, array %d holds %lld",
+                 (long long)n, which, (long long)lens[which]);
+        HS_HIP(hipMemcpy(out, srcs[which], n * sizeof(double), hipMemcpyDeviceToHost));
+        return HMMSORT_OK;
+    }
+};
+}  // namespace
+
+int wave_engine_create(std::unique_ptr<Engine> *out, const std::vector<HostModel> &models, int64_t T,
+                       int64_t block_req, int64_t halo_req)
+{
+    std::unique_ptr<WaveEngine> e(new WaveEngine());
+    int rc = wave_create(&e->w, models, T, block_req, halo_req);
+    if (rc) return rc;
+    *out = std::move(e);
+    return HMMSORT_OK;
+}
+
 }  // namespace hmmsort
 
 // ---- self-test of the cross-lane primitives (DPP scans vs their shuffle references) ---------------
