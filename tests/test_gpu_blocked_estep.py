@@ -5,6 +5,7 @@ engine (the reference's own op order on materialised alpha/beta) at 10^6 samples
 import numpy as np
 import pytest
 
+import posterior_model as PM
 from conftest import to_oracle_sm, two_templates
 
 pytestmark = pytest.mark.gpu
@@ -113,3 +114,66 @@ def test_blocks_shorter_than_the_warmup(O, H):
         H.set_option("block", 0)
         H.shutdown()
     assert np.allclose(mu_n, omu, rtol=1e-8, atol=1e-11) and abs(sig_n - osig) <= 1e-9 * osig
+
+
+# One case per row of bes_run's (states per thread, launch bound) table, two templates so that S = K^2.  The last row,
+# <16,1024>, has no case: its posterior instantiation ended in an illegal memory access on the one run it has had
+# (K = 96, 9 216 states; DESIGN.md section 3.5 "Open: the <16,1024> posterior instantiation").  Add (96, "<16,1024>")
+# when its cause is known.
+DISPATCH_ROWS = [(12, "256 threads"), (20, "<1,1024>"), (30, "<2,1024>"), (40, "<4,512>"), (60, "<8,512>"),
+                 (80, "<8,1024>")]
+
+
+@pytest.mark.parametrize("K,row", DISPATCH_ROWS)
+def test_every_dispatch_row_matches_oracle(O, H, K, row):
+    """E-step + M-step and posteriors through the plan API (no ladder that could end on the strict engine) on a
+    blocked plan, at 4 096 samples: several blocks under the default geometry, so both warm-ups, the boundary
+    records and a ragged last block are exercised.  No shape passes without certified boundaries: the warm-up is
+    the first of default, 512, 1 024 samples that certifies, and is printed."""
+    import torch
+    from test_gpu_blocked_big import Post, estep_mstep, plan_with_certificates
+    from test_gpu_posteriors import check_against_oracle, check_decode
+    N, T, sigma = 2, 4_096, 0.4
+    y, sm, mu0 = overlap_case(H, N, K, T, seed=50 + K)
+    S, KN = sm.nstates, K * N
+    assert S == K * K
+    nt = 256 if S <= 256 else (512 if S <= 4096 else 1024)
+    name = "K=%d S=%d row %s (%d states per thread)" % (K, S, row, -(-S // nt))
+    osm = to_oracle_sm(O, sm)
+    # O.train_step is update(forward, backward) and posterior_model.gamma is exp(forward + backward - z): one pair of
+    # oracle sweeps serves both (the update alone takes 4 s at K = 80)
+    al, be = O.forward(y, osm, mu0, sigma), O.backward(y, osm, mu0, sigma)
+    osm_n, omu, osig, olp, opp = O.update(al, be, osm, mu0.copy(order="F"), sigma, y)
+    m = al[:, -1].max()
+    z = float(m + np.log(np.exp(al[:, -1] - m).sum()))
+    g = np.exp(al + be - z)
+    del al, be
+    tol = PM.tolerance(g)
+    dy = torch.from_numpy(y).cuda()
+    H.set_option("engine", H.ENGINE_BLOCKED)
+    try:
+        plan, (stats, out), diag = plan_with_certificates(H, T, sm, mu0, sigma, estep_mstep(dy))
+        info = plan.info()
+        plan.close()
+        o = out.cpu().numpy()
+        nsrc1 = int((sm.transitions["src"] == 1).sum())
+        mu, sig, lp = o[:KN].reshape((K, N), order="F"), o[KN], o[KN + 1:KN + nsrc1]
+        print("%s: E-step at a warm-up of %d samples, %d blocks of %d, certificates %s: max|d mu| %.3g  rel d sigma "
+              "%.3g  max|d lp| %.3g" % (name, info["halo"], info["nchains"], info["block"], diag[3:7],
+                                         np.abs(mu - omu).max(), abs(sig - osig) / osig, np.abs(lp - olp).max()), flush=True)
+        assert info["nchains"] >= 3, info
+        assert diag[3] == 0 and diag[5] == 0, diag
+        assert np.allclose(mu, omu, rtol=1e-8, atol=1e-11)
+        assert abs(sig - osig) <= 1e-9 * osig
+        assert len(lp) == len(olp) and np.allclose(lp, olp, rtol=1e-8, atol=1e-11)
+        plan, post, diag = plan_with_certificates(H, T, sm, mu0, sigma, lambda p: Post(p, dy, N, T))
+        info = plan.info()
+        plan.close()
+        print("%s: posteriors at a warm-up of %d samples, certificates %s" % (name, info["halo"], diag[3:7]), flush=True)
+        assert diag[3] == 0 and diag[5] == 0, diag
+        check_against_oracle(name, post, g, z, sm.states, tol)
+        check_decode(name, post.xm, g, tol)
+    finally:
+        H.set_option("halo", 0)
+        H.set_option("engine", H.ENGINE_AUTO)
+        H.shutdown()
