@@ -293,6 +293,15 @@ __device__ __forceinline__ double wave_sum(double v)
     return v;
 }
 
+// Orders a wavefront's LDS accesses across its lanes: the hardware serves one wave's LDS instructions in program
+// order, so what lanes of the SAME wave exchange through LDS needs only that the compiler keeps that order.
+__device__ __forceinline__ void wave_lds_order()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // ---- exact near-tie resolver (wave_ties.hip) ------------------------------------------------------
 constexpr int kTieBlk = 512;                 // samples per block of the exact prefix
 constexpr int kTieCap = 65536;               // flagged decisions on the decoded path kept per channel

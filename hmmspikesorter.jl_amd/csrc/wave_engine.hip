@@ -357,6 +357,53 @@ int wave_diagnostics(WaveDev *r, hipStream_t st, int64_t diag[8])
 
 int64_t wave_stats_len(const WaveDev *r) { return 3 * (int64_t)r->g.N * r->g.L + r->g.N + 4; }
 
+// virtual onsets t' = -j, j = 1..L-1: rings already running at the first sample (the reference's
+// first column is "emission only" for every state: viterbi.jl:55-62, baumwelch.jl:36).  Their score
+// covers phases k = 1+j..L on samples 0..L-1-j.  V[ch][a][j]; V[.][.][L] = -inf ("no such onset").
+// Runs as workgroup 0 of every channel's pre-pass grid (it needs y, the means and cint only, and a launch of
+// its own sat in front of every sweep).  The serial sum takes its operands eight steps at a time: the loads of a
+// batch are unconditional (clamped) and issued before the batch's adds, which keep their order.
+__device__ __forceinline__ void virtual_onsets(const WaveGeom &g, int ch, const WaveConst *__restrict__ cst,
+                                               const double *__restrict__ y, const double *__restrict__ mean,
+                                               const double *__restrict__ cint, double *__restrict__ virt)
+{
+    const int L = g.L, N = g.N, S = 1 + N * L;
+    const double *yc = y + (int64_t)ch * g.T, *mc = mean + (int64_t)ch * S;
+    const double *ci = cint + (int64_t)ch * N * (L + 1);
+    const double den = cst[ch].den, A = cst[ch].A;
+    for (int i = threadIdx.x; i < N * L; i += blockDim.x) {
+        const int a = i / L, j = i % L + 1;  // j = 1..L
+        double v;
+        if (j == L) {
+            v = -INFINITY;
+        } else if (j == L - 1) {
+            // A ring in its LAST phase at the first sample: one emission term.  Template tails are
+            // ~1e-16 (sin(3*pi)), so these N candidates tie to the last bit in the reference, whose
+            // first column is funcl = A - d*d/den (viterbi.jl:55-62); round exactly like it, then take
+            // A out again, so that equal reference values stay equal here (lowest ring wins the tie).
+            const double d = yc[0] - mc[1 + a * L + (L - 1)];
+            v = (A - (d * d) / den) - A;
+        } else {
+            double acc = 0.0;
+            for (int k0 = 1 + j; k0 <= L; k0 += 8) {
+                double yv[8], mv[8];
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    const int k = k0 + u <= L ? k0 + u : L;
+                    yv[u] = yc[k - 1 - j]; mv[u] = mc[1 + a * L + (k - 1)];
+                }
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    const double d = yv[u] - mv[u];
+                    if (k0 + u <= L) acc += d * d;
+                }
+            }
+            v = (ci[a * (L + 1) + L] - ci[a * (L + 1) + (1 + j)]) - acc / den;
+        }
+        virt[((int64_t)ch * N + a) * (L + 1) + j] = v;
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // pre-pass: ring scores for every onset time t' in [0, T) of every channel, natural layout
 //   Rf[ch][a][t'] = Cint[a][kmax] - (sum_k y^2 - 2 sum_k y*mean(a,k) + Msq[a][kmax]) / den,
@@ -369,8 +416,18 @@ int64_t wave_stats_len(const WaveDev *r) { return 3 * (int64_t)r->g.N * r->g.L +
 // Accumulation order over the lags is the textbook one (k = 0..L-1, fused multiply-add).
 // Also accumulates sum y and sum y^2 per channel (magnitude of the reference's trellis, for the
 // near-tie threshold of the Viterbi sweep).
+// Grid (1 + tiles, channels): workgroup 0 of a channel computes the virtual onsets (from mean_states, the
+// state-major means; the tiles use the lag-major table `mean`), so tile i is workgroup blockIdx.x = i + 1.
 // ------------------------------------------------------------------------------------------
 template <int N> constexpr int pre_rows() { return N <= 4 ? 8 : 4; }   // measured: N = 4: 4 rows 0.30 ms, 8 rows 0.19 ms, 16 rows 0.24 ms (10 M samples); N = 8: 8 rows 2.44 ms, 4 rows 1.92 ms (40 M)
+
+// dynamic LDS of a pre-pass workgroup: the padded y tile with its tail of max(L, 256) samples
+template <int N> static size_t pre_lds(int L)
+{
+    constexpr int R = pre_rows<N>();
+    const int n = 256 * R + (L > 256 ? L : 256);
+    return (size_t)(n + n / R + 2) * sizeof(double);
+}
 
 template <int N>
 __global__ __launch_bounds__(256) void kw_prepass(WaveGeom g, const WaveConst *__restrict__ cst,
@@ -379,25 +436,56 @@ __global__ __launch_bounds__(256) void kw_prepass(WaveGeom g, const WaveConst *_
                                                   const double *__restrict__ cint,
                                                   const double *__restrict__ msq,
                                                   double *__restrict__ Rf, double *__restrict__ W2,
-                                                  double *__restrict__ ysum)
+                                                  double *__restrict__ ysum, const double *__restrict__ mean_states,
+                                                  double *__restrict__ virt)
 {
     constexpr int R = pre_rows<N>(), TILE = 256 * R;
-    extern __shared__ double ly[];  // y tile (TILE + L, padded); reused for the transposed results (TILE, padded)
+    extern __shared__ double ly[];  // y tile (TILE + max(L, 256), padded: pre_lds); reused for the transposed results (TILE, padded)
     __shared__ double red[8];
     const int ch = blockIdx.y, L = g.L, tid = threadIdx.x;
-    const int64_t T = g.T, t0 = (int64_t)blockIdx.x * TILE;
+    if (blockIdx.x == 0) {   // workgroup 0 of a channel: the virtual onsets; the tiles follow
+        virtual_onsets(g, ch, cst, y, mean_states, cint, virt);
+        return;
+    }
+    const int64_t T = g.T, t0 = (int64_t)(blockIdx.x - 1) * TILE;
     const double *yc = y + (int64_t)ch * T;
     const double *mc = mean + (int64_t)ch * N * L;    // lag-major: mc[k * N + a]
     auto pad = [](int i) { return i + i / R; };
     double s1 = 0.0, s2 = 0.0;
-    for (int i = tid; i < TILE + L; i += 256) {
-        const int64_t t = t0 + i;
-        const double v = yc[t < T ? t : T - 1];
-        const double yv = t < T ? v : 0.0;
-        ly[pad(i)] = yv;
-        if (i < TILE) { s1 += yv; s2 = __builtin_fma(yv, yv, s2); }
+    {
+        // all loads of a thread (R full passes and the first pass of the L-sample tail) leave before the first
+        // one is waited for: one trip to memory per workgroup instead of one per pass.  Unconditional, clamped
+        // 32-bit offsets from the tile's first sample; LDS writes and the partial sums in the order of the passes
+        // (the tail pass writes all 256 slots: the tile has room for them, see pre_lds).
+        const double *yt = yc + t0;
+        const int nv = (int)(T - t0 < TILE + 512 ? T - t0 : TILE + 512);   // samples of the recording from t0 on
+        double v[R + 1];
+#pragma unroll
+        for (int q = 0; q <= R; q++) {
+            const unsigned i = tid + 256 * q;
+            v[q] = yt[i < (unsigned)nv ? i : (unsigned)nv - 1u];
+        }
+#pragma unroll
+        for (int q = 0; q <= R; q++) {
+            const int i = tid + 256 * q;
+            const double yv = i < nv ? v[q] : 0.0;
+            ly[pad(i)] = yv;
+            if (q < R) { s1 += yv; s2 = __builtin_fma(yv, yv, s2); }
+        }
+        for (int i = TILE + 256 + tid; i < TILE + L; i += 256) {   // rings longer than 256 states
+            const int64_t t = t0 + i;
+            const double yv = yc[t < T ? t : T - 1];
+            ly[pad(i)] = t < T ? yv : 0.0;
+        }
     }
+    // the channel sums leave here, so that they hold no registers through the lag loop
+    s1 = wave_sum(s1); s2 = wave_sum(s2);
+    if ((tid & 63) == 0) { red[tid >> 6] = s1; red[4 + (tid >> 6)] = s2; }
     __syncthreads();
+    if (tid == 0) {
+        atomicAdd(&ysum[2 * ch], (red[0] + red[1]) + (red[2] + red[3]));
+        atomicAdd(&ysum[2 * ch + 1], (red[4] + red[5]) + (red[6] + red[7]));
+    }
     // window of R + 1 registers, slot (r + k) mod (R + 1) = y[t + k + r]; the free slot receives the sample
     // the NEXT lag needs (one lag ahead of its use, like the means), so the loop is unrolled by R + 1
     constexpr int U = R + 1;
@@ -449,63 +537,29 @@ __global__ __launch_bounds__(256) void kw_prepass(WaveGeom g, const WaveConst *_
     };
     {
         // ring by ring through LDS, thread-major in, time-major out (stores straight from the registers, lanes
-        // 64 bytes apart per instruction, measured slower: 0.225 against 0.194 ms at 10 M samples)
+        // 64 bytes apart per instruction, measured slower: 0.225 against 0.194 ms at 10 M samples).  A wave's 64 R
+        // onsets are one contiguous segment of every plane, staged in the slots its own lanes own: once every wave
+        // has left the lag loop (the wave below still reads L + R samples of this wave's y) the planes need the
+        // order of the wave's own LDS accesses only, no workgroup barrier.  The LDS stores are unpredicated.
+        __syncthreads();
+        const int lane = tid & 63, seg = (tid >> 6) * (64 * R);
 #pragma unroll
         for (int a = 0; a <= N; a++) {
-            __syncthreads();
             const int64_t cb = ((int64_t)ch * N + (a < N ? a : 0)) * (L + 1);
             const double msqL = msq[cb + L], cintL = cint[cb + L];
+            wave_lds_order();
 #pragma unroll
             for (int r = 0; r < R; r++)
                 ly[pad(R * tid + r)] = a < N ? value(a < N ? a : 0, r, msqL, cintL, cb) : ysq[r];
-            __syncthreads();
+            wave_lds_order();
             double *dst = a < N ? Rf + ((int64_t)ch * N + a) * T : W2 + (int64_t)ch * T;
-            for (int i = tid; i < TILE; i += 256)
-                if (t0 + i < T) dst[t0 + i] = ly[pad(i)];
-        }
-    }
-    s1 = wave_sum(s1); s2 = wave_sum(s2);
-    __syncthreads();
-    if ((tid & 63) == 0) { red[tid >> 6] = s1; red[4 + (tid >> 6)] = s2; }
-    __syncthreads();
-    if (tid == 0) {
-        atomicAdd(&ysum[2 * ch], (red[0] + red[1]) + (red[2] + red[3]));
-        atomicAdd(&ysum[2 * ch + 1], (red[4] + red[5]) + (red[6] + red[7]));
-    }
-}
-
-// virtual onsets t' = -j, j = 1..L-1: rings already running at the first sample (the reference's
-// first column is "emission only" for every state: viterbi.jl:55-62, baumwelch.jl:36).  Their score
-// covers phases k = 1+j..L on samples 0..L-1-j.  V[ch][a][j]; V[.][.][L] = -inf ("no such onset").
-__global__ void kw_virtual(WaveGeom g, const WaveConst *__restrict__ cst, const double *__restrict__ y,
-                           const double *__restrict__ mean, const double *__restrict__ cint,
-                           double *__restrict__ virt)
-{
-    const int L = g.L, N = g.N, ch = blockIdx.x, S = 1 + N * L;
-    const double *yc = y + (int64_t)ch * g.T, *mc = mean + (int64_t)ch * S;
-    const double *ci = cint + (int64_t)ch * N * (L + 1);
-    const double den = cst[ch].den, A = cst[ch].A;
-    for (int i = threadIdx.x; i < N * L; i += blockDim.x) {
-        const int a = i / L, j = i % L + 1;  // j = 1..L
-        double v;
-        if (j == L) {
-            v = -INFINITY;
-        } else if (j == L - 1) {
-            // A ring in its LAST phase at the first sample: one emission term.  Template tails are
-            // ~1e-16 (sin(3*pi)), so these N candidates tie to the last bit in the reference, whose
-            // first column is funcl = A - d*d/den (viterbi.jl:55-62); round exactly like it, then take
-            // A out again, so that equal reference values stay equal here (lowest ring wins the tie).
-            const double d = yc[0] - mc[1 + a * L + (L - 1)];
-            v = (A - (d * d) / den) - A;
-        } else {
-            double acc = 0.0;
-            for (int k = 1 + j; k <= L; k++) {
-                const double d = yc[k - 1 - j] - mc[1 + a * L + (k - 1)];
-                acc += d * d;
+#pragma unroll
+            for (int q = 0; q < R; q++) {
+                const int i = seg + lane + 64 * q;
+                const double o = ly[pad(i)];
+                if (t0 + i < T) dst[t0 + i] = o;
             }
-            v = (ci[a * (L + 1) + L] - ci[a * (L + 1) + (1 + j)]) - acc / den;
         }
-        virt[((int64_t)ch * N + a) * (L + 1) + j] = v;
     }
 }
 
@@ -519,17 +573,13 @@ int wave_prepare(WaveDev *r, const double *d_y, hipStream_t st)
         constexpr int N = decltype(n)::value;
         WPROF(r, "kw_prepass", st);
         constexpr int kPreTile = 256 * pre_rows<N>();
-        hipLaunchKernelGGL((kw_prepass<N>), dim3((unsigned)((g.T + kPreTile - 1) / kPreTile), g.C), dim3(256),
-                           (size_t)((kPreTile + g.L) + (kPreTile + g.L) / pre_rows<N>() + 2) * sizeof(double), st, g, r->d_cst, d_y, r->d_meanT, r->d_cint,
-                           r->d_msq, r->Rf, r->W2, r->ysum);
+        hipLaunchKernelGGL((kw_prepass<N>), dim3(1 + (unsigned)((g.T + kPreTile - 1) / kPreTile), g.C), dim3(256),
+                           pre_lds<N>(g.L), st, g, r->d_cst, d_y, r->d_meanT, r->d_cint,
+                           r->d_msq, r->Rf, r->W2, r->ysum, r->d_mean, r->virt);
         HS_HIP(hipGetLastError());
         return HMMSORT_OK;
     });
-    if (rc) return rc;
-    { WPROF(r, "kw_virtual", st);
-      hipLaunchKernelGGL(kw_virtual, dim3(g.C), dim3(256), 0, st, g, r->d_cst, d_y, r->d_mean, r->d_cint, r->virt); }
-    HS_HIP(hipGetLastError());
-    return HMMSORT_OK;
+    return rc;
 }
 
 int wave_bind(WaveDev *r, const double *d_y, hipStream_t st)
