@@ -8,7 +8,7 @@ from . import _lib, dist, synth
 from ._lib import (ENGINE_AUTO, ENGINE_BLOCKED, ENGINE_RING, ENGINE_STRICT, ENGINE_WAVE, HmmsortError, device_count,
                    get_option, set_option, shutdown)
 from .api import (HMMSpikeTemplateModel, HMMSpikingModel, Posteriors, StateMatrix, backward, extract_spiketimes,
-                  fit, forward,
+                  fit, fit_channels, forward,
                   posterior_decode, posteriors, predict, reconstruct_signal, spike_confidence, train_model, train_step, unroll_mlseq, update,
                   viterbi)
 from .device import Plan
@@ -19,7 +19,7 @@ from .synth import create_signal, create_spike_template
 
 __all__ = ["StateMatrix", "HMMSpikeTemplateModel", "HMMSpikingModel", "forward", "backward",
            "update", "train_model", "train_step", "viterbi", "reconstruct_signal", "unroll_mlseq",
-           "fit", "predict", "extract_spiketimes", "Plan", "create_signal", "create_spike_template", "HmmsortError",
+           "fit", "fit_channels", "predict", "extract_spiketimes", "Plan", "create_signal", "create_spike_template", "HmmsortError",
            "set_option", "get_option", "shutdown", "device_count", "ENGINE_AUTO", "ENGINE_STRICT",
            "ENGINE_RING", "ENGINE_BLOCKED", "ENGINE_WAVE", "get_lp", "sort_data", "find_best_overlap",
            "condense_candidates", "condense_templates", "remove_sparse", "remove_small", "prune_templates",

@@ -15,13 +15,16 @@ LIB_PATH = os.environ.get("HMMSORT_LIB", os.path.join(_HERE, "libhmmsort_hip.so"
 TRANS_DTYPE = np.dtype([("src", np.int64), ("dst", np.int64), ("lp", np.float64)], align=True)
 assert TRANS_DTYPE.itemsize == 24
 
-OK, EINVAL, ENOMEM, EHIP, ENOCONV, EUNSUP = 0, -1, -2, -3, -4, -5
+OK, EINVAL, ENOMEM, EHIP, ENOCONV, EUNSUP, ENOSILENT = 0, -1, -2, -3, -4, -5, -6
+SAMPLES_I16, SAMPLES_I32, SAMPLES_F32, SAMPLES_F64 = 0, 1, 2, 3
 ENGINE_AUTO, ENGINE_STRICT, ENGINE_RING, ENGINE_BLOCKED, ENGINE_WAVE = 0, 1, 2, 3, 4
 # option "blocked_hbm_columns": the blocked E-step / posteriors with their state columns in device memory.  OFF
 # (default): models past the LDS limit (~9 900 states) are refused as before; AUTO: they take the device-memory
 # kernels; FORCE: every blocked plan does (cross-checks).  A plan keeps the value it was created under.
 OPT_BLOCKED_HBM_COLUMNS = "blocked_hbm_columns"
 HBM_COLUMNS_OFF, HBM_COLUMNS_AUTO, HBM_COLUMNS_FORCE = 0, 1, 2
+# option "fit_streams": channels one worker of hmmsort_fit_channels keeps in flight, each on its own stream (1..16)
+OPT_FIT_STREAMS = "fit_streams"
 
 
 class HmmsortError(RuntimeError):
@@ -33,6 +36,13 @@ class HmmsortError(RuntimeError):
 _i64, _f64, _int = C.c_int64, C.c_double, C.c_int
 _vp = C.c_void_p
 _pi64 = C.POINTER(C.c_int64)
+
+
+class Model(C.Structure):
+    """struct hmmsort_model: the model arguments of hmmsort_viterbi, one record per channel"""
+    _fields_ = [("states", _vp), ("N", _i64), ("K", _i64), ("S", _i64), ("tr", _vp), ("R", _i64), ("mu", _vp),
+                ("sigma", _f64)]
+
 
 # name -> (restype, argtypes); every symbol include/hmmsort.h declares
 SIGNATURES = {
@@ -47,6 +57,11 @@ SIGNATURES = {
     "hmmsort_build_transitions": (_i64, [_i64, _i64, _vp, _i64, _int, _vp, _i64]),
     "hmmsort_viterbi": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _f64, _vp, _vp]),
     "hmmsort_viterbi_i16": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _f64, _vp, _vp]),
+    "hmmsort_fit_chunked": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _f64, _vp, _vp]),
+    "hmmsort_fit_chunked_i16": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _f64, _vp, _vp]),
+    "hmmsort_fit_channels": (_int, [_i64, C.POINTER(_vp), _int, _i64, _i64, C.POINTER(Model), C.POINTER(_int), _i64,
+                                    C.POINTER(_vp), _vp, C.POINTER(_int)]),
+    "hmmsort_chunk_stitch": (_int, [_vp, _i64, _int, _int, _vp, _vp, _vp]),
     "hmmsort_samples_to_f64": (_int, [_vp, C.c_int, _i64, _i64, _vp, _vp]),
     "hmmsort_forward": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _f64, _vp]),
     "hmmsort_backward": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _f64, _vp]),

@@ -414,6 +414,47 @@ def fit(templates, X, chunksize=None):
     return HMMSpikingModel(templates, ml_seq, ll, X)
 
 
+def fit_channels(templates, X, chunksize=None, devices=None):
+    """The chunked decode of fit (fit.jl:11-42) for C recording channels in one native call
+    (hmmsort_fit_channels): the chunk loop, the stitch and the per-channel state stay behind the C ABI, and
+    channels on the same device are decoded in step on streams of their own (option "fit_streams").
+
+    `templates`: one HMMSpikeTemplateModel for every channel, or a list of C of them (each channel its own
+    templates, src/hmmsort.jl:79-83).  `X`: C x T (float64 or int16, rows C-contiguous) or a list of C
+    one-dimensional arrays of equal length.  `chunksize=None`: every channel in one decode.  `devices`: list of
+    device numbers, channel c runs on devices[c % len(devices)]; None = the current device.
+    Returns a list of HMMSpikingModel.  A channel the reference would die on (no silent sample where the stitch
+    needs one) raises HmmsortError naming the channel."""
+    rows = [X[c] for c in range(len(X))]
+    if not rows:
+        raise ValueError("fit_channels: no channel")
+    raw = all(isinstance(r, np.ndarray) and r.dtype == np.int16 for r in rows)
+    rows = [np.ascontiguousarray(r) if raw else _signal(r) for r in rows]
+    nch, n = len(rows), len(rows[0])
+    if any(r.ndim != 1 or len(r) != n for r in rows):
+        raise ValueError("fit_channels: channels must be one-dimensional and of equal length")
+    tms = list(templates) if isinstance(templates, (list, tuple)) else [templates] * nch
+    if len(tms) != nch:
+        raise ValueError("fit_channels: %d template models for %d channels" % (len(tms), nch))
+    keep = []
+    models = (_lib.Model * nch)()
+    for c, tm in enumerate(tms):
+        k, m = _model_args(tm.state_matrix, tm.mu, tm.sigma)
+        keep.append(k)
+        models[c] = _lib.Model(*m)
+    ml = [np.zeros(n, dtype=np.int16) for _ in range(nch)]
+    ll = np.zeros(nch)
+    status = (C.c_int * nch)()
+    ys = (C.c_void_p * nch)(*[r.ctypes.data for r in rows])
+    outs = (C.c_void_p * nch)(*[m.ctypes.data for m in ml])
+    dev = (C.c_int * len(devices))(*devices) if devices else None
+    rc = lib().hmmsort_fit_channels(nch, ys, _lib.SAMPLES_I16 if raw else _lib.SAMPLES_F64, n,
+                                    0 if chunksize is None else int(chunksize), models, dev,
+                                    len(devices) if devices else 0, outs, ptr(ll), status)
+    check(rc)
+    return [HMMSpikingModel(tms[c], ml[c], float(ll[c]), rows[c]) for c in range(nch)]
+
+
 def predict(model):
     """StatsBase.predict(model)   fit.jl:54-56."""
     tm = model.template_model

@@ -119,6 +119,9 @@ int hmmsort_set_option(const char *key, int64_t value)
     } else if (!strcmp(key, "tie_debug")) {
         HS_CHECK(value >= 0 && value <= 3, HMMSORT_EINVAL, "set_option: tie_debug must be 0..3");
         options_modify([&](Options &o) { o.tie_debug = value; });
+    } else if (!strcmp(key, "fit_streams")) {
+        HS_CHECK(value >= 1 && value <= 16, HMMSORT_EINVAL, "set_option: fit_streams must be 1..16");
+        options_modify([&](Options &o) { o.fit_streams = value; });
     } else if (!strcmp(key, "plan_cache")) {
         HS_CHECK(value >= 0 && value <= 64, HMMSORT_EINVAL, "set_option: plan_cache must be 0..64");
         options_modify([&](Options &o) { o.plan_cache = value; });
@@ -143,6 +146,7 @@ int hmmsort_get_option(const char *key, int64_t *value)
     else if (!strcmp(key, "blocked_hbm_columns")) *value = o.blocked_hbm_columns;
     else if (!strcmp(key, "tie_scale")) *value = o.tie_scale;
     else if (!strcmp(key, "tie_debug")) *value = o.tie_debug;
+    else if (!strcmp(key, "fit_streams")) *value = o.fit_streams;
     else if (!strcmp(key, "last_escalations")) *value = last_escalations();
     else {
         set_error("get_option: unknown key '%s'", key);

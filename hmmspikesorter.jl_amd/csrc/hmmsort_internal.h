@@ -45,6 +45,7 @@ struct Options {
     int64_t tie_scale = 1;         // test aid: multiplies the wave engine's near-tie threshold (more decisions flagged)
     int64_t blocked_hbm_columns = 0;   // blocked E-step / posteriors with the state columns in device memory: 0, 1, 2
     int64_t tie_debug = 0;         // test aids: 1 the resolver folds the exact prefix to the end, 2 resolver off
+    int64_t fit_streams = 4;       // hmmsort_fit_channels: channels one worker keeps in flight, each on its own stream
 };
 // process-wide options behind a mutex: entry points work on a snapshot taken when they start
 Options options_get();
@@ -298,6 +299,16 @@ int dev_spike_compact(const int16_t *d_x, int64_t T, const uint32_t *d_match, in
                       hipStream_t st);
 int dev_unroll(const int16_t *d_x, int64_t T, const int16_t *d_states, int64_t N, int64_t S,
                int16_t *d_out, hipStream_t st);
+// chunked decode (chunk_stitch.hip): the stitch rule of fit.jl:24-36 on a decoded chunk (hmmsort_chunk_stitch), and
+// p[0..n) = v for the path's initial ones
+int dev_chunk_stitch(const int16_t *d_x, int64_t k, bool lead, bool trail, int16_t *d_dst, int64_t *d_lk,
+                     hipStream_t st);
+int dev_fill_i16(int16_t *d_p, int64_t n, int16_t v, hipStream_t st);
+// d_ll[0] = viterbi.jl:92-96 along the decoded chunk d_x[0..k) in the reference's operation order, bit for bit;
+// mean / in_* as in HostModel, d_pv: k doubles of scratch
+int dev_chunk_ll(const double *d_y, const int16_t *d_x, int64_t k, int64_t S, const double *d_mean,
+                 const int32_t *d_in_ptr, const int32_t *d_in_src, const double *d_in_lp, double sigma, double *d_pv,
+                 double *d_ll, hipStream_t st);
 // posterior helpers (wave_post.hip): sum_{|d| <= J} src[t + d - shift] (head[-index] for a negative index when
 // head is given, 0 otherwise and outside [0, T)), capped at 1; sums over time of n rows of length T
 constexpr int kPostParts = 256;

@@ -3,9 +3,12 @@
 // that uploads the signal, runs the call on a plan and climbs the escalation ladder when the plan's own
 // certificates fail.  No CPU compute path exists here.
 #include <algorithm>
+#include <atomic>
 #include <cstring>
+#include <map>
 #include <memory>
 #include <mutex>
+#include <thread>
 
 #include "hmmsort_internal.h"
 
@@ -164,11 +167,12 @@ bool strict_table_does_not_fit(const hmmsort_plan *p, const Options &opt, int64_
 // result stands, and out(slot) brings it to the caller.  The slot goes back to the cache only with the plan a
 // first attempt builds.
 template <class Run, class Out>
-int host_call(const Entry &e, const void *y, int sample_type, int64_t T, const ModelArgs &a, Run run, Out out)
+int host_call(const Entry &e, const void *y, int sample_type, int64_t T, const ModelArgs &a, Run run, Out out,
+              const Options *snapshot = nullptr)
 {
     int rc;
     if ((rc = need_device())) return rc;
-    const Options opt = options_get();
+    const Options opt = snapshot ? *snapshot : options_get();   // a chunked decode passes the one it took on entry
     last_escalations() = 0;
     std::unique_ptr<HostSlot> slot = take_slot(T, a, opt);
     if (!slot) slot = new_slot(T, opt);
@@ -240,7 +244,8 @@ int host_call(const Entry &e, const void *y, int sample_type, int64_t T, const M
     return HMMSORT_OK;
 }
 
-int viterbi_host(const void *y, int sample_type, int64_t T, const ModelArgs &a, int16_t *x_out, double *ll_out)
+int viterbi_host(const void *y, int sample_type, int64_t T, const ModelArgs &a, int16_t *x_out, double *ll_out,
+                 const Options *snapshot = nullptr)
 {
     HS_CHECK(y && x_out && ll_out, HMMSORT_EINVAL, "viterbi: null argument");
     HS_CHECK(T >= 1, HMMSORT_EINVAL, "viterbi: empty signal (T = %lld)", (long long)T);
@@ -256,7 +261,385 @@ int viterbi_host(const void *y, int sample_type, int64_t T, const ModelArgs &a, 
             HS_HIP(hipMemcpyAsync(ll_out, h.dll.p, sizeof(double), hipMemcpyDeviceToHost, h.st));
             HS_HIP(hipStreamSynchronize(h.st));
             return HMMSORT_OK;
-        });
+        },
+        snapshot);
+}
+
+// ---- chunked decode (fit.jl:11-42) ---------------------------------------------------------------
+// One recording channel's walk through its chunks.  The signal and the stitched path stay in device memory; a
+// chunk is decode (the chunk length's plan) + stitch (chunk_stitch.hip) + a 24-byte copy into pinned memory, all
+// enqueued on the channel's stream by enqueue(); finish() waits for the stream once, reads the plan's
+// diagnostics, the trim points and the chunk's log-likelihood, and advances.  Several channels are driven in step
+// by fit_worker() below: all enqueue, then all finish.
+// The chunk's log-likelihood is the reference's to the last bit (fit.jl:37 adds the chunks' values and the sum is
+// compared with ==): the strict engine's own value, or, where a time-parallel engine or the ladder decoded the
+// chunk -- they sum ll in parts, 1e-9 relative -- k_chunk_ll's serial fold along the decoded path.
+bool fit_stops_call(int rc) { return rc == HMMSORT_EHIP || rc == HMMSORT_ENOMEM; }
+
+struct FitChannel {
+    const void *y;
+    const int sample_type;
+    const int64_t T, chunksize;
+    const ModelArgs a;
+    const Options &opt;
+    int16_t *const ml_out;
+    double *const ll_out;
+
+    DevBuf dy, dml, dx, dsmall;   // signal (fp64), stitched path, one chunk's decode, [l, kk, chunk ll]
+    // what k_chunk_ll folds along, from the first chunk plan's HostModel (every plan of the channel holds the same
+    // model): per-state means and incoming transitions; and one chunk's path values
+    DevBuf dmean, dinptr, dinsrc, dinlp, dpv;
+    bool tables = false;
+    bool path_ready = false;      // dml holds the initial ones: only then is there a path to bring back
+    void *pin = nullptr;          // pinned copy of dsmall
+    hipStream_t st = nullptr;
+    std::map<int64_t, std::unique_ptr<HostSlot>> slots;   // chunk length -> plan
+    bool twins = false;           // duplicate templates: a ring-engine plan cannot see their near-ties
+    int64_t i = 1, j = 1, k = 0;  // fit.jl's i and j, the chunk in flight is [i, j] of k samples
+    bool lead = false, trail = false, ladder = false;
+    hmmsort_plan *plan = nullptr; // the plan of the chunk in flight
+    double ll = 0.0;
+    int64_t escalations = 0;
+    bool done = false;
+    int status = HMMSORT_OK;      // the channel's code once done
+    std::string message;
+
+    FitChannel(const void *y_, int type, int64_t T_, int64_t chunk, const ModelArgs &a_, const Options &o, int16_t *ml,
+               double *ll_)
+        : y(y_), sample_type(type), T(T_), chunksize(chunk), a(a_), opt(o), ml_out(ml), ll_out(ll_)
+    {
+    }
+    ~FitChannel()
+    {
+        for (auto &kv : slots) give_slot(std::move(kv.second), opt);
+        if (pin) (void)hipHostFree(pin);
+        if (st) (void)hipStreamDestroy(st);
+    }
+    int64_t *pin_lk() { return static_cast<int64_t *>(pin); }
+    int64_t *d_lk() { return dsmall.as<int64_t>(); }
+    double *d_ll() { return dsmall.as<double>() + 2; }
+
+    // the channel ends here with `code`; the thread's message is kept because a worker's is lost with its thread
+    int end(int code)
+    {
+        done = true;
+        status = code;
+        if (code) message = last_error();
+        return code;
+    }
+
+    // ends the channel with its own errors (returns 0); passes on what stops the call
+    int guard(int rc)
+    {
+        if (rc && !fit_stops_call(rc)) {
+            end(rc);
+            return HMMSORT_OK;
+        }
+        return rc;
+    }
+
+    int escalated(const void *yc, int64_t n, int16_t *x, double *ll_chunk)
+    {
+        int rc = viterbi_host(yc, sample_type, n, a, x, ll_chunk, &opt);
+        escalations += std::max<int64_t>(last_escalations(), 0);
+        return rc;
+    }
+
+    // uploads the signal, sets the path to ones; a whole-recording decode (chunksize <= 0) is finished here
+    int open()
+    {
+        // fit.jl:6-9; one chunk that holds the recording (more than one sample of it) is the same decode
+        if (chunksize <= 0 || (chunksize >= T && T > 1)) {
+            int rc = escalated(y, T, ml_out, ll_out);
+            return rc ? guard(rc) : end(HMMSORT_OK);
+        }
+        if (T == 1) {           // `while j < n` is never entered
+            ml_out[0] = 1;
+            *ll_out = 0.0;
+            return end(HMMSORT_OK);
+        }
+        for (int64_t p = 0; p < a.N && !twins; p++)
+            for (int64_t q = p + 1; q < a.N && !twins; q++)
+                twins = std::equal(a.mu + a.K * p, a.mu + a.K * (p + 1), a.mu + a.K * q);
+        int rc;
+        HS_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        HS_HIP(hipHostMalloc(&pin, 3 * sizeof(int64_t), hipHostMallocDefault));
+        if ((rc = dy.alloc(T * sizeof(double))) || (rc = dml.alloc(T * sizeof(int16_t))) ||
+            (rc = dx.alloc(std::min(chunksize, T) * sizeof(int16_t))) || (rc = dsmall.alloc(3 * sizeof(int64_t))))
+            return rc;
+        if ((rc = dpv.alloc(std::min(chunksize, T) * sizeof(double)))) return rc;
+        if (sample_type == HMMSORT_SAMPLES_F64) {
+            HS_HIP(hipMemcpyAsync(dy.p, y, T * sizeof(double), hipMemcpyHostToDevice, st));
+        } else {
+            // raw samples cross as they are; the path's buffer holds them until they are widened
+            HS_HIP(hipMemcpyAsync(dml.p, y, T * sizeof(int16_t), hipMemcpyHostToDevice, st));
+            if ((rc = dev_widen(dml.p, sample_type, T, 1, dy.as<double>(), st))) return rc;
+        }
+        if ((rc = dev_fill_i16(dml.as<int16_t>(), T, 1, st))) return rc;   // fit.jl:15
+        path_ready = true;
+        return HMMSORT_OK;
+    }
+
+    // the plan's model tables to the device, once per channel (the plan and its model outlive the copies: the slot
+    // stays with the channel)
+    int upload_tables(const HostModel &m)
+    {
+        int rc;
+        if ((rc = dmean.alloc(m.mean.size() * sizeof(double))) || (rc = dinptr.alloc(m.in_ptr.size() * sizeof(int32_t))) ||
+            (rc = dinsrc.alloc(m.in_src.size() * sizeof(int32_t))) || (rc = dinlp.alloc(m.in_lp.size() * sizeof(double))))
+            return rc;
+        HS_HIP(hipMemcpyAsync(dmean.p, m.mean.data(), m.mean.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        HS_HIP(hipMemcpyAsync(dinptr.p, m.in_ptr.data(), m.in_ptr.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        HS_HIP(hipMemcpyAsync(dinsrc.p, m.in_src.data(), m.in_src.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        HS_HIP(hipMemcpyAsync(dinlp.p, m.in_lp.data(), m.in_lp.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        tables = true;
+        return HMMSORT_OK;
+    }
+
+    int plan_for(int64_t n, hmmsort_plan **out)
+    {
+        std::unique_ptr<HostSlot> &slot = slots[n];
+        if (!slot) {
+            slot = take_slot(n, a, opt);
+            if (!slot) slot = new_slot(n, opt);
+            if (slot->plan && hmmsort_plan_set_model(slot->plan, a.tr, a.R, a.mu, a.sigma)) slot->drop_plan();
+        }
+        if (!slot->plan) {
+            int rc = plan_create_engine(&slot->plan, n, a.states, a.N, a.K, a.S, a.tr, a.R, a.mu, a.sigma, opt.engine);
+            if (rc) return rc;
+        }
+        *out = slot->plan;
+        return HMMSORT_OK;
+    }
+
+    // d_ll = the ll of the chunk in dx, rounded as the reference rounds it
+    int exact_ll()
+    {
+        return dev_chunk_ll(dy.as<double>() + (i - 1), dx.as<int16_t>(), k, a.S, dmean.as<double>(), dinptr.as<int32_t>(),
+                            dinsrc.as<int32_t>(), dinlp.as<double>(), a.sigma, dpv.as<double>(), d_ll(), st);
+    }
+
+    int stitch() { return dev_chunk_stitch(dx.as<int16_t>(), k, lead, trail, dml.as<int16_t>() + (i - 1), d_lk(), st); }
+
+    int enqueue_chunk()
+    {
+        j = std::min(i + chunksize - 1, T);
+        k = j - i + 1;
+        lead = i > 1;
+        trail = j < T;
+        int rc;
+        if ((rc = plan_for(k, &plan))) return rc;
+        if (!tables && (rc = upload_tables(plan->model))) return rc;
+        // the lane-per-chain ring engine has no near-tie detector: with twin templates the ladder decodes
+        ladder = twins && plan->eng->id == HMMSORT_ENGINE_RING;
+        if (ladder) return HMMSORT_OK;
+        if ((rc = plan->eng->viterbi(dy.as<double>() + (i - 1), dx.as<int16_t>(), d_ll(), st))) return rc;
+        if (plan->eng->id != HMMSORT_ENGINE_STRICT && (rc = exact_ll())) return rc;
+        if ((rc = stitch())) return rc;
+        HS_HIP(hipMemcpyAsync(pin, dsmall.p, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        return HMMSORT_OK;
+    }
+
+    // the chunk again through hmmsort_viterbi's ladder, from the caller's host buffer, stitched like any other
+    int ladder_chunk(bool stitched_before, double *ll_chunk)
+    {
+        std::vector<int16_t> x(k);
+        double ll_ladder = 0.0;   // of whichever engine the ladder ended on: replaced by the fold along its path
+        const char *yc = static_cast<const char *>(y) +
+                         (i - 1) * (sample_type == HMMSORT_SAMPLES_F64 ? sizeof(double) : sizeof(int16_t));
+        int rc;
+        if ((rc = escalated(yc, k, x.data(), &ll_ladder))) return rc;
+        // what the first stitch wrote lies inside the chunk, where the path still held its initial ones
+        if (stitched_before && (rc = dev_fill_i16(dml.as<int16_t>() + (i - 1), k, 1, st))) return rc;
+        HS_HIP(hipMemcpyAsync(dx.p, x.data(), k * sizeof(int16_t), hipMemcpyHostToDevice, st));
+        if ((rc = exact_ll()) || (rc = stitch())) return rc;
+        HS_HIP(hipMemcpyAsync(pin, dsmall.p, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        HS_HIP(hipStreamSynchronize(st));
+        memcpy(ll_chunk, pin_lk() + 2, sizeof(double));
+        return HMMSORT_OK;
+    }
+
+    int finish_chunk()
+    {
+        int rc;
+        double ll_chunk = 0.0;
+        bool again = ladder;
+        if (!ladder) {
+            HS_HIP(hipStreamSynchronize(st));   // the one wait of this chunk
+            Engine &eng = *plan->eng;
+            if (eng.id != HMMSORT_ENGINE_STRICT && opt.escalate) {
+                int64_t diag[8] = {0};
+                if ((rc = eng.diagnostics(st, diag))) return rc;
+                again = diag[0] != 0 ||
+                        ((eng.id == HMMSORT_ENGINE_BLOCKED || eng.id == HMMSORT_ENGINE_WAVE) && diag[7] != 0);
+            }
+            memcpy(&ll_chunk, pin_lk() + 2, sizeof(double));
+        }
+        if (again && (rc = ladder_chunk(!ladder, &ll_chunk))) return rc;
+        const int64_t l = pin_lk()[0], kk = pin_lk()[1];
+        if (l > k) {
+            set_error("fit_chunked: the chunk at sample %lld (%lld samples) holds no silent sample: its leading trim "
+                      "runs off the chunk (fit.jl:26, BoundsError in the reference)", (long long)i, (long long)k);
+            return end(HMMSORT_ENOSILENT);
+        }
+        ll += ll_chunk;
+        j = i + kk - 1;
+        if (j <= i) {
+            set_error("fit_chunked: the chunk at sample %lld (%lld samples) has no silent sample after its first: "
+                      "the next chunk would not advance (fit.jl:41, the reference loops forever)", (long long)i,
+                      (long long)k);
+            return end(HMMSORT_ENOSILENT);
+        }
+        i = j;
+        if (!(j < T)) end(HMMSORT_OK);
+        return HMMSORT_OK;
+    }
+
+    // the path and the sum as they stand, complete or not
+    int collect()
+    {
+        if (!st || !path_ready) return HMMSORT_OK;   // finished in open(), or ended there before there was a path
+        HS_HIP(hipMemcpyAsync(ml_out, dml.p, T * sizeof(int16_t), hipMemcpyDeviceToHost, st));
+        HS_HIP(hipStreamSynchronize(st));
+        *ll_out = ll;
+        return HMMSORT_OK;
+    }
+};
+
+struct FitJob {
+    int64_t C, T, chunksize;
+    const void *const *y;
+    int sample_type;
+    const hmmsort_model *models;
+    int16_t *const *ml_out;
+    double *ll_out;
+    Options opt;
+    std::vector<int> status;
+    std::vector<std::string> message;
+    std::atomic<bool> stop{false};
+    std::atomic<int64_t> escalations{0};
+};
+
+// channels first, first + stride, ... of the job on the current device of the calling thread
+int fit_worker(FitJob &job, int64_t first, int64_t stride)
+{
+    std::vector<std::unique_ptr<FitChannel>> live;   // their position in `live` is their turn
+    std::vector<int64_t> which;
+    int64_t next = first;
+    int fatal = HMMSORT_OK;
+    auto retire = [&](size_t at) {
+        FitChannel &ch = *live[at];
+        int rc = ch.collect();
+        job.status[which[at]] = rc ? rc : ch.status;
+        job.message[which[at]] = rc ? std::string(last_error()) : ch.message;
+        job.escalations += ch.escalations;
+        live.erase(live.begin() + at);   // signal and path buffers go before the next channel is taken
+        which.erase(which.begin() + at);
+        return rc;
+    };
+    while (!fatal && !job.stop && (next < job.C || !live.empty())) {
+        while (!fatal && next < job.C && (int64_t)live.size() < job.opt.fit_streams) {
+            const hmmsort_model &m = job.models[next];
+            live.emplace_back(new FitChannel(job.y[next], job.sample_type, job.T, job.chunksize,
+                                             {m.states, m.N, m.K, m.S, m.tr, m.R, m.mu, m.sigma}, job.opt,
+                                             job.ml_out[next], &job.ll_out[next]));
+            which.push_back(next);
+            next += stride;
+            fatal = live.back()->guard(live.back()->open());
+            if (!fatal && live.back()->done) fatal = retire(live.size() - 1);
+        }
+        for (size_t n = 0; n < live.size() && !fatal; n++) fatal = live[n]->guard(live[n]->enqueue_chunk());
+        for (size_t n = 0; n < live.size() && !fatal; n++)
+            if (!live[n]->done) fatal = live[n]->guard(live[n]->finish_chunk());
+        for (size_t n = live.size(); n-- > 0 && !fatal;)
+            if (live[n]->done) fatal = retire(n);
+    }
+    if (fatal) {
+        job.stop = true;
+        // work of the other channels may still be in flight on their streams: wait before their buffers go
+        for (auto &ch : live)
+            if (ch->st) (void)hipStreamSynchronize(ch->st);
+        (void)hipGetLastError();
+    }
+    return fatal;
+}
+
+int fit_channels_host(int64_t C, const void *const *y, int sample_type, int64_t T, int64_t chunksize,
+                      const hmmsort_model *models, const int *devices, int64_t ndev, int16_t *const *ml_out,
+                      double *ll_out, int *status_out, bool prefix)
+{
+    HS_CHECK(C >= 1 && y && models && ml_out && ll_out, HMMSORT_EINVAL, "fit_channels: null argument or no channel");
+    HS_CHECK(T >= 1, HMMSORT_EINVAL, "fit_channels: empty signal (T = %lld)", (long long)T);
+    HS_CHECK(sample_type == HMMSORT_SAMPLES_F64 || sample_type == HMMSORT_SAMPLES_I16, HMMSORT_EINVAL,
+             "fit_channels: samples must be HMMSORT_SAMPLES_F64 or HMMSORT_SAMPLES_I16");
+    for (int64_t c = 0; c < C; c++)
+        HS_CHECK(y[c] && ml_out[c] && models[c].states && models[c].tr && models[c].mu, HMMSORT_EINVAL,
+                 "fit_channels: null pointer in channel %lld", (long long)c);
+    int rc;
+    if ((rc = need_device())) return rc;
+    if (!devices) ndev = 0;
+    HS_CHECK(ndev >= 0 && ndev <= 64, HMMSORT_EINVAL, "fit_channels: device list of %lld entries", (long long)ndev);
+    int count = 0;
+    HS_HIP(hipGetDeviceCount(&count));
+    for (int64_t d = 0; d < ndev; d++)
+        HS_CHECK(devices[d] >= 0 && devices[d] < count, HMMSORT_EINVAL, "fit_channels: no device %d", devices[d]);
+    FitJob job;
+    job.C = C, job.T = T, job.chunksize = chunksize, job.y = y, job.sample_type = sample_type, job.models = models;
+    job.ml_out = ml_out, job.ll_out = ll_out;
+    job.opt = options_get();
+    job.status.assign(C, HMMSORT_EHIP);
+    job.message.assign(C, "fit_channels: the call stopped before this channel was decoded");
+    last_escalations() = 0;
+    int fatal = HMMSORT_OK;
+    std::string fatal_message;
+    if (ndev == 0) {
+        fatal = fit_worker(job, 0, 1);
+        if (fatal) fatal_message = last_error();
+    } else {
+        // hipSetDevice is per host thread: the workers leave the caller's current device alone
+        std::vector<int> rcs(ndev, HMMSORT_OK);
+        std::vector<std::string> msgs(ndev);
+        std::vector<std::thread> workers;
+        for (int64_t p = 0; p < ndev; p++)
+            workers.emplace_back([&, p] {
+                if (hipSetDevice(devices[p]) != hipSuccess) {
+                    (void)hipGetLastError();
+                    set_error("fit_channels: hipSetDevice(%d) failed", devices[p]);
+                    rcs[p] = HMMSORT_EHIP;
+                    job.stop = true;
+                } else {
+                    rcs[p] = fit_worker(job, p, ndev);
+                }
+                if (rcs[p]) msgs[p] = last_error();
+            });
+        for (auto &w : workers) w.join();
+        for (int64_t p = ndev; p-- > 0;)
+            if (rcs[p]) fatal = rcs[p], fatal_message = msgs[p];
+    }
+    last_escalations() = job.escalations;
+    if (status_out)
+        for (int64_t c = 0; c < C; c++) status_out[c] = job.status[c];
+    if (fatal) {
+        set_error("%s", fatal_message.c_str());
+        return fatal;
+    }
+    for (int64_t c = 0; c < C; c++)
+        if (job.status[c]) {
+            if (prefix)
+                set_error("channel %lld: %s", (long long)c, job.message[c].c_str());
+            else
+                set_error("%s", job.message[c].c_str());
+            return job.status[c];
+        }
+    return HMMSORT_OK;
+}
+
+int fit_chunked_host(const void *y, int sample_type, int64_t T, int64_t chunksize, const ModelArgs &a,
+                     int16_t *ml_out, double *ll_out)
+{
+    HS_CHECK(y && ml_out && ll_out, HMMSORT_EINVAL, "fit_chunked: null argument");
+    const hmmsort_model m = {a.states, a.N, a.K, a.S, a.tr, a.R, a.mu, a.sigma};
+    return fit_channels_host(1, &y, sample_type, T, chunksize, &m, nullptr, 0, &ml_out, ll_out, nullptr, false);
 }
 
 int fwd_bwd_host(bool fwd, const double *y, int64_t T, const ModelArgs &a, double *out)
@@ -324,6 +707,30 @@ int hmmsort_viterbi_i16(const int16_t *y, int64_t T, const int16_t *states, int6
                         int16_t *x_out, double *ll_out)
 {
     return viterbi_host(y, HMMSORT_SAMPLES_I16, T, {states, N, K, S, tr, R, mu, sigma}, x_out, ll_out);
+}
+
+int hmmsort_fit_chunked(const double *y, int64_t T, int64_t chunksize, const int16_t *states, int64_t N,
+                        int64_t K, int64_t S, const hmm_trans *tr, int64_t R, const double *mu, double sigma,
+                        int16_t *ml_seq_out, double *ll_out)
+{
+    return fit_chunked_host(y, HMMSORT_SAMPLES_F64, T, chunksize, {states, N, K, S, tr, R, mu, sigma}, ml_seq_out,
+                            ll_out);
+}
+
+int hmmsort_fit_chunked_i16(const int16_t *y, int64_t T, int64_t chunksize, const int16_t *states, int64_t N,
+                            int64_t K, int64_t S, const hmm_trans *tr, int64_t R, const double *mu,
+                            double sigma, int16_t *ml_seq_out, double *ll_out)
+{
+    return fit_chunked_host(y, HMMSORT_SAMPLES_I16, T, chunksize, {states, N, K, S, tr, R, mu, sigma}, ml_seq_out,
+                            ll_out);
+}
+
+int hmmsort_fit_channels(int64_t C, const void *const *y, int sample_type, int64_t T, int64_t chunksize,
+                         const hmmsort_model *models, const int *devices, int64_t ndev,
+                         int16_t *const *ml_seq_out, double *ll_out, int *status_out)
+{
+    return fit_channels_host(C, y, sample_type, T, chunksize, models, devices, ndev, ml_seq_out, ll_out, status_out,
+                             true);
 }
 
 int hmmsort_forward(const double *y, int64_t T, const int16_t *states, int64_t N, int64_t K,

@@ -42,6 +42,7 @@ extern "C" {
 #define HMMSORT_EHIP (-3)    /* HIP runtime error (includes: no device) */
 #define HMMSORT_ENOCONV (-4) /* time-parallel engine could not certify its block boundaries */
 #define HMMSORT_EUNSUP (-5)  /* model shape not supported by the requested engine */
+#define HMMSORT_ENOSILENT (-6) /* chunked decode: a chunk held no silent sample where the stitch rule needs one */
 
 /* Julia Tuple{Int64,Int64,Float64}  (types.jl:3) */
 typedef struct hmm_trans {
@@ -78,7 +79,10 @@ int hmmsort_set_device(int device);
  *       "last_escalations" (retries of the calling thread's last host-buffer call; NEGATIVE = minus the
  *       number of near-tie decisions on a time-parallel path that was returned because the strict sweep's
  *       S x T back-pointers do not fit: the path can differ from the reference's at those decisions only,
- *       whose margins are inside the reference's own rounding noise; hmmsort_last_error has the text).
+ *       whose margins are inside the reference's own rounding noise; hmmsort_last_error has the text;
+ *       after a chunked decode: the retries summed over all chunks and channels), "fit_streams" (channels one
+ *       worker of hmmsort_fit_channels keeps in flight, each on a stream of its own: default 4, the runtime's
+ *       default number of hardware queues; 1..16, HMMSORT_EINVAL outside).
  * Process-wide defaults behind a mutex; an entry point works on the snapshot it takes when it starts,
  * so options may be changed while other host threads are inside the library.  hmmsort_last_error is
  * per thread. */
@@ -117,6 +121,67 @@ int hmmsort_viterbi(const double *y, int64_t T, const int16_t *states, int64_t N
 int hmmsort_viterbi_i16(const int16_t *y, int64_t T, const int16_t *states, int64_t N, int64_t K,
                         int64_t S, const hmm_trans *tr, int64_t R, const double *mu, double sigma,
                         int16_t *x_out, double *ll_out);
+
+/* ---- chunked decode: fit(HMMSpikingModel, templates, X, chunksize)   fit.jl:11-42, hmmsort.jl:90 ------------
+ * The recording is decoded in chunks of `chunksize` samples that depend on each other: the leading non-silent
+ * samples of a chunk are skipped (fit.jl:24-28), its trailing ones are left to the next chunk, which starts at
+ * the chunk's last silent sample (fit.jl:30-36, :41).  ml_seq starts as all ones; ll is the sum of the chunks'
+ * log-likelihoods, added on the host in chunk order; a chunk's value is rounded as the reference rounds it
+ * (viterbi.jl:92-96 folded serially along the decoded path on the device), so the sum equals the reference's to
+ * the last bit.  The fold is serial (about 3 dependent additions per sample by one thread): measured 3.2 ms per
+ * 100 000-sample chunk beside a decode of about 0.8 ms, so one channel runs at 0.20 x the rate of the host loop
+ * api.fit, which keeps the engines' own ll (1e-9 relative); channels in step hide part of it.  chunksize <= 0, or one chunk that holds the recording (chunksize >= T > 1): the whole recording
+ * in one decode (fit.jl:6-9), exactly hmmsort_viterbi, whose ll keeps 1e-9 relative on the time-parallel engines.
+ * T == 1 with chunksize > 0 never enters the loop: ml_seq = [1], ll = 0.
+ * The signal is uploaded once (int16 samples as they are, widened in device memory), the stitched path stays in
+ * device memory and comes back once; per chunk the host waits once for the chunk's work, reads the chunk's
+ * log-likelihood and the two trim points from a pinned record, and then the plan's diagnostics (the engine's own
+ * small copies on the idle stream).  Chunk plans (one per chunk length) are made under the options
+ * in force and come from / go back to the cache of the host-buffer entry points.  A chunk whose plan reports a
+ * failed boundary certificate or open near-ties is decoded again by hmmsort_viterbi's escalation ladder (option
+ * "escalate"), as is every chunk of a model with duplicate templates on HMMSORT_ENGINE_RING (no near-tie
+ * detector); "last_escalations" is the sum of those retries.
+ * Where the reference dies the call returns HMMSORT_ENOSILENT, hmmsort_last_error names the place and the 1-based
+ * first sample i of the chunk, and ml_seq_out / ll_out hold what the loop had at that moment:
+ *   - fit.jl:26, a chunk that is not the first has no silent sample (BoundsError in the reference): found before
+ *     the chunk is written or its log-likelihood added;
+ *   - fit.jl:41, a chunk's last silent sample is its first one (or it has none), so the next chunk would not
+ *     advance (the reference loops forever): found after the chunk is written and its log-likelihood added.
+ * Out of scope here: a channels form of hmmsort_em_step, any collective between devices, spike extraction from
+ * the resident path, speculative decoding of dependent chunks. */
+int hmmsort_fit_chunked(const double *y, int64_t T, int64_t chunksize, const int16_t *states, int64_t N,
+                        int64_t K, int64_t S, const hmm_trans *tr, int64_t R, const double *mu, double sigma,
+                        int16_t *ml_seq_out, double *ll_out);
+int hmmsort_fit_chunked_i16(const int16_t *y, int64_t T, int64_t chunksize, const int16_t *states, int64_t N,
+                            int64_t K, int64_t S, const hmm_trans *tr, int64_t R, const double *mu,
+                            double sigma, int16_t *ml_seq_out, double *ll_out);
+
+/* the model arguments of hmmsort_viterbi, one record per channel */
+typedef struct hmmsort_model {
+    const int16_t *states;
+    int64_t N, K, S;
+    const hmm_trans *tr;
+    int64_t R;
+    const double *mu;
+    double sigma;
+} hmmsort_model;
+
+/* The chunked decode of C recording channels of T samples, each with its own model (the reference sorts one
+ * channel per call with that channel's templates, hmmsort.jl:79-83; N, K and S may differ between channels).
+ * y[c] / ml_seq_out[c]: per-channel host pointers; sample_type HMMSORT_SAMPLES_F64 or HMMSORT_SAMPLES_I16;
+ * ll_out: C doubles; status_out: C codes or NULL.  devices == NULL or ndev == 0: everything on the current
+ * device, on the calling thread.  Otherwise channel c runs on devices[c % ndev], one worker thread per list
+ * position (a device listed twice gets two workers).  The chunks of one channel depend on each other, those of
+ * different channels do not: a worker keeps up to option "fit_streams" of its channels in flight, enqueues
+ * decode + stitch of each on the channel's own stream, then waits for each, reads and advances.  Options are
+ * read once, by the calling thread.  A channel that ends in HMMSORT_ENOSILENT (or another error of its own
+ * model) does not stop the others; a HIP or allocation error stops the call.  Returns HMMSORT_OK when every
+ * channel is, else the code of the lowest failing channel, whose message goes to the caller's
+ * hmmsort_last_error prefixed "channel c:" (0-based).  Each channel's result is what hmmsort_fit_chunked gives
+ * for it.  The caller's current device is unchanged. */
+int hmmsort_fit_channels(int64_t C, const void *const *y, int sample_type, int64_t T, int64_t chunksize,
+                         const hmmsort_model *models, const int *devices, int64_t ndev,
+                         int16_t *const *ml_seq_out, double *ll_out, int *status_out);
 
 /* forward(V, lA::StateMatrix, mu, sigma) -> alpha (S x T)            baumwelch.jl:25-51 */
 int hmmsort_forward(const double *y, int64_t T, const int16_t *states, int64_t N, int64_t K,
@@ -350,6 +415,16 @@ int hmmsort_posteriors(const double *y, int64_t T, const int16_t *states, int64_
 #define HMMSORT_SAMPLES_F64 3
 int hmmsort_samples_to_f64(const void *d_in, int sample_type, int64_t T, int64_t stride, double *d_out,
                            void *stream);
+
+/* fit.jl:24-36 on a decoded chunk in device memory.  d_x: the chunk's k states (1 = silent), 1 <= k <= 2^31 - 1.
+ * lead  != 0 (the chunk is not the recording's first, fit.jl:24):  l  = 1 + number of leading samples with x > 1,
+ *            l = k + 1 when no sample is silent;        lead  == 0: l  = 1.
+ * trail != 0 (the chunk does not end the recording, fit.jl:30): kk = 1-based index of the last silent sample,
+ *            0 when there is none;                      trail == 0: kk = k.
+ * Copies d_x[l-1 .. kk-1] to d_dst[l-1 .. kk-1] (d_dst = where the chunk's first sample belongs in ml_seq);
+ * copies nothing when l > kk.  d_lk[0] = l, d_lk[1] = kk (device int64[2]).  Asynchronous on `stream`. */
+int hmmsort_chunk_stitch(const int16_t *d_x, int64_t k, int lead, int trail, int16_t *d_dst, int64_t *d_lk,
+                         void *stream);
 
 /* Per-kernel timing of the ring engine with HIP events recorded on the caller's stream (used by
  * bench.py for the roofline line).  hmmsort_plan_profile(plan, 1) switches bracketing on;

@@ -6,14 +6,14 @@
 #
 # Usage:   using HMMSpikeSorter; include("HMMSpikeSorterHIP.jl"); HMMSpikeSorterHIP.enable!()
 # After enable!(), HMMSpikeSorter.viterbi / forward / backward / update /
-# train_model(X, sm, mu, sigma) / reconstruct_signal keep their signatures and return values
-# (reference src/viterbi.jl:44, src/baumwelch.jl:25,73,205,362, src/reconstruction.jl:1) but run on
-# the GPU.  Julia arrays are passed as they are: Matrix{Int16} states, Vector{Tuple{Int64,Int64,
+# train_model(X, sm, mu, sigma) / reconstruct_signal / fit(HMMSpikingModel, templates, X, chunksize) keep their
+# signatures and return values (reference src/viterbi.jl:44, src/baumwelch.jl:25,73,205,362,
+# src/reconstruction.jl:1, src/fit.jl:11) but run on the GPU.  Julia arrays are passed as they are: Matrix{Int16} states, Vector{Tuple{Int64,Int64,
 # Float64}} transitions (24-byte isbits records), column-major Float64 matrices.
 module HMMSpikeSorterHIP
 
 using HMMSpikeSorter
-import HMMSpikeSorter: StateMatrix
+import HMMSpikeSorter: StateMatrix, HMMSpikeTemplateModel, HMMSpikingModel
 
 const lib = get(ENV, "HMMSORT_LIB", "libhmmsort_hip.so")
 
@@ -40,6 +40,61 @@ function viterbi(y::AbstractArray{Int16,1}, lA::StateMatrix, μ::Array{Float64,2
          Ptr{Int16}, Ref{Float64}),
         yv, length(yv), lA.states, lA.N, lA.K, lA.nstates, lA.transitions, length(lA.transitions), μ, σ, x, ll))
     x, ll[]
+end
+
+# fit(HMMSpikingModel, templates, X, chunksize) (fit.jl:11-42, the CLI's call hmmsort.jl:90): the chunk loop, the
+# stitch and the path stay on the device behind one call; the signal goes up once.  Where the reference dies on a
+# chunk without a silent sample (BoundsError at fit.jl:26, endless loop at :41) this raises (HMMSORT_ENOSILENT).
+function fit_chunked(templates::HMMSpikeTemplateModel, X::AbstractVector{T}, chunksize::Integer) where T <: Union{Float64,Int16}
+    Xv = X isa Array ? X : collect(X)
+    lA = templates.state_matrix
+    ml_seq = zeros(Int16, length(Xv)); ll = Ref{Float64}(0.0)
+    sym = T === Int16 ? :hmmsort_fit_chunked_i16 : :hmmsort_fit_chunked
+    check(ccall((sym, lib), Cint,
+        (Ptr{T}, Int64, Int64, Ptr{Int16}, Int64, Int64, Int64, Ptr{Cvoid}, Int64, Ptr{Float64}, Float64,
+         Ptr{Int16}, Ref{Float64}),
+        Xv, length(Xv), chunksize, lA.states, lA.N, lA.K, lA.nstates, lA.transitions, length(lA.transitions),
+        templates.μ, templates.σ, ml_seq, ll))
+    HMMSpikingModel(templates, ml_seq, ll[], X)
+end
+
+# sample types of hmmsort_fit_channels (include/hmmsort.h)
+const HMMSORT_SAMPLES_I16 = Cint(0)
+const HMMSORT_SAMPLES_F64 = Cint(3)
+
+# struct hmmsort_model (include/hmmsort.h): the model arguments of viterbi, one record per channel
+struct CModel
+    states::Ptr{Int16}; N::Int64; K::Int64; S::Int64
+    tr::Ptr{Cvoid}; R::Int64; mu::Ptr{Float64}; sigma::Float64
+end
+
+"""
+    fit_channels(templates, X, chunksize; devices=Int[]) -> Vector{HMMSpikingModel}
+
+The chunked decode of several recording channels in one call (`hmmsort_fit_channels`): `templates[c]` and `X[c]`
+(all of one length, all `Float64` or all `Int16`) belong to channel `c`; `chunksize <= 0` decodes every channel
+whole.  Channel `c` runs on `devices[c % length(devices) + 1]` (0-based device numbers; empty: the current
+device), channels on one device in step on streams of their own (option "fit_streams").  An extension: the
+reference sorts one channel per process (hmmsort.jl:79-90).
+"""
+function fit_channels(templates::Vector{HMMSpikeTemplateModel}, X::Vector{Vector{T}}, chunksize::Integer;
+                      devices::Vector{<:Integer}=Int[]) where T <: Union{Float64,Int16}
+    C = length(X); n = length(X[1])
+    length(templates) == C && all(length(x) == n for x in X) || error("fit_channels: one model per channel, equal lengths")
+    ml = [zeros(Int16, n) for _ in 1:C]; ll = zeros(Float64, C); status = zeros(Cint, C)
+    dev = Cint.(devices)
+    GC.@preserve templates X ml dev begin
+        models = [CModel(pointer(t.state_matrix.states), t.state_matrix.N, t.state_matrix.K, t.state_matrix.nstates,
+                         Ptr{Cvoid}(pointer(t.state_matrix.transitions)), length(t.state_matrix.transitions),
+                         pointer(t.μ), t.σ) for t in templates]
+        ys = [Ptr{Cvoid}(pointer(x)) for x in X]; outs = [pointer(m) for m in ml]
+        check(ccall((:hmmsort_fit_channels, lib), Cint,
+            (Int64, Ptr{Ptr{Cvoid}}, Cint, Int64, Int64, Ptr{CModel}, Ptr{Cint}, Int64, Ptr{Ptr{Int16}}, Ptr{Float64},
+             Ptr{Cint}),
+            C, ys, T === Int16 ? HMMSORT_SAMPLES_I16 : HMMSORT_SAMPLES_F64, n, chunksize, models, isempty(dev) ? Ptr{Cint}(C_NULL) : pointer(dev),
+            length(dev), outs, ll, status))
+    end
+    [HMMSpikingModel(templates[c], ml[c], ll[c], X[c]) for c in 1:C]
 end
 
 function _fb(sym, V, lA, μ, σ)
@@ -128,6 +183,7 @@ function enable!()
         update(α::Array{Float64,2}, β::Array{Float64,2}, lA::StateMatrix, μ::Array{Float64,2}, σ::Float64, x::Array{Float64,1}) = $(update)(α, β, lA, μ, σ, x)
         train_model(X::Array{Float64,1}, sm::StateMatrix, μ0::Array{Float64,2}, σ0::Float64; verbose=0) = $(train_model)(X, sm, μ0, σ0; verbose=verbose)
         reconstruct_signal(x::Array{T,1}, lA::StateMatrix, μ::Array{Float64,2}, σ::Float64) where T <: Integer = $(reconstruct_signal)(x, lA, μ, σ)
+        StatsBase.fit(::Type{HMMSpikingModel}, templates::HMMSpikeTemplateModel, X::AbstractVector{Float64}, chunksize::Integer, callback::Function=x->nothing) = $(fit_chunked)(templates, X, chunksize)
     end
     atexit(shutdown)
     nothing
