@@ -47,6 +47,7 @@ struct WaveGeom {
     int first, last;
     double thr_scale;        // test aid: multiplier of the near-tie threshold (option "tie_scale")
     int tie_debug;           // test aids (option "tie_debug"): 1 exact prefix folded to the end, 2 resolver off (flagged = unresolved)
+    int backtrace;           // option "backtrace": 0 auto (light form beside an E-step, register rows alone), 1 register rows, 2 light
 };
 
 // per-channel model constants (device table, wave-uniform scalar loads)
@@ -92,7 +93,7 @@ struct WaveDev {
     double *vpre = nullptr, *vend = nullptr;   // C*nch x (1 + N*L) Viterbi boundary states
     int32_t *vfail = nullptr;         // C*nch
     int32_t *bstate = nullptr;        // C*nseg
-    int32_t *redo = nullptr;          // stitch list
+    int32_t *redo = nullptr;          // 2 x C*nseg: the stitch lists of the first and the second check
     int32_t *final_state = nullptr;   // C
     double *part = nullptr;           // reduction partials (ll)
     double *FA0 = nullptr;            // C x T   log alpha(silent)
@@ -107,7 +108,13 @@ struct WaveDev {
     double *yhead = nullptr;          // C x (N*L + 2): Yn_a(t), t < L (logs) | lb0(0) | z0
     double *extra = nullptr;          // C x 3*N*L
     double *pp = nullptr;             // C x S
+    // what a call zeroes with ONE memset at its start, one allocation: diag[8] | tie_cnt[C x 8] | heads[4] (int32).
+    // A decode zeroes all of it (wave_zero_bytes(r, true)), an E-step or posterior call only diag, so that the tie
+    // counters of the last decode stay readable (hmmsort_plan_tie_stats)
     int64_t *diag = nullptr;          // 8
+    int32_t *heads = nullptr;         // list lengths: [0], [1] chains to sweep again after certificate rounds 0 and 1 (vlist),
+                                      // [2], [3] segments queued by the first / second stitch check (redo)
+    int32_t *vlist = nullptr;         // 2 x C*nch chains to sweep again, one list per round
     double *trash = nullptr;          // 64 x 64 doubles: where idle lanes of a partial super-step store (branch-free stores)
     double *dbg = nullptr;            // 64 doubles: debug record of the first failing certificate
     // posterior calls (wave_post.hip); the buffers are allocated by the first such call
@@ -118,7 +125,7 @@ struct WaveDev {
     double *plogz = nullptr;          // C       log-likelihood of the recording
     double *pcnt = nullptr;           // C*N x kPostParts partial sums of rho (expected spike counts)
     // exact near-tie resolver (wave_ties.hip)
-    int64_t *tie_cnt = nullptr;       // C x 8 counters (kTie* below)
+    int64_t *tie_cnt = nullptr;       // C x 8 counters (kTie* below); lives behind diag
     int64_t *tie_list = nullptr;      // C x kTieCap flagged decisions on the decoded path: t * 32 + entry, time order
     int64_t *tie_off = nullptr;       // C x (ntile + 1) list offsets of the tiles of 4096 samples
     int64_t tie_ntile = 0;
@@ -393,6 +400,11 @@ int wave_graphed(WaveDev *r, int kind, const void *p0, const void *p1, const voi
     return HMMSORT_OK;
 }
 
+inline size_t wave_zero_bytes(const WaveDev *r, bool decode)
+{
+    return (size_t)(decode ? 8 + 8 * (int64_t)r->g.C + 2 : 8) * sizeof(int64_t);
+}
+
 // wave_engine.hip
 int wave_create(WaveDev **out, const std::vector<HostModel> &models, int64_t T, int64_t block_req,
                 int64_t halo_req);
@@ -406,7 +418,8 @@ int wave_profile_read(WaveDev *r, hipStream_t st, std::vector<std::string> &name
                       std::vector<double> &ms, std::vector<int64_t> &calls);
 // wave_viterbi.hip
 int wave_viterbi_sweep(WaveDev *r, const double *d_y, hipStream_t st);
-int wave_viterbi_post(WaveDev *r, const double *d_y, int16_t *d_x, double *d_ll, hipStream_t st);
+// beside: the decode runs next to an E-step's sweeps (decides the backtrace form under option "backtrace" = 0)
+int wave_viterbi_post(WaveDev *r, const double *d_y, int16_t *d_x, double *d_ll, hipStream_t st, bool beside);
 int wave_viterbi(WaveDev *r, const double *d_y, int16_t *d_x, double *d_ll, hipStream_t st);
 // wave_ties.hip
 int wave_tie_resolve(WaveDev *r, const double *d_y, int16_t *d_x, hipStream_t st);

@@ -58,7 +58,8 @@ static int make_geometry(WaveGeom &g, int64_t T, int C, int N, int L, int64_t bl
 {
     g.T = T; g.C = C; g.N = N; g.L = L;
     g.own_lo = 0; g.own_hi = T; g.first = 1; g.last = 1;
-    { const Options o = options_get(); g.thr_scale = (double)o.tie_scale; g.tie_debug = (int)o.tie_debug; }
+    { const Options o = options_get(); g.thr_scale = (double)o.tie_scale; g.tie_debug = (int)o.tie_debug;
+      g.backtrace = (int)o.backtrace; }
     g.W = std::min(L, 64);
     g.RB = (int)wround_up(L + g.W, 32);
     // warm-up: four ring lengths, at least 256 samples; with chains of thousands of samples this is
@@ -244,7 +245,8 @@ int wave_create(WaveDev **out, const std::vector<HostModel> &models, int64_t T, 
     A(&r->vend, nchT * (1 + N * L));
     A(&r->vfail, nchT + 8);
     A(&r->bstate, C * g.nseg);
-    A(&r->redo, C * g.nseg + 8);
+    A(&r->redo, 2 * C * g.nseg + 8);
+    A(&r->vlist, 2 * nchT + 8);
     A(&r->final_state, C + 8);
     A(&r->part, (int64_t)C * 4 * r->nparts);
     A(&r->FA0, CT);
@@ -262,11 +264,11 @@ int wave_create(WaveDev **out, const std::vector<HostModel> &models, int64_t T, 
     A(&r->yhead, C * (N * L + 2));
     A(&r->extra, C * 3 * N * L);
     A(&r->pp, C * m.S);
-    A(&r->diag, 8);
+    A(&r->diag, 8 + 8 * (int64_t)C + 2);
+    if (ok) { r->tie_cnt = r->diag + 8; r->heads = reinterpret_cast<int32_t *>(r->diag + 8 + 8 * (int64_t)C); }
     A(&r->dbg, 64);
     A(&r->trash, 64 * 64);
     r->tie_nblk = (T + kTieBlk - 1) / kTieBlk;
-    A(&r->tie_cnt, (int64_t)C * 8);
     A(&r->tie_list, (int64_t)C * kTieCap);
     r->tie_ntile = (T + 4095) / 4096;
     A(&r->tie_off, (int64_t)C * (r->tie_ntile + 1));
@@ -293,8 +295,7 @@ int wave_create(WaveDev **out, const std::vector<HostModel> &models, int64_t T, 
         (void)hipMemset(r->partG, 0xFF, (int64_t)C * r->gparts * N * L * 8);
         (void)hipMemset(r->yhead, 0xFF, C * (N * L + 2) * 8);
     }
-    if (hipMemset(r->diag, 0, 8 * sizeof(int64_t)) != hipSuccess ||
-        hipMemset(r->tie_cnt, 0, (size_t)C * 8 * sizeof(int64_t)) != hipSuccess ||
+    if (hipMemset(r->diag, 0, wave_zero_bytes(r, true)) != hipSuccess ||
         hipMemset(r->vfail, 0, (nchT + 8) * sizeof(int32_t)) != hipSuccess) {
         wave_destroy(r);
         return HMMSORT_EHIP;
@@ -332,7 +333,7 @@ void wave_destroy(WaveDev *r)
     void *ptrs[] = {r->d_cst, r->d_mean, r->d_meanT, r->d_cint, r->d_msq, r->d_ctab, r->d_states, r->Rf, r->W2, r->virt, r->ysum,
                     r->psi, r->vpre, r->vend, r->vfail, r->bstate, r->redo, r->final_state, r->part, r->FA0,
                     r->FV, r->FREF, r->fpre, r->bpre, r->bown, r->rho, r->Zc, r->partS, r->partG, r->yhead,
-                    r->extra, r->pp, r->diag, r->dbg, r->trash, r->tie_cnt, r->tie_list, r->tie_off, r->tie_walk, r->tie_guess,
+                    r->extra, r->pp, r->diag, r->vlist, r->dbg, r->trash, r->tie_list, r->tie_off, r->tie_walk, r->tie_guess,
                     r->tie_c, r->tie_ok, r->tie_v, r->gsil, r->phead, r->plogz, r->pcnt};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);

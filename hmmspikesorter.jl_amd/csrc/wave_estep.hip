@@ -1247,7 +1247,7 @@ int wave_decode_estep(WaveDev *r, const double *d_y, int16_t *d_x, double *d_ll,
     r->post_valid = false;
     return wave_graphed(r, 3, d_y, d_x, d_ll, d_stats, st, [&](hipStream_t s) -> int {
         int rc;
-        HS_HIP(hipMemsetAsync(r->diag, 0, 8 * sizeof(int64_t), s));
+        HS_HIP(hipMemsetAsync(r->diag, 0, wave_zero_bytes(r, true), s));   // diag, the tie counters, the list heads
         if ((rc = wave_prepare(r, d_y, s))) return rc;
         HS_HIP(hipEventRecord(r->ev_fork, s));
         HS_HIP(hipStreamWaitEvent(r->side2, r->ev_fork, 0));
@@ -1255,7 +1255,7 @@ int wave_decode_estep(WaveDev *r, const double *d_y, int16_t *d_x, double *d_ll,
         // decode would otherwise hold the forward sweep back by their host-side enqueue time, ~0.1 ms)
         if ((rc = wave_estep_sweeps(r, d_y, d_stats, s))) return rc;
         if ((rc = wave_viterbi_sweep(r, d_y, r->side2))) return rc;
-        if ((rc = wave_viterbi_post(r, d_y, d_x, d_ll, r->side2))) return rc;
+        if ((rc = wave_viterbi_post(r, d_y, d_x, d_ll, r->side2, true))) return rc;
         HS_HIP(hipEventRecord(r->ev_join, r->side2));
         HS_HIP(hipStreamWaitEvent(s, r->ev_join, 0));
         return HMMSORT_OK;

@@ -144,26 +144,40 @@ __global__ __launch_bounds__(256) void kw_tie_collect(WaveGeom g, const int16_t 
     if (!WRITE && lane == 0) off[tile] = run;
 }
 
-__global__ __launch_bounds__(1024) void kw_tie_offsets(const int64_t *__restrict__ tie_cnt_in, int64_t *__restrict__ tie_cnt,
-                                                       int64_t *__restrict__ tie_off, int64_t ntile)
+// The two scans below (kw_tie_offsets, kw_tie_bscan) cut their input into 1 024 partitions; a workgroup of 256
+// threads takes four partitions per thread, each summed and rewritten in its own order, and thread 0 scans the
+// 1 024 partial values serially: the same additions in the same order as one thread per partition (the double
+// prefix comes out bit for bit), in four waves of a few dozen registers instead of sixteen on one CU.
+constexpr int kTieParts = 1024, kTieScanThreads = 256, kTiePer = kTieParts / kTieScanThreads;
+
+__global__ __launch_bounds__(kTieScanThreads) void kw_tie_offsets(int64_t *__restrict__ tie_cnt,
+                                                                  int64_t *__restrict__ tie_off, int64_t ntile)
 {
-    __shared__ int64_t part[1024];
+    __shared__ int64_t part[kTieParts];
     const int ch = blockIdx.x, tid = threadIdx.x;
-    if (tie_cnt_in[ch * 8 + kTieTrig] == 0) return;
+    if (tie_cnt[ch * 8 + kTieTrig] == 0) return;
     int64_t *off = tie_off + (int64_t)ch * (ntile + 1);
-    const int64_t per = (ntile + 1023) / 1024, lo = (int64_t)tid * per, hi = lo + per < ntile ? lo + per : ntile;
-    int64_t acc = 0;
-    for (int64_t b = lo; b < hi; b++) acc += off[b];
-    part[tid] = acc;
+    const int64_t per = (ntile + kTieParts - 1) / kTieParts;
+    for (int j = 0; j < kTiePer; j++) {
+        const int p = tid * kTiePer + j;
+        const int64_t lo = (int64_t)p * per, hi = lo + per < ntile ? lo + per : ntile;
+        int64_t acc = 0;
+        for (int64_t b = lo; b < hi; b++) acc += off[b];
+        part[p] = acc;
+    }
     __syncthreads();
     if (tid == 0) {
         int64_t run = 0;
-        for (int i = 0; i < 1024; i++) { const int64_t v = part[i]; part[i] = run; run += v; }
+        for (int i = 0; i < kTieParts; i++) { const int64_t v = part[i]; part[i] = run; run += v; }
         tie_cnt[ch * 8 + kTieListed] = run;
     }
     __syncthreads();
-    int64_t run = part[tid];
-    for (int64_t b = lo; b < hi; b++) { const int64_t v = off[b]; off[b] = run; run += v; }
+    for (int j = 0; j < kTiePer; j++) {
+        const int p = tid * kTiePer + j;
+        const int64_t lo = (int64_t)p * per, hi = lo + per < ntile ? lo + per : ntile;
+        int64_t run = part[p];
+        for (int64_t b = lo; b < hi; b++) { const int64_t v = off[b]; off[b] = run; run += v; }
+    }
 }
 
 // ---- approximate prefix: block sums, then their exclusive scan ---------------------------------------
@@ -198,20 +212,24 @@ __global__ __launch_bounds__(256) void kw_tie_bsum(WaveGeom g, const WaveConst *
     if (lane == 0) guess[(int64_t)ch * nblk + b] = acc;
 }
 
-__global__ __launch_bounds__(1024) void kw_tie_bscan(WaveGeom g, const WaveConst *__restrict__ cst,
-                                                     const double *__restrict__ y, const int16_t *__restrict__ x,
-                                                     const double *__restrict__ mean,
-                                                     const int64_t *__restrict__ tie_cnt, double *__restrict__ guess,
-                                                     int64_t nblk)
+__global__ __launch_bounds__(kTieScanThreads) void kw_tie_bscan(WaveGeom g, const WaveConst *__restrict__ cst,
+                                                                const double *__restrict__ y, const int16_t *__restrict__ x,
+                                                                const double *__restrict__ mean,
+                                                                const int64_t *__restrict__ tie_cnt, double *__restrict__ guess,
+                                                                int64_t nblk)
 {
-    __shared__ double part[1024];
+    __shared__ double part[kTieParts];
     const int ch = blockIdx.x, tid = threadIdx.x;
     if (tie_cnt[ch * 8 + kTieTrig] == 0) return;
     double *gc = guess + (int64_t)ch * nblk;
-    const int64_t per = (nblk + 1023) / 1024, lo = (int64_t)tid * per, hi = lo + per < nblk ? lo + per : nblk;
-    double acc = 0.0;
-    for (int64_t b = lo; b < hi; b++) acc += gc[b];
-    part[tid] = acc;
+    const int64_t per = (nblk + kTieParts - 1) / kTieParts;
+    for (int j = 0; j < kTiePer; j++) {
+        const int p = tid * kTiePer + j;
+        const int64_t lo = (int64_t)p * per, hi = lo + per < nblk ? lo + per : nblk;
+        double acc = 0.0;
+        for (int64_t b = lo; b < hi; b++) acc += gc[b];
+        part[p] = acc;
+    }
     __syncthreads();
     if (tid == 0) {
         const int x0 = x[(int64_t)ch * g.T];
@@ -220,11 +238,15 @@ __global__ __launch_bounds__(1024) void kw_tie_bscan(WaveGeom g, const WaveConst
             const double d = y[(int64_t)ch * g.T] - mean[(int64_t)ch * (1 + g.N * g.L) + x0 - 1];
             run = cst[ch].A - (d * d) / cst[ch].den;
         }
-        for (int i = 0; i < 1024; i++) { const double v = part[i]; part[i] = run; run += v; }
+        for (int i = 0; i < kTieParts; i++) { const double v = part[i]; part[i] = run; run += v; }
     }
     __syncthreads();
-    double run = part[tid];
-    for (int64_t b = lo; b < hi; b++) { const double v = gc[b]; gc[b] = run; run += v; }
+    for (int j = 0; j < kTiePer; j++) {
+        const int p = tid * kTiePer + j;
+        const int64_t lo = (int64_t)p * per, hi = lo + per < nblk ? lo + per : nblk;
+        double run = part[p];
+        for (int64_t b = lo; b < hi; b++) { const double v = gc[b]; gc[b] = run; run += v; }
+    }
 }
 
 // ---- exact block increments ------------------------------------------------------------------------
@@ -755,12 +777,12 @@ int wave_tie_resolve(WaveDev *r, const double *d_y, int16_t *d_x, hipStream_t st
       const int64_t ntile = r->tie_ntile;
       const dim3 gt((unsigned)((ntile + 3) / 4), g.C);
       hipLaunchKernelGGL(kw_tie_collect<false>, gt, dim3(256), 0, st, g, d_x, r->psi, r->tie_cnt, r->tie_off, r->tie_list, ntile);
-      hipLaunchKernelGGL(kw_tie_offsets, dim3(g.C), dim3(1024), 0, st, r->tie_cnt, r->tie_cnt, r->tie_off, ntile);
+      hipLaunchKernelGGL(kw_tie_offsets, dim3(g.C), dim3(kTieScanThreads), 0, st, r->tie_cnt, r->tie_off, ntile);
       hipLaunchKernelGGL(kw_tie_collect<true>, gt, dim3(256), 0, st, g, d_x, r->psi, r->tie_cnt, r->tie_off, r->tie_list, ntile); }
     { WPROF(r, "kw_tie_prefix", st);
       hipLaunchKernelGGL(kw_tie_bsum, dim3((unsigned)((nblk + 3) / 4), g.C), dim3(256), 0, st, g, r->d_cst, d_y, d_x,
                          r->d_mean, r->d_ctab, r->tie_cnt, r->tie_guess, nblk);
-      hipLaunchKernelGGL(kw_tie_bscan, dim3(g.C), dim3(1024), 0, st, g, r->d_cst, d_y, d_x, r->d_mean, r->tie_cnt,
+      hipLaunchKernelGGL(kw_tie_bscan, dim3(g.C), dim3(kTieScanThreads), 0, st, g, r->d_cst, d_y, d_x, r->d_mean, r->tie_cnt,
                          r->tie_guess, nblk);
       hipLaunchKernelGGL(kw_tie_btransfer, dim3((unsigned)((nblk + 63) / 64), g.C), dim3(64), 0, st, g, r->d_cst, d_y,
                          d_x, r->d_mean, r->d_ctab, r->tie_cnt, r->tie_guess, r->tie_c, r->tie_ok, nblk); }

@@ -59,16 +59,14 @@ struct WIn {
 // exits serves all N junctions (O(N) instead of O(N^2) per sample).  Adding the same constant is
 // monotone, so the winner can differ from the reference's candidate-by-candidate scan only by a tie
 // created in rounding; such a decision has a zero margin and is flagged like any other near-tie.
-template <int N, bool UC>
-__global__ __launch_bounds__(64, wave_occ<N>()) void kw_vit(WaveGeom g, const WaveConst *__restrict__ cst,
-                                                            const double *__restrict__ y,
-                                                            const double *__restrict__ Rf,
-                                                            const double *__restrict__ virt,
-                                                            const double *__restrict__ ysum,
-                                                            uint32_t *__restrict__ psi, double *__restrict__ vpre,
-                                                            double *__restrict__ vend,
-                                                            const int32_t *__restrict__ vfail, uint32_t *__restrict__ trash,
-                                                            int redo)
+// One chain's sweep, the body of kw_vit (redo = false: every chain, from its warm-up) and of kw_vit_redo (redo = true:
+// a chain whose certificate failed, from the previous chain's exact end state).
+template <int N, bool UC, bool redo>
+__device__ __forceinline__ void vit_chain(const WaveGeom &g, const WaveConst *__restrict__ cst,
+                                          const double *__restrict__ y, const double *__restrict__ Rf,
+                                          const double *__restrict__ virt, const double *__restrict__ ysum,
+                                          uint32_t *__restrict__ psi, double *__restrict__ vpre,
+                                          double *__restrict__ vend, uint32_t *__restrict__ trash, const int cg)
 {
     constexpr int EB = wpsi_bits_c(N), EPW = wpsi_epw_c(N), PW = wpsi_words_c(N), D = wave_depth<N>();
     // Model constants live in LDS next to the delay line: they are wave-uniform and many; as
@@ -80,8 +78,7 @@ __global__ __launch_bounds__(64, wave_occ<N>()) void kw_vit(WaveGeom g, const Wa
     double *KC = lds_vit;           // c00 | mean0 | den | c0[N] | cend[N] | cxT[N*N] (UC: cxin[N] first)
     double *DL = lds_vit + KSIZE;   // [N][RB] delay line: P_a(t') at slot (t' - tinit + L) mod RB
     const int lane = threadIdx.x;
-    const int cg = blockIdx.x, ch = cg / g.nch, c = cg % g.nch;
-    if (redo && (c == 0 || vfail[cg] == 0 || vfail[cg - 1] != 0)) return;  // wave-uniform
+    const int ch = cg / g.nch, c = cg % g.nch;
     const int L = g.L, W = g.W, RB = g.RB, B = g.B;
     const int64_t T = g.T;
     const int64_t tc = (int64_t)c * B;
@@ -281,16 +278,56 @@ __global__ __launch_bounds__(64, wave_occ<N>()) void kw_vit(WaveGeom g, const Wa
     }
 }
 
+template <int N, bool UC>
+__global__ __launch_bounds__(64, wave_occ<N>()) void kw_vit(WaveGeom g, const WaveConst *__restrict__ cst,
+                                                            const double *__restrict__ y,
+                                                            const double *__restrict__ Rf,
+                                                            const double *__restrict__ virt,
+                                                            const double *__restrict__ ysum,
+                                                            uint32_t *__restrict__ psi, double *__restrict__ vpre,
+                                                            double *__restrict__ vend, uint32_t *__restrict__ trash)
+{
+    vit_chain<N, UC, false>(g, cst, y, Rf, virt, ysum, psi, vpre, vend, trash, (int)blockIdx.x);
+}
+
+// Re-sweep of the chains the previous kw_vit_check launch listed (its certificate failed, its predecessor's did
+// not, so vend of the predecessor is final): a small fixed grid walks the list, and in the common case of an
+// empty list its few waves exit at once.  TIGHT (the decode runs beside an E-step, up to four rings): the kernel is
+// held to the 80 registers that are free on a SIMD beside two waves of the backward sweep (six waves per SIMD).  A
+// launch that needs more waits, list empty or not, until a wave of that sweep retires on every XCD its workgroups
+// were dealt to -- 0.2 ms measured.  The price is scratch traffic in the rare re-sweep of a chain (184 B per lane
+// at N = 4), and a decode on its own, which has the registers to itself, does not pay it.  Not for more than four
+// rings: there the backward sweep holds 330 registers in ONE wave per SIMD, which leaves 182, and the redo kernel
+// of 5-8 rings (127-172 registers) fits beside it as it is; at 80 registers it would spill its whole delay-line
+// state.
+constexpr int kVitRedoGrid = 64;
+template <int N, bool UC, bool TIGHT>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TIGHT ? 6 : 1))) void kw_vit_redo(WaveGeom g, const WaveConst *__restrict__ cst,
+                                                                 const double *__restrict__ y,
+                                                                 const double *__restrict__ Rf,
+                                                                 const double *__restrict__ virt,
+                                                                 const double *__restrict__ ysum,
+                                                                 uint32_t *__restrict__ psi, double *__restrict__ vpre,
+                                                                 double *__restrict__ vend, uint32_t *__restrict__ trash,
+                                                                 const int32_t *__restrict__ head,
+                                                                 const int32_t *__restrict__ list)
+{
+    const int n = head[0];
+    for (int q = blockIdx.x; q < n; q += gridDim.x)   // wave-uniform; a chain's sweep ends on a barrier
+        vit_chain<N, UC, true>(g, cst, y, Rf, virt, ysum, psi, vpre, vend, trash, list[q]);
+}
+
 // Boundary certificate: one wavefront per chain boundary; all 1 + N*L entries of the warm-up state
 // must equal the previous chain's end state up to one constant.
-__global__ __launch_bounds__(64) void kw_vit_check(WaveGeom g, const double *__restrict__ vpre,
-                                                   const double *__restrict__ vend,
-                                                   int32_t *__restrict__ vfail, int64_t *__restrict__ diag,
-                                                   int final_round, double *__restrict__ dbg)
+struct VitCert {
+    bool fail, anybad;
+    double spread;
+};
+
+__device__ __forceinline__ VitCert vit_cert(const WaveGeom &g, const double *__restrict__ vpre,
+                                            const double *__restrict__ vend, int cg, int lane, double *__restrict__ dbgrec)
 {
-    const int lane = threadIdx.x;
-    const int cg = blockIdx.x, c = cg % g.nch;
-    if (c == 0) { if (lane == 0) vfail[cg] = 0; return; }
+    const int c = cg % g.nch;
     const int64_t SR = 1 + (int64_t)g.N * g.L;
     double lo = INFINITY, hi = -INFINITY;
     int64_t ilo = -1, ihi = -1, ibad = -1;
@@ -306,7 +343,7 @@ __global__ __launch_bounds__(64) void kw_vit_check(WaveGeom g, const double *__r
         if (d < lo) { lo = d; ilo = i; }
         if (d > hi) { hi = d; ihi = i; }
     }
-    if (dbg && final_round) {   // debug record: the extreme entries of the first boundaries
+    if (dbgrec) {   // debug record: the extreme entries of the first boundaries
         for (int o = 32; o > 0; o >>= 1) {
             const double l2 = __shfl_xor(lo, o), h2 = __shfl_xor(hi, o);
             const long long il2 = __shfl_xor((long long)ilo, o), ih2 = __shfl_xor((long long)ihi, o), ib2 = __shfl_xor((long long)ibad, o);
@@ -315,35 +352,55 @@ __global__ __launch_bounds__(64) void kw_vit_check(WaveGeom g, const double *__r
             if (ib2 > ibad) ibad = ib2;
         }
         if (lane == 0 && c <= 3) {
-            double *r = dbg + 16 + 8 * (c - 1);
+            double *r = dbgrec + 16 + 8 * (c - 1);
             r[0] = (double)cg; r[1] = lo; r[2] = (double)ilo; r[3] = hi; r[4] = (double)ihi; r[5] = (double)ibad;
             r[6] = ilo >= 0 ? vpre[cg * SR + ilo] : 0.0; r[7] = ilo >= 0 ? vend[(cg - 1) * SR + ilo] : 0.0;
         }
     }
     lo = -wave_max(-lo); hi = wave_max(hi);
-    const bool anybad = __any(bad);
-    const double spread = hi - lo;
-    const bool fail = anybad || !(spread <= kVitTol);
+    VitCert v;
+    v.anybad = __any(bad);
+    v.spread = hi - lo;
+    v.fail = v.anybad || !(v.spread <= kVitTol);
+    return v;
+}
+
+// The rounds before the final one also list the chains the next kw_vit_redo launch sweeps again: chain cg failed,
+// its predecessor did not (so the predecessor's end state is final) and it is not a channel's first chain.  The
+// predecessor's verdict is another workgroup's result of this same launch, so a failing chain works it out itself.
+__global__ __launch_bounds__(64) void kw_vit_check(WaveGeom g, const double *__restrict__ vpre,
+                                                   const double *__restrict__ vend,
+                                                   int32_t *__restrict__ vfail, int64_t *__restrict__ diag,
+                                                   int final_round, double *__restrict__ dbg,
+                                                   int32_t *__restrict__ head, int32_t *__restrict__ list)
+{
+    const int lane = threadIdx.x;
+    const int cg = blockIdx.x, c = cg % g.nch;
+    if (c == 0) { if (lane == 0) vfail[cg] = 0; return; }
+    const VitCert v = vit_cert(g, vpre, vend, cg, lane, final_round ? dbg : nullptr);
     if (lane == 0) {
-        vfail[cg] = fail ? 1 : 0;
+        vfail[cg] = v.fail ? 1 : 0;
         if (final_round) {
-            if (fail) atomicAdd((unsigned long long *)&diag[0], 1ull);
-            if (!anybad && spread == spread && spread < INFINITY)
-                atomicMax((unsigned long long *)&diag[2], (unsigned long long)__double_as_longlong(spread));
-        } else if (fail) {
+            if (v.fail) atomicAdd((unsigned long long *)&diag[0], 1ull);
+            if (!v.anybad && v.spread == v.spread && v.spread < INFINITY)
+                atomicMax((unsigned long long *)&diag[2], (unsigned long long)__double_as_longlong(v.spread));
+        } else if (v.fail) {
             atomicAdd((unsigned long long *)&diag[1], 1ull);  // chains swept again (all rounds)
         }
+    }
+    if (!final_round && v.fail) {   // wave-uniform
+        const bool prev_fail = c > 1 && vit_cert(g, vpre, vend, cg - 1, lane, nullptr).fail;
+        if (!prev_fail && lane == 0) list[atomicAdd(&head[0], 1)] = cg;
     }
 }
 
 // Final state = argmax over all S states at the last sample, first maximum in state order
-// (viterbi.jl:90).  delta(a,k) at T-1 is P_a(T-k).  One wave per channel.
-__global__ __launch_bounds__(64) void kw_vit_tail(WaveGeom g, const WaveConst *__restrict__ cst,
-                                                  const double *__restrict__ ysum,
-                                                  const double *__restrict__ vend,
-                                                  int32_t *__restrict__ final_state, int64_t *__restrict__ tie_cnt)
+// (viterbi.jl:90).  delta(a,k) at T-1 is P_a(T-k).  One wave per channel; every lane returns the same state.
+// *flagged: the runner-up is within the near-tie threshold (wave_ties.hip re-decides the arg-max exactly).
+__device__ __forceinline__ int vit_final_state(const WaveGeom &g, const WaveConst *__restrict__ cst,
+                                               const double *__restrict__ ysum, const double *__restrict__ vend,
+                                               int ch, int lane, bool *flagged)
 {
-    const int lane = threadIdx.x, ch = blockIdx.x;
     const int64_t SR = 1 + (int64_t)g.N * g.L;
     const double *rec = vend + ((int64_t)ch * g.nch + g.nch - 1) * SR;
     const int S = 1 + g.N * g.L;
@@ -362,13 +419,8 @@ __global__ __launch_bounds__(64) void kw_vit_tail(WaveGeom g, const WaveConst *_
         sec = fmax(fmax(sec, os), lose);
         if (take) { best = ov; bi = oi; }
     }
-    if (lane == 0) {
-        final_state[ch] = (bi >= S) ? 0 : bi;
-        if ((best - sec) < wave_thr(g, cst[ch], ysum, ch)) {   // wave_ties.hip re-decides it exactly
-            tie_cnt[ch * 8 + kTieTail] = 1;
-            atomicAdd((unsigned long long *)&tie_cnt[ch * 8 + kTieTrig], 1ull);
-        }
-    }
+    *flagged = (best - sec) < wave_thr(g, cst[ch], ysum, ch);
+    return (bi >= S) ? 0 : bi;
 }
 
 // Backtrace (viterbi.jl:93-94).  The path is cut into segments of Bb samples, one LANE per segment;
@@ -378,9 +430,204 @@ __global__ __launch_bounds__(64) void kw_vit_tail(WaveGeom g, const WaveConst *_
 // x 64 samples is read with coalesced rows into LDS and walked column-wise; x leaves the same way.
 // Flagged (near-tie) junction decisions met inside the owned segment are counted per channel (the trigger of
 // the exact resolver, wave_ties.hip).
+// Two kernels.  kw_backtrace (register rows): a lane holds its whole tile row (one or two words per sample) in
+// registers through the tile's unrolled walk -- 300 registers per lane, one wave per SIMD, the fastest when nothing
+// else runs.  kw_backtrace_light: tiles of 64 / 32 / 16 samples, and a lane reads its row from LDS in chunks of 8 / 4
+// samples (all words of a chunk's samples, so the reads do not depend on the walk) and puts the decoded ids into
+// the output tile chunk by chunk: at most 80 registers and 32 KB of LDS, so that it fits on a SIMD beside two
+// waves of the backward sweep (decode + E-step in one call).  Same integer logic, same x, bstate and tie counters.
+// Start of the walks that begin at a channel's last sample.  The workgroups that hold such a walk find the final
+// state themselves (vit_final_state: vend is final by now); the one that owns the last segment records it and its
+// near-tie flag.  (wave-uniform branch)
 template <int N>
-__global__ __launch_bounds__(64) void kw_backtrace(WaveGeom g, const uint32_t *__restrict__ psi,
-                                                   const int32_t *__restrict__ final_state,
+__device__ __forceinline__ void bt_start(const WaveGeom &g, const WaveConst *__restrict__ cst,
+                                         const double *__restrict__ ysum, const double *__restrict__ vend,
+                                         int32_t *__restrict__ final_state, int64_t *__restrict__ tie_cnt, int ch, int lane,
+                                         bool at_end, int &id, int &rem, int &wi, int &sh)
+{
+    constexpr int EB = wpsi_bits_c(N), EPW = wpsi_epw_c(N);
+    if (!__any(at_end)) return;
+    bool flagged;
+    const int fs = vit_final_state(g, cst, ysum, vend, ch, lane, &flagged);
+    if (blockIdx.x == gridDim.x - 1 && lane == 0) {   // the workgroup of the last segment
+        final_state[ch] = fs;
+        if (flagged) {   // wave_ties.hip re-decides it exactly
+            tie_cnt[ch * 8 + kTieTail] = 1;
+            atomicAdd((unsigned long long *)&tie_cnt[ch * 8 + kTieTrig], 1ull);
+        }
+    }
+    if (at_end && fs > 0) {
+        const int L = g.L, a0 = (fs - 1) / L, k0 = (fs - 1) % L + 1, e0 = a0 + 1;
+        id = fs + 1; rem = k0 - 1; wi = e0 / EPW; sh = (e0 % EPW) * EB;
+    }
+}
+
+// samples per tile of the light backtrace (the LDS of a workgroup stays below 32 KB)
+template <int N> constexpr int bt_tile()
+{
+    constexpr int PW = wpsi_words_c(N);
+    return PW == 1 ? 64 : (PW <= 3 ? 32 : 16);
+}
+// dynamic LDS of a light backtrace workgroup: the psi tile and the output tile (rows padded by one word)
+template <int N> constexpr size_t bt_lds_bytes()
+{
+    constexpr int PW = wpsi_words_c(N), TS = bt_tile<N>();
+    return sizeof(uint32_t) * (size_t)(PW * 64 * (TS + 1) + 64 * (TS / 2 + 1));
+}
+
+template <int N>
+__device__ __forceinline__ void backtrace_light_body(const WaveGeom &g, const WaveConst *__restrict__ cst,
+                                               const double *__restrict__ ysum, const double *__restrict__ vend,
+                                               const uint32_t *__restrict__ psi, int32_t *__restrict__ final_state,
+                                               int16_t *__restrict__ x, int32_t *__restrict__ bstate,
+                                               int64_t *__restrict__ tie_cnt)
+{
+    constexpr int EB = wpsi_bits_c(N), EPW = wpsi_epw_c(N), PW = wpsi_words_c(N);
+    constexpr int TS = bt_tile<N>();
+    constexpr int RPI = 64 / TS;            // segment rows per load instruction
+    constexpr int XW = TS / 2;              // decoded ids leave as pairs (two int16 per word)
+    constexpr int XRI = 64 / XW;            // rows per store instruction
+    constexpr int CH = PW == 1 ? 8 : 4;     // samples per register chunk
+    constexpr int NCH = TS / CH;
+    constexpr int SU = 2;                   // row loads in flight while a tile is staged
+    constexpr int XU = 2;                   // row stores in flight while the output tile leaves
+    static_assert(CH % 2 == 0 && TS % CH == 0, "chunks hold whole int16 pairs");
+    static_assert(bt_lds_bytes<N>() <= 32 * 1024, "LDS budget");
+    extern __shared__ uint32_t lds_bt[];    // tile[PW][64][TS + 1] | xt[64][XW + 1]
+    uint32_t (*tile)[64][TS + 1] = reinterpret_cast<uint32_t (*)[64][TS + 1]>(lds_bt);
+    uint32_t (*xt)[XW + 1] = reinterpret_cast<uint32_t (*)[XW + 1]>(lds_bt + PW * 64 * (TS + 1));
+    const int lane = threadIdx.x, ch = blockIdx.y;
+    const int L = g.L, Bb = g.Bb, Hb = g.Hb;
+    const int64_t T = g.T;
+    const int64_t sg0 = (int64_t)blockIdx.x * 64, sg = sg0 + lane;
+    const bool active = sg < g.nseg;
+    const int64_t s_lo = sg * Bb;
+    const int64_t s_hi = active ? ((s_lo + Bb) < T ? (s_lo + Bb) : T) : s_lo;
+    const int64_t te = (s_hi + Hb) < T ? (s_hi + Hb) : T;  // walk starts at te-1
+    const int64_t planePsi = (int64_t)g.C * T;
+    const uint32_t *pc = psi + (int64_t)ch * T;
+    int16_t *xc = x + (int64_t)ch * T;
+    const bool xal = ((reinterpret_cast<uintptr_t>(xc)) & 3) == 0;   // odd T puts later channels on odd samples
+    // times relative to the segment start: u = t - s_lo
+    const int te_rel = active ? (int)(te - s_lo) : 0, hi_rel = (int)(s_hi - s_lo);
+    const int t1 = s_lo >= 1 ? 0 : 1;                      // the step at t = 0 has no predecessor
+    const int t2 = s_lo >= 2 ? 0 : (int)(2 - s_lo);        // psi(1) only decides x[0]: kw_first_state
+    // walk state: id = state id at the current sample, rem = steps left inside the ring (0 at a junction),
+    // (wi, sh) = word and bit offset of the psi entry the next junction decision reads (entry e = ring + 1)
+    int id = 1, rem = 0, wi = 0, sh = 0;
+    bt_start<N>(g, cst, ysum, vend, final_state, tie_cnt, ch, lane, active && te == T, id, rem, wi, sh);
+    int nflag = 0, bs = 0;
+    const int lr = lane / TS, lc = lane % TS;
+    // one tile of the walk, newest sample first.  FAST: every lane of the wave is inside its walk for the
+    // whole tile and (OWN) inside / (not OWN) behind its own segment, so no per-lane time predicates.
+    // The decoded ids of a chunk go to the output tile when `emit` (the tile is inside the owned segments).
+    auto walk = [&](int q, auto fast_tag, auto own_tag, bool emit) {
+        constexpr bool FAST = decltype(fast_tag)::value, OWN = decltype(own_tag)::value;
+#pragma unroll 1
+        for (int k = NCH - 1; k >= 0; k--) {
+            uint32_t rowv[PW][CH], xr[CH / 2];
+#pragma unroll
+            for (int w = 0; w < PW; w++)
+#pragma unroll
+                for (int i = 0; i < CH; i++) rowv[w][i] = tile[w][lane][k * CH + i];
+#pragma unroll
+            for (int i = CH - 1; i >= 0; i--) {
+                const int u = TS * q + k * CH + i;
+                const bool interior = rem > 0;
+                if (FAST ? OWN : true) {
+                    if (i & 1) xr[i / 2] = (uint32_t)id << 16;
+                    else xr[i / 2] |= (uint32_t)id & 0xffffu;
+                }
+                uint32_t wsel = rowv[0][i];
+#pragma unroll
+                for (int w = 1; w < PW; w++) wsel = (wi == w) ? rowv[w][i] : wsel;
+                const uint32_t ent = wsel >> sh;
+                const int pj = (int)(ent & ((1u << (EB - 1)) - 1u));
+                const int flag = (int)((ent >> (EB - 1)) & 1u);
+                // junction: predecessor p = 0 silent (id 1), else the last state of ring p-1 (id 1 + p L)
+                const int jid = 1 + pj * L, jrem = pj ? L - 1 : 0;
+                const int jwi = pj / EPW, jsh = (pj % EPW) * EB;
+                if (FAST) {
+                    if (OWN) nflag += interior ? 0 : flag;
+                    id = interior ? id - 1 : jid;
+                    rem = interior ? rem - 1 : jrem;
+                    wi = interior ? wi : jwi;
+                    sh = interior ? sh : jsh;
+                } else {
+                    const bool live = u < te_rel, step = live && u >= t1;
+                    bs = (live && u == hi_rel) ? id : bs;
+                    if (step && !interior && u < hi_rel && u >= t2) nflag += flag;
+                    id = step ? (interior ? id - 1 : jid) : id;
+                    rem = step ? (interior ? rem - 1 : jrem) : rem;
+                    wi = step ? (interior ? wi : jwi) : wi;
+                    sh = step ? (interior ? sh : jsh) : sh;
+                }
+            }
+            if (FAST ? OWN : true) {
+                if (emit) {
+#pragma unroll
+                    for (int j = 0; j < CH / 2; j++) xt[lane][k * (CH / 2) + j] = xr[j];
+                }
+            }
+        }
+    };
+    const int nq = (Bb + Hb) / TS;
+    for (int q = nq - 1; q >= 0; q--) {
+        // stage psi rows: row r = segment sg0 + r, samples s_lo(r) + TS q + lc.  Wave-uniform tile origin +
+        // 32-bit lane offsets; rows that do not exist read the origin and are staged as zeros.
+        {
+            const int64_t tb = sg0 * Bb + (int64_t)TS * q;
+            const uint32_t *base = pc + (tb < T ? tb : 0);
+#pragma unroll SU
+            for (int rr = 0; rr < 64; rr += RPI) {
+                const int r = rr + lr;
+                const bool ok = (sg0 + r) < g.nseg && tb + (int64_t)r * Bb + lc < T;
+                const uint32_t off = ok ? (uint32_t)(r * Bb + lc) : 0u;
+                uint32_t v[PW];
+#pragma unroll
+                for (int w = 0; w < PW; w++) v[w] = (base + w * planePsi)[off];
+#pragma unroll
+                for (int w = 0; w < PW; w++) tile[w][r][lc] = ok ? v[w] : 0u;
+            }
+        }
+        __syncthreads();
+        const int u0 = TS * q, u1 = u0 + TS;
+        const bool own_tile = u0 < Bb;
+        // wave-uniform choice of the tile body
+        const bool lane_fast = u0 >= t1 && u1 <= te_rel &&
+                               (own_tile ? (u1 <= hi_rel && u0 >= t2) : (u0 > hi_rel));
+        const bool fast = __all(lane_fast);
+        if (fast && own_tile) walk(q, std::true_type(), std::true_type(), true);
+        else if (fast) walk(q, std::true_type(), std::false_type(), false);
+        else walk(q, std::false_type(), std::false_type(), own_tile);
+        if (own_tile) {  // owned rows: write x out, coalesced
+            __syncthreads();
+            const int xrw = lane / XW, xcw = lane % XW;
+#pragma unroll XU
+            for (int rr = 0; rr < 64; rr += XRI) {
+                const int r = rr + xrw;
+                const int64_t t = (sg0 + r) * Bb + (int64_t)TS * q + 2 * xcw;
+                if ((sg0 + r) < g.nseg && t < T) {
+                    const uint32_t v = xt[r][xcw];
+                    if (t + 1 < T && xal) *reinterpret_cast<uint32_t *>(xc + t) = v;
+                    else {
+                        xc[t] = (int16_t)(v & 0xffffu);
+                        if (t + 1 < T) xc[t + 1] = (int16_t)(v >> 16);
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (active && hi_rel < te_rel) bstate[(int64_t)ch * g.nseg + sg] = bs;
+    for (int o = 32; o > 0; o >>= 1) nflag += __shfl_xor(nflag, o);
+    if (lane == 0 && nflag) atomicAdd((unsigned long long *)&tie_cnt[ch * 8 + kTieTrig], (unsigned long long)nflag);
+}
+
+template <int N>
+__global__ __launch_bounds__(64) void kw_backtrace(WaveGeom g, const WaveConst *__restrict__ cst,
+                                                   const double *__restrict__ ysum, const double *__restrict__ vend,
+                                                   const uint32_t *__restrict__ psi, int32_t *__restrict__ final_state,
                                                    int16_t *__restrict__ x, int32_t *__restrict__ bstate,
                                                    int64_t *__restrict__ tie_cnt)
 {
@@ -410,13 +657,7 @@ __global__ __launch_bounds__(64) void kw_backtrace(WaveGeom g, const uint32_t *_
     // walk state: id = state id at the current sample, rem = steps left inside the ring (0 at a junction),
     // (wi, sh) = word and bit offset of the psi entry the next junction decision reads (entry e = ring + 1)
     int id = 1, rem = 0, wi = 0, sh = 0;
-    if (active && te == T) {
-        const int fs = final_state[ch];
-        if (fs > 0) {
-            const int a0 = (fs - 1) / L, k0 = (fs - 1) % L + 1, e0 = a0 + 1;
-            id = fs + 1; rem = k0 - 1; wi = e0 / EPW; sh = (e0 % EPW) * EB;
-        }
-    }
+    bt_start<N>(g, cst, ysum, vend, final_state, tie_cnt, ch, lane, active && te == T, id, rem, wi, sh);
     int nflag = 0, bs = 0;
     const int lr = lane / TS, lc = lane % TS;
     constexpr bool ROWREG = PW <= 2;        // the lane's tile row in registers (wider rows stay in LDS)
@@ -525,6 +766,19 @@ __global__ __launch_bounds__(64) void kw_backtrace(WaveGeom g, const uint32_t *_
     if (lane == 0 && nflag) atomicAdd((unsigned long long *)&tie_cnt[ch * 8 + kTieTrig], (unsigned long long)nflag);
 }
 
+// Six waves per SIMD is an 80-register budget.  The tiles are DYNAMIC shared memory: with a static size the
+// compiler sees that LDS caps the waves per SIMD at two and takes twice the registers that are free beside the
+// backward sweep.
+template <int N>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6)))
+void kw_backtrace_light(WaveGeom g, const WaveConst *__restrict__ cst, const double *__restrict__ ysum,
+                        const double *__restrict__ vend, const uint32_t *__restrict__ psi,
+                        int32_t *__restrict__ final_state, int16_t *__restrict__ x, int32_t *__restrict__ bstate,
+                        int64_t *__restrict__ tie_cnt)
+{
+    backtrace_light_body<N>(g, cst, ysum, vend, psi, final_state, x, bstate, tie_cnt);
+}
+
 __device__ __forceinline__ void wwalk_step(const WaveGeom &g, const uint32_t *__restrict__ pc, int64_t planePsi,
                                            int64_t t, int &a, int &k, int64_t &nflag)
 {
@@ -539,42 +793,46 @@ __device__ __forceinline__ void wwalk_step(const WaveGeom &g, const uint32_t *__
 }
 
 // Stitch check: the state segment s's walk had on the first sample of segment s+1 must equal what
-// segment s+1 emitted there; otherwise segment s is queued for a serial re-walk.
-__global__ void kw_stitch_check(WaveGeom g, const int16_t *__restrict__ x, const int32_t *__restrict__ bstate,
-                                int32_t *__restrict__ redo)
+// segment s+1 emitted there; otherwise segment s is queued for a re-walk.
+__device__ __forceinline__ void stitch_check_one(const WaveGeom &g, const int16_t *x, const int32_t *bstate,
+                                                 int32_t *head, int32_t *list, int64_t i)
 {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)g.C * g.nseg) return;
     const int ch = (int)(i / g.nseg);
     const int64_t sg = i % g.nseg;
     if (sg >= g.nseg - 1) return;
-    if (bstate[i] != (int)x[(int64_t)ch * g.T + (sg + 1) * g.Bb]) {
-        const int slot = atomicAdd(&redo[0], 1);
-        redo[1 + slot] = (int32_t)i;
-    }
+    if (bstate[i] != (int)x[(int64_t)ch * g.T + (sg + 1) * g.Bb]) list[atomicAdd(&head[0], 1)] = (int32_t)i;
+}
+
+__global__ void kw_stitch_check(WaveGeom g, const int16_t *__restrict__ x, const int32_t *__restrict__ bstate,
+                                int32_t *__restrict__ head, int32_t *__restrict__ list)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)g.C * g.nseg) return;
+    stitch_check_one(g, x, bstate, head, list, i);
 }
 
 // Parallel repair of the queued segments whose successor is not queued itself (the common case: isolated
 // disagreements on busy signals with long rings).  One workgroup per segment: its psi goes global -> LDS in
 // full rows, lane 0 walks it from the successor's first state, all lanes write x.  A repaired segment whose
-// own first sample changed is caught by the second kw_stitch_check and the serial kw_stitch_fix below, which
+// own first sample changed is caught by the second check and the serial repair of kw_stitch_fix below, which
 // also takes the chains of consecutive failures this kernel leaves alone.
 __global__ __launch_bounds__(64) void kw_stitch_fix_par(WaveGeom g, const uint32_t *__restrict__ psi,
                                                         int16_t *__restrict__ x, int32_t *__restrict__ bstate,
+                                                        const int32_t *__restrict__ head,
                                                         const int32_t *__restrict__ redo, int64_t *__restrict__ diag,
                                                         int64_t *__restrict__ tie_cnt)
 {
     extern __shared__ uint32_t shp[];                 // [PW][Bb + 1] psi of the segment and the sample after it | Bb ids
-    const int lane = threadIdx.x, n = redo[0];
+    const int lane = threadIdx.x, n = head[0];
     const int L = g.L, Bb = g.Bb, PW = g.PW;
     int16_t *xs = reinterpret_cast<int16_t *>(shp + (size_t)PW * (Bb + 1));
     const int64_t planePsi = (int64_t)g.C * g.T;
     for (int q = blockIdx.x; q < n; q += gridDim.x) {
-        const int32_t id = redo[1 + q];
+        const int32_t id = redo[q];
         const int ch = (int)(id / g.nseg);
         const int64_t sg = id % g.nseg;
         bool succ = false;
-        for (int j = lane; j < n; j += 64) succ = succ || (redo[1 + j] == id + 1 && sg + 1 < g.nseg);
+        for (int j = lane; j < n; j += 64) succ = succ || (redo[j] == id + 1 && sg + 1 < g.nseg);
         if (__any(succ)) continue;
         const uint32_t *pc = psi + (int64_t)ch * g.T;
         int16_t *xc = x + (int64_t)ch * g.T;
@@ -614,52 +872,14 @@ __global__ __launch_bounds__(64) void kw_stitch_fix_par(WaveGeom g, const uint32
     }
 }
 
-__global__ void kw_stitch_fix(WaveGeom g, const uint32_t *__restrict__ psi, int16_t *__restrict__ x,
-                              int32_t *__restrict__ bstate, const int32_t *__restrict__ redo,
-                              int64_t *__restrict__ diag, int64_t *__restrict__ tie_cnt)
-{
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const int n = redo[0];
-    const int L = g.L, Bb = g.Bb;
-    const int64_t planePsi = (int64_t)g.C * g.T;
-    int64_t fixes = 0;
-    for (int q = 0; q < n; q++) {
-        const int ch = (int)(redo[1 + q] / g.nseg);
-        int64_t nflag = 0;
-        int64_t sg = redo[1 + q] % g.nseg;
-        const uint32_t *pc = psi + (int64_t)ch * g.T;
-        int16_t *xc = x + (int64_t)ch * g.T;
-        while (sg >= 0) {
-            const int64_t tn = (sg + 1) * Bb;  // first sample of segment sg+1
-            const int want = xc[tn];
-            if (bstate[(int64_t)ch * g.nseg + sg] == want) break;
-            bstate[(int64_t)ch * g.nseg + sg] = want;
-            fixes++;
-            int a = -1, k = 0;
-            if (want > 1) { a = (want - 2) / L; k = (want - 2) % L + 1; }
-            wwalk_step(g, pc, planePsi, tn, a, k, nflag);
-            for (int64_t t = tn - 1; t >= sg * Bb; t--) {
-                xc[t] = (int16_t)((a < 0) ? 1 : 2 + a * L + (k - 1));
-                if (t == 0) break;
-                if (t > sg * Bb) wwalk_step(g, pc, planePsi, t, a, k, nflag);
-            }
-            sg--;  // did the first sample of segment sg change?  then segment sg-1 must be re-checked
-        }
-        if (nflag) atomicAdd((unsigned long long *)&tie_cnt[ch * 8 + kTieTrig], (unsigned long long)nflag);
-    }
-    diag[1] += fixes;
-}
-
 // The first decoded state, exactly as the reference finds it: x[0] = psi_1(x[1]) and psi_1 only sees
 // the first trellis column, which is plain emission (viterbi.jl:55-63).  Template tails are ~1e-16, so
 // the "ring in its last phase at sample 0" candidates differ by a few ulps only; re-deciding this one
 // sample with the reference's own operations (strict '>', list order) makes it exact.
-__global__ void kw_first_state(WaveGeom g, const WaveConst *__restrict__ cst, const double *__restrict__ y,
-                               const double *__restrict__ mean, const double *__restrict__ ctab_all,
-                               int16_t *__restrict__ x)
+__device__ __forceinline__ void first_state(const WaveGeom &g, const WaveConst *__restrict__ cst,
+                                            const double *__restrict__ y, const double *__restrict__ mean,
+                                            const double *__restrict__ ctab_all, int16_t *x, int ch)
 {
-    const int ch = blockIdx.x;
-    if (threadIdx.x != 0 || g.T < 2) return;
     const int N = g.N, L = g.L, S = 1 + N * L;
     const double *ctab = ctab_all + (int64_t)ch * (1 + 2 * N + N * N + N * L);
     const double *c0 = ctab + 1, *cend = ctab + 1 + N, *cx = ctab + 1 + 2 * N, *cint = ctab + 1 + 2 * N + N * N;
@@ -677,7 +897,7 @@ __global__ void kw_first_state(WaveGeom g, const WaveConst *__restrict__ cst, co
         const double tt = t1 + lp;
         if (tt > best) { best = tt; arg = state; }
     };
-    const int x1 = xc[1];
+    const int x1 = *(const volatile int16_t *)&xc[1];   // the repair above may have rewritten it
     if (x1 == 1) {
         cand(1, 0.0, ctab[0]);
         for (int a = 0; a < N; a++) cand(1 + a * L + L, T1(a, L), cend[a]);
@@ -692,6 +912,63 @@ __global__ void kw_first_state(WaveGeom g, const WaveConst *__restrict__ cst, co
         }
     }
     xc[0] = (int16_t)arg;
+}
+
+// What is left after kw_stitch_fix_par, in ONE workgroup: when the first check listed anything (head1), the check
+// is repeated (list 2), thread 0 repairs the listed segments serially -- chains of consecutive failures, first
+// samples that changed -- and a workgroup barrier orders its stores before the last step, which every call needs:
+// x[0] of every channel (first_state).  Nothing was listed: nothing can have changed, straight to that step.
+__global__ __launch_bounds__(256) void kw_stitch_fix(WaveGeom g, const WaveConst *__restrict__ cst,
+                                                     const double *__restrict__ y, const double *__restrict__ mean,
+                                                     const double *__restrict__ ctab_all,
+                                                     const uint32_t *__restrict__ psi, int16_t *x, int32_t *bstate,
+                                                     const int32_t *__restrict__ head1, int32_t *head2, int32_t *redo,
+                                                     int64_t *__restrict__ diag, int64_t *__restrict__ tie_cnt)
+{
+    const int tid = threadIdx.x;
+    if (head1[0] != 0) {   // uniform over the workgroup
+        const int64_t nsegT = (int64_t)g.C * g.nseg;
+        for (int64_t i = tid; i < nsegT; i += blockDim.x) stitch_check_one(g, x, bstate, head2, redo, i);
+        __threadfence();
+        __syncthreads();
+        if (tid == 0) {
+            const int n = atomicAdd(&head2[0], 0);
+            const volatile int32_t *lst = redo;
+            const int L = g.L, Bb = g.Bb;
+            const int64_t planePsi = (int64_t)g.C * g.T;
+            int64_t fixes = 0;
+            for (int q = 0; q < n; q++) {
+                const int32_t ent = lst[q];
+                const int ch = (int)(ent / g.nseg);
+                int64_t nflag = 0;
+                int64_t sg = ent % g.nseg;
+                const uint32_t *pc = psi + (int64_t)ch * g.T;
+                int16_t *xc = x + (int64_t)ch * g.T;
+                while (sg >= 0) {
+                    const int64_t tn = (sg + 1) * Bb;  // first sample of segment sg+1
+                    const int want = xc[tn];
+                    if (bstate[(int64_t)ch * g.nseg + sg] == want) break;
+                    bstate[(int64_t)ch * g.nseg + sg] = want;
+                    fixes++;
+                    int a = -1, k = 0;
+                    if (want > 1) { a = (want - 2) / L; k = (want - 2) % L + 1; }
+                    wwalk_step(g, pc, planePsi, tn, a, k, nflag);
+                    for (int64_t t = tn - 1; t >= sg * Bb; t--) {
+                        xc[t] = (int16_t)((a < 0) ? 1 : 2 + a * L + (k - 1));
+                        if (t == 0) break;
+                        if (t > sg * Bb) wwalk_step(g, pc, planePsi, t, a, k, nflag);
+                    }
+                    sg--;  // did the first sample of segment sg change?  then segment sg-1 must be re-checked
+                }
+                if (nflag) atomicAdd((unsigned long long *)&tie_cnt[ch * 8 + kTieTrig], (unsigned long long)nflag);
+            }
+            diag[1] += fixes;
+        }
+        __threadfence();
+        __syncthreads();
+    }
+    if (g.T >= 2)
+        for (int ch = tid; ch < g.C; ch += blockDim.x) first_state(g, cst, y, mean, ctab_all, x, ch);
 }
 
 // ll = sum_{t=1..T-1} T1[x_t, t]  (viterbi.jl:92-96) without the trellis:
@@ -764,39 +1041,44 @@ int wave_viterbi_sweep(WaveDev *r, const double *d_y, hipStream_t st)
         if (rc) return rc;
         { WPROF(r, "kw_vit", st);
           hipLaunchKernelGGL(kern, dim3(nchT), dim3(64), lds, st, g, r->d_cst, d_y, r->Rf, r->virt, r->ysum,
-                             r->psi, r->vpre, r->vend, r->vfail, (uint32_t *)r->trash, 0); }
+                             r->psi, r->vpre, r->vend, (uint32_t *)r->trash); }
         HS_HIP(hipGetLastError());
         return HMMSORT_OK;
     });
 }
 
-// boundary certificates with exact re-sweeps, final state, backtrace + stitch, x[0], ll
-int wave_viterbi_post(WaveDev *r, const double *d_y, int16_t *d_x, double *d_ll, hipStream_t st)
+// boundary certificates with exact re-sweeps, final state + backtrace, stitch + x[0], near-ties, ll.  The call has
+// zeroed diag, the tie counters and the list heads (wave_zero_bytes): every dependency below is a launch boundary.
+int wave_viterbi_post(WaveDev *r, const double *d_y, int16_t *d_x, double *d_ll, hipStream_t st, bool beside)
 {
     const WaveGeom &g = r->g;
     const int nchT = g.C * g.nch;
+    const bool light = g.backtrace == 2 || (g.backtrace == 0 && beside);
     int rc = dispatch_N(g.N, [&](auto n) {
         constexpr int N = decltype(n)::value;
         const size_t lds = ((size_t)N * (g.RB + 1) + 3 + 2 * N + N * N) * sizeof(double);
-        auto kern = kw_vit<N, true>;
-        if constexpr (N <= 8) { if (!r->uniform_cx) kern = kw_vit<N, false>; }   // per-source values: up to 8 rings (wave_supported)
+        auto kern = kw_vit_redo<N, true, false>;
+        if constexpr (N <= 8) { if (!r->uniform_cx) kern = kw_vit_redo<N, false, false>; }   // per-source values: up to 8 rings (wave_supported)
+        if constexpr (N <= 4) { if (beside) kern = r->uniform_cx ? kw_vit_redo<N, true, true> : kw_vit_redo<N, false, true>; }
+        int rc2 = wave_lds_attr(kern, lds);
+        if (rc2) return rc2;
         for (int round = 0; round < kVitRounds && g.nch > 1; round++) {
+            int32_t *head = r->heads + round, *list = r->vlist + (size_t)round * nchT;
             { WPROF(r, "kw_vit_check", st);
-              hipLaunchKernelGGL(kw_vit_check, dim3(nchT), dim3(64), 0, st, g, r->vpre, r->vend, r->vfail, r->diag, 0, nullptr); }
+              hipLaunchKernelGGL(kw_vit_check, dim3(nchT), dim3(64), 0, st, g, r->vpre, r->vend, r->vfail, r->diag, 0, nullptr,
+                                 head, list); }
             { WPROF(r, "kw_vit_redo", st);
-              hipLaunchKernelGGL(kern, dim3(nchT), dim3(64), lds, st, g, r->d_cst, d_y, r->Rf, r->virt,
-                                 r->ysum, r->psi, r->vpre, r->vend, r->vfail, (uint32_t *)r->trash, 1); }
+              hipLaunchKernelGGL(kern, dim3(std::min(nchT, kVitRedoGrid)), dim3(64), lds, st, g, r->d_cst, d_y, r->Rf,
+                                 r->virt, r->ysum, r->psi, r->vpre, r->vend, (uint32_t *)r->trash, head, list); }
         }
         { WPROF(r, "kw_vit_check", st);
-          hipLaunchKernelGGL(kw_vit_check, dim3(nchT), dim3(64), 0, st, g, r->vpre, r->vend, r->vfail, r->diag, 1, r->dbg); }
-        HS_HIP(hipMemsetAsync(r->tie_cnt, 0, (size_t)g.C * 8 * sizeof(int64_t), st));
-        { WPROF(r, "kw_vit_tail", st);
-          hipLaunchKernelGGL(kw_vit_tail, dim3(g.C), dim3(64), 0, st, g, r->d_cst, r->ysum, r->vend, r->final_state,
-                             r->tie_cnt); }
-        HS_HIP(hipMemsetAsync(r->redo, 0, sizeof(int32_t), st));
+          hipLaunchKernelGGL(kw_vit_check, dim3(nchT), dim3(64), 0, st, g, r->vpre, r->vend, r->vfail, r->diag, 1, r->dbg,
+                             nullptr, nullptr); }
         { WPROF(r, "kw_backtrace", st);
-          hipLaunchKernelGGL((kw_backtrace<N>), dim3((unsigned)((g.nseg + 63) / 64), g.C), dim3(64), 0, st, g, r->psi,
-                             r->final_state, d_x, r->bstate, r->tie_cnt); }
+          auto kb = light ? kw_backtrace_light<N> : kw_backtrace<N>;
+          const size_t ldsb = light ? bt_lds_bytes<N>() : 0;   // the register-row form's tiles are static
+          hipLaunchKernelGGL(kb, dim3((unsigned)((g.nseg + 63) / 64), g.C), dim3(64), ldsb, st, g, r->d_cst, r->ysum, r->vend,
+                             r->psi, r->final_state, d_x, r->bstate, r->tie_cnt); }
         HS_HIP(hipGetLastError());
         return HMMSORT_OK;
     });
@@ -804,20 +1086,15 @@ int wave_viterbi_post(WaveDev *r, const double *d_y, int16_t *d_x, double *d_ll,
     const int64_t nsegT = (int64_t)g.C * g.nseg;
     { WPROF(r, "kw_stitch_check", st);
       hipLaunchKernelGGL(kw_stitch_check, dim3((unsigned)((nsegT + 255) / 256)), dim3(256), 0, st, g, d_x, r->bstate,
-                         r->redo); }
+                         r->heads + 2, r->redo); }
     { WPROF(r, "kw_stitch_fix", st);
-      // isolated failures in parallel, then a second check and the serial repair for what is left (chains of
-      // consecutive failures, first samples that changed)
+      // isolated failures in parallel, then (one launch) a second check and the serial repair for what is left
+      // (chains of consecutive failures, first samples that changed) and x[0] of every channel
       const size_t ldsp = ((size_t)g.PW * (g.Bb + 1)) * sizeof(uint32_t) + (size_t)g.Bb * sizeof(int16_t) + 8;
-      hipLaunchKernelGGL(kw_stitch_fix_par, dim3(256), dim3(64), ldsp, st, g, r->psi, d_x, r->bstate, r->redo, r->diag,
-                         r->tie_cnt);
-      HS_HIP(hipMemsetAsync(r->redo, 0, sizeof(int32_t), st));
-      hipLaunchKernelGGL(kw_stitch_check, dim3((unsigned)((nsegT + 255) / 256)), dim3(256), 0, st, g, d_x, r->bstate,
-                         r->redo);
-      hipLaunchKernelGGL(kw_stitch_fix, dim3(1), dim3(64), 0, st, g, r->psi, d_x, r->bstate, r->redo, r->diag,
-                         r->tie_cnt); }
-    { WPROF(r, "kw_first_state", st);
-      hipLaunchKernelGGL(kw_first_state, dim3(g.C), dim3(64), 0, st, g, r->d_cst, d_y, r->d_mean, r->d_ctab, d_x); }
+      hipLaunchKernelGGL(kw_stitch_fix_par, dim3(256), dim3(64), ldsp, st, g, r->psi, d_x, r->bstate, r->heads + 2, r->redo,
+                         r->diag, r->tie_cnt);
+      hipLaunchKernelGGL(kw_stitch_fix, dim3(1), dim3(256), 0, st, g, r->d_cst, d_y, r->d_mean, r->d_ctab, r->psi, d_x,
+                         r->bstate, r->heads + 2, r->heads + 3, r->redo + nsegT, r->diag, r->tie_cnt); }
     // flagged near-ties on the decoded path: re-decided with the reference's own arithmetic (no-ops otherwise)
     if ((rc = wave_tie_resolve(r, d_y, d_x, st))) return rc;
     { WPROF(r, "kw_ll_partial", st);
@@ -833,10 +1110,10 @@ int wave_viterbi(WaveDev *r, const double *d_y, int16_t *d_x, double *d_ll, hipS
 {
     return wave_graphed(r, 1, d_y, d_x, d_ll, nullptr, st, [&](hipStream_t s) -> int {
         int rc;
-        HS_HIP(hipMemsetAsync(r->diag, 0, 8 * sizeof(int64_t), s));
+        HS_HIP(hipMemsetAsync(r->diag, 0, wave_zero_bytes(r, true), s));   // diag, the tie counters, the list heads
         if ((rc = wave_prepare(r, d_y, s))) return rc;
         if ((rc = wave_viterbi_sweep(r, d_y, s))) return rc;
-        return wave_viterbi_post(r, d_y, d_x, d_ll, s);
+        return wave_viterbi_post(r, d_y, d_x, d_ll, s, false);
     });
 }
 
