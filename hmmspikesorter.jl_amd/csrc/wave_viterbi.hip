@@ -382,8 +382,13 @@ __global__ __launch_bounds__(64) void kw_vit_check(WaveGeom g, const double *__r
         vfail[cg] = v.fail ? 1 : 0;
         if (final_round) {
             if (v.fail) atomicAdd((unsigned long long *)&diag[0], 1ull);
-            if (!v.anybad && v.spread == v.spread && v.spread < INFINITY)
-                atomicMax((unsigned long long *)&diag[2], (unsigned long long)__double_as_longlong(v.spread));
+            if (!v.anybad && v.spread == v.spread && v.spread < INFINITY) {
+                // a spread is >= 0, so its bits order like its value.  Most chains do not raise the maximum: they
+                // read it and leave (a stale read only costs an atomic that changes nothing).
+                const unsigned long long sb = (unsigned long long)__double_as_longlong(v.spread);
+                if (sb > *reinterpret_cast<volatile unsigned long long *>(&diag[2]))
+                    atomicMax((unsigned long long *)&diag[2], sb);
+            }
         } else if (v.fail) {
             atomicAdd((unsigned long long *)&diag[1], 1ull);  // chains swept again (all rounds)
         }
@@ -468,11 +473,13 @@ template <int N> constexpr int bt_tile()
     constexpr int PW = wpsi_words_c(N);
     return PW == 1 ? 64 : (PW <= 3 ? 32 : 16);
 }
-// dynamic LDS of a light backtrace workgroup: the psi tile and the output tile (rows padded by one word)
+// dynamic LDS of a light backtrace workgroup: the psi tile (rows padded by four words: a row starts on 16 bytes,
+// and both the 128-bit staging writes and the 128-bit chunk reads of the walk are conflict-free per quarter wave)
+// and the output tile (rows padded by one word)
 template <int N> constexpr size_t bt_lds_bytes()
 {
     constexpr int PW = wpsi_words_c(N), TS = bt_tile<N>();
-    return sizeof(uint32_t) * (size_t)(PW * 64 * (TS + 1) + 64 * (TS / 2 + 1));
+    return sizeof(uint32_t) * (size_t)(PW * 64 * (TS + 4) + 64 * (TS / 2 + 1));
 }
 
 template <int N>
@@ -489,13 +496,18 @@ __device__ __forceinline__ void backtrace_light_body(const WaveGeom &g, const Wa
     constexpr int XRI = 64 / XW;            // rows per store instruction
     constexpr int CH = PW == 1 ? 8 : 4;     // samples per register chunk
     constexpr int NCH = TS / CH;
-    constexpr int SU = 2;                   // row loads in flight while a tile is staged
-    constexpr int XU = 2;                   // row stores in flight while the output tile leaves
-    static_assert(CH % 2 == 0 && TS % CH == 0, "chunks hold whole int16 pairs");
+    constexpr int TSP = TS + 4;             // tile row stride in words
+    constexpr int LPR = TS / 4;             // lanes per row of a 16-byte load instruction
+    constexpr int RPW = 64 / LPR;           // segment rows per 16-byte load instruction (TS / 4 instructions per plane)
+    constexpr int WU = 4;                   // 16-byte loads in flight while a tile is staged (16 registers, dead in the walk)
+    constexpr int SU = 2;                   // row loads in flight on the dword path (planes off 16 bytes)
+    constexpr int XU = PW == 4 ? 2 : 4;     // row stores in flight while the output tile leaves (four spill at PW = 4)
+    static_assert(CH % 4 == 0 && TS % CH == 0, "chunks are whole 16-byte groups");
+    static_assert(64 % (RPW * WU) == 0, "whole batches of wide loads");
     static_assert(bt_lds_bytes<N>() <= 32 * 1024, "LDS budget");
-    extern __shared__ uint32_t lds_bt[];    // tile[PW][64][TS + 1] | xt[64][XW + 1]
-    uint32_t (*tile)[64][TS + 1] = reinterpret_cast<uint32_t (*)[64][TS + 1]>(lds_bt);
-    uint32_t (*xt)[XW + 1] = reinterpret_cast<uint32_t (*)[XW + 1]>(lds_bt + PW * 64 * (TS + 1));
+    extern __shared__ __align__(16) uint32_t lds_bt[];    // tile[PW][64][TS + 4] | xt[64][XW + 1]
+    uint32_t (*tile)[64][TSP] = reinterpret_cast<uint32_t (*)[64][TSP]>(lds_bt);
+    uint32_t (*xt)[XW + 1] = reinterpret_cast<uint32_t (*)[XW + 1]>(lds_bt + PW * 64 * TSP);
     const int lane = threadIdx.x, ch = blockIdx.y;
     const int L = g.L, Bb = g.Bb, Hb = g.Hb;
     const int64_t T = g.T;
@@ -529,7 +541,10 @@ __device__ __forceinline__ void backtrace_light_body(const WaveGeom &g, const Wa
 #pragma unroll
             for (int w = 0; w < PW; w++)
 #pragma unroll
-                for (int i = 0; i < CH; i++) rowv[w][i] = tile[w][lane][k * CH + i];
+                for (int i = 0; i < CH; i += 4) {
+                    const uint4 t4 = *reinterpret_cast<const uint4 *>(&tile[w][lane][k * CH + i]);
+                    rowv[w][i] = t4.x; rowv[w][i + 1] = t4.y; rowv[w][i + 2] = t4.z; rowv[w][i + 3] = t4.w;
+                }
 #pragma unroll
             for (int i = CH - 1; i >= 0; i--) {
                 const int u = TS * q + k * CH + i;
@@ -573,21 +588,57 @@ __device__ __forceinline__ void backtrace_light_body(const WaveGeom &g, const Wa
     };
     const int nq = (Bb + Hb) / TS;
     for (int q = nq - 1; q >= 0; q--) {
-        // stage psi rows: row r = segment sg0 + r, samples s_lo(r) + TS q + lc.  Wave-uniform tile origin +
-        // 32-bit lane offsets; rows that do not exist read the origin and are staged as zeros.
+        // stage psi rows: row r = segment sg0 + r, samples s_lo(r) + TS q + (0..TS-1).  Wave-uniform tile origin +
+        // 32-bit lane offsets; rows that do not exist read the origin and are staged as zeros.  A plane that starts
+        // on 16 bytes (rows start at multiples of 64 samples from it) comes in with 16-byte loads, four rows of 64
+        // samples per instruction and WU of them in flight; the other planes (T decides where the planes w > 0 and
+        // the channels ch > 0 start) and the one group of four samples that T cuts take the dword path.
         {
-            const int64_t tb = sg0 * Bb + (int64_t)TS * q;
-            const uint32_t *base = pc + (tb < T ? tb : 0);
+            const int64_t tb = sg0 * Bb + (int64_t)TS * q, left = T - tb;
+            const int nrow = g.nseg - sg0 < 64 ? (int)(g.nseg - sg0) : 64;                  // rows that exist
+            const int lim = left < 0 ? 0 : (left < (int64_t)64 * Bb ? (int)left : 64 * Bb);   // offsets below it are data
+#pragma unroll
+            for (int w = 0; w < PW; w++) {
+                const uint32_t *pw = pc + w * planePsi;
+                if (T >= 4 && (reinterpret_cast<uintptr_t>(pw) & 15) == 0) {   // wave-uniform
+                    const uint32_t *base = pw + (lim >= 4 ? tb : 0);          // no whole group in the tile: all read pw[0..3]
+                    const int wr = lane / LPR, wc = 4 * (lane % LPR);
+#pragma unroll 1
+                    for (int r0 = 0; r0 < 64; r0 += RPW * WU) {
+                        uint4 v[WU];
+#pragma unroll
+                        for (int j = 0; j < WU; j++) {
+                            const int r = r0 + j * RPW + wr, o = r * Bb + wc;
+                            const bool ok = r < nrow && o + 4 <= lim;
+                            v[j] = *reinterpret_cast<const uint4 *>(base + (ok ? (uint32_t)o : 0u));
+                        }
+#pragma unroll
+                        for (int j = 0; j < WU; j++) {
+                            const int r = r0 + j * RPW + wr, o = r * Bb + wc;
+                            const bool ok = r < nrow && o + 4 <= lim;
+                            *reinterpret_cast<uint4 *>(&tile[w][r][wc]) = ok ? v[j] : make_uint4(0u, 0u, 0u, 0u);
+                        }
+                    }
+                    // the group T cuts (staged as zeros above) starts at offset lim & ~3; the lane whose row holds
+                    // it in this tile, if there is one, brings in its one to three samples
+                    if (left < (int64_t)64 * Bb && (lim & 3)) {
+                        const int c0 = (lim & ~3) - lane * Bb;
+                        if (c0 >= 0 && c0 < TS) {
+#pragma unroll
+                            for (int j = 0; j < 3; j++)
+                                if (j < (lim & 3)) tile[w][lane][c0 + j] = pw[tb + (lim & ~3) + j];
+                        }
+                    }
+                } else {
+                    const uint32_t *base = pw + (lim > 0 ? tb : 0);
 #pragma unroll SU
-            for (int rr = 0; rr < 64; rr += RPI) {
-                const int r = rr + lr;
-                const bool ok = (sg0 + r) < g.nseg && tb + (int64_t)r * Bb + lc < T;
-                const uint32_t off = ok ? (uint32_t)(r * Bb + lc) : 0u;
-                uint32_t v[PW];
-#pragma unroll
-                for (int w = 0; w < PW; w++) v[w] = (base + w * planePsi)[off];
-#pragma unroll
-                for (int w = 0; w < PW; w++) tile[w][r][lc] = ok ? v[w] : 0u;
+                    for (int rr = 0; rr < 64; rr += RPI) {
+                        const int r = rr + lr, o = r * Bb + lc;
+                        const bool ok = r < nrow && o < lim;
+                        const uint32_t v = base[ok ? (uint32_t)o : 0u];
+                        tile[w][r][lc] = ok ? v : 0u;
+                    }
+                }
             }
         }
         __syncthreads();
@@ -619,7 +670,7 @@ __device__ __forceinline__ void backtrace_light_body(const WaveGeom &g, const Wa
         }
         __syncthreads();
     }
-    if (active && hi_rel < te_rel) bstate[(int64_t)ch * g.nseg + sg] = bs;
+    if (active && hi_rel < te_rel) (bstate + ((int64_t)ch * g.nseg + sg0))[lane] = bs;   // wave-uniform base: sg is not kept
     for (int o = 32; o > 0; o >>= 1) nflag += __shfl_xor(nflag, o);
     if (lane == 0 && nflag) atomicAdd((unsigned long long *)&tie_cnt[ch * 8 + kTieTrig], (unsigned long long)nflag);
 }
