@@ -10,7 +10,7 @@ from ._lib import (ENGINE_AUTO, ENGINE_BLOCKED, ENGINE_RING, ENGINE_STRICT, ENGI
 from .api import (HMMSpikeTemplateModel, HMMSpikingModel, Posteriors, StateMatrix, backward, extract_spiketimes,
                   fit, fit_channels, forward,
                   posterior_decode, posteriors, predict, reconstruct_signal, spike_confidence, train_model, train_step, unroll_mlseq, update,
-                  viterbi)
+                  viterbi, viterbi_step)
 from .device import Plan
 from .postprocess import (condense_candidates, condense_templates, find_best_overlap, match_templates,
                           prune_templates, remove_small, remove_sparse)
@@ -23,4 +23,5 @@ __all__ = ["StateMatrix", "HMMSpikeTemplateModel", "HMMSpikingModel", "forward",
            "set_option", "get_option", "shutdown", "device_count", "ENGINE_AUTO", "ENGINE_STRICT",
            "ENGINE_RING", "ENGINE_BLOCKED", "ENGINE_WAVE", "get_lp", "sort_data", "find_best_overlap",
            "condense_candidates", "condense_templates", "remove_sparse", "remove_small", "prune_templates",
-           "match_templates", "Posteriors", "posteriors", "posterior_decode", "spike_confidence"]
+           "match_templates", "Posteriors", "posteriors", "posterior_decode", "spike_confidence",
+           "viterbi_step"]

@@ -69,6 +69,8 @@ SIGNATURES = {
                               _vp, _vp, _i64, _pi64, _vp]),
     "hmmsort_em_step": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _f64, _vp, _vp,
                                _i64, _pi64, _vp]),
+    "hmmsort_viterbi_step": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _f64, _vp, _vp,
+                                    _i64, _pi64, _vp, _vp, _vp]),
     "hmmsort_reconstruct": (_int, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp]),
     "hmmsort_unroll_mlseq": (_int, [_vp, _i64, _vp, _i64, _i64, _vp]),
     "hmmsort_extract_spiketimes": (_int, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
@@ -91,6 +93,7 @@ SIGNATURES = {
     "hmmsort_plan_set_shard": (_int, [_vp, _i64, _i64, _int, _int]),
     "hmmsort_plan_mstep": (_int, [_vp, _vp, _vp, _vp]),
     "hmmsort_plan_mstep_len": (_i64, [_vp]),
+    "hmmsort_plan_path_update": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "hmmsort_plan_diagnostics": (_int, [_vp, _vp, _pi64]),
     "hmmsort_plan_tie_stats": (_int, [_vp, _vp, _pi64]),
     "hmmsort_plan_extract_spiketimes": (_int, [_vp, _vp, _vp, _i64, _vp, _vp]),

@@ -13,7 +13,8 @@ Reference methods mirrored (file:line relative to the reference root):
   reconstruct_signal                                                  src/reconstruction.jl:1
   unroll_mlseq                                                        src/extraction.jl:4
   fit(HMMSpikingModel, templates, X, chunksize)                       src/fit.jl:11-42
-Extensions (no counterpart in the reference): posteriors, posterior_decode, spike_confidence.
+Extensions (no counterpart in the reference): posteriors, posterior_decode, spike_confidence, viterbi_step and
+train_model(..., method="viterbi").
 """
 import ctypes as C
 from dataclasses import dataclass
@@ -199,16 +200,83 @@ def train_step(X, state_matrix, mu0, sigma0, verbose=0):
     return _finish_step(state_matrix, mu_f, sig, lp, nlp, pp)
 
 
+def viterbi_step(X, state_matrix, mu, sigma, return_path=False):
+    """One step of Viterbi training (hard EM): decode X with the model, then re-estimate the model from the decoded
+    path -- update() of baumwelch.jl:205-309 with gamma and xi the indicators of that path.  One C-ABI call
+    (hmmsort_viterbi_step); signal and path stay on the GPU between the two halves.  Returns
+    (state_matrix', mu', sigma'), plus the path and its log-likelihood under the OLD model with `return_path`.
+    A template row no sample visits keeps its value; an entry transition the path never takes gets -Inf and
+    leaves the new list (types.jl:121).  `mu` is updated in place like train_step's."""
+    X = _signal(X)
+    keep, margs = _model_args(state_matrix, mu, sigma)
+    st, tr, mu_f = keep
+    mu_f = np.array(mu_f, dtype=np.float64, order="F", copy=True) if mu_f is mu else mu_f
+    sig = C.c_double(0.0)
+    nlp = C.c_int64(0)
+    lp = np.zeros(len(tr), dtype=np.float64)
+    pp = np.zeros(state_matrix.nstates, dtype=np.float64)
+    x = np.zeros(len(X), dtype=np.int16) if return_path else None
+    ll = C.c_double(0.0)
+    check(lib().hmmsort_viterbi_step(ptr(X), len(X), ptr(st), state_matrix.N, state_matrix.K,
+                                     state_matrix.nstates, ptr(tr), len(tr), ptr(mu_f), float(sigma),
+                                     C.cast(C.byref(sig), C.c_void_p), ptr(lp), len(lp), C.byref(nlp), ptr(pp),
+                                     ptr(x), C.cast(C.byref(ll), C.c_void_p) if return_path else None))
+    if isinstance(mu, np.ndarray) and mu.shape == mu_f.shape and mu.dtype == np.float64:
+        mu[...] = mu_f
+    out = _finish_step(state_matrix, mu_f, sig, lp, nlp, pp)
+    return out + (x, ll.value) if return_path else out
+
+
 class _EMSession:
     """EM steps on one signal that stays in HBM: the signal is uploaded once and one plan is
     re-armed with hmmsort_plan_set_model between steps (ring-engine models; anything else, a
-    changed model shape or a failed warm-up certificate goes through train_step, which escalates)."""
+    changed model shape or a failed warm-up certificate goes through train_step, which escalates).
+    With `hard` every step is a Viterbi-training step (plan.viterbi + plan.path_update) and the signal
+    stays resident for every engine; a failed boundary certificate or an open near-tie goes through
+    viterbi_step, which escalates."""
 
-    def __init__(self, X):
+    def __init__(self, X, hard=False):
         self.X = X
         self.dX = None
         self.plan = None
         self.key = None
+        self.hard = hard
+
+    def _hard_step(self, lA, mu, sigma):
+        import torch
+        from . import _lib
+        from .device import Plan
+        key = (lA.N, lA.K, lA.nstates, len(lA.transitions), lA.resolve_overlaps)
+        try:
+            if self.key != key or self.plan is None:
+                self.close()
+                self.key = key
+                self.plan = Plan(len(self.X), lA, mu, sigma)
+            else:
+                self.plan.set_model(lA, mu, sigma)
+        except _lib.HmmsortError:
+            self.close()
+            self.key = None
+            return viterbi_step(self.X, lA, mu, sigma)
+        if self.dX is None:
+            self.dX = torch.from_numpy(self.X).cuda()
+            self.dx = torch.zeros(len(self.X), dtype=torch.int16, device="cuda")
+            self.dll = torch.zeros(1, dtype=torch.float64, device="cuda")
+        out = torch.zeros(self.plan.mstep_len(), dtype=torch.float64, device="cuda")
+        self.plan.viterbi(self.dX, self.dx, self.dll)
+        self.plan.path_update(self.dX, self.dx, out)
+        d = self.plan.diagnostics()
+        if d[0] != 0 or (self.plan.info()["engine"] in (_lib.ENGINE_BLOCKED, _lib.ENGINE_WAVE) and d[7] != 0):
+            return viterbi_step(self.X, lA, mu, sigma)
+        o = out.cpu().numpy()
+        K, N, S = lA.K, lA.N, lA.nstates
+        nlp = len(o) - K * N - 1 - S
+        mu_n = np.asfortranarray(o[:K * N].reshape((K, N), order="F"))
+        if isinstance(mu, np.ndarray) and mu.shape == mu_n.shape and mu.dtype == np.float64:
+            mu[...] = mu_n
+        lA_n = StateMatrix.from_states(lA.states, o[K * N + 1 + nlp:], K, o[K * N + 1:K * N + 1 + nlp].copy(),
+                                       lA.resolve_overlaps)
+        return lA_n, mu_n, float(o[K * N])
 
     def close(self):
         if self.plan is not None:
@@ -216,6 +284,8 @@ class _EMSession:
             self.plan = None
 
     def step(self, lA, mu, sigma, verbose=0):
+        if self.hard:
+            return self._hard_step(lA, mu, sigma)
         import torch
         from . import _lib
         from .device import Plan
@@ -252,7 +322,8 @@ class _EMSession:
         return lA_n, mu_n, float(o[K * N])
 
 
-def train_model(X, *args, callback=None, verbose=0, p0=None, rng=None, postprocess="reference"):
+def train_model(X, *args, callback=None, verbose=0, p0=None, rng=None, postprocess="reference",
+                method="baum-welch"):
     """The three `train_model` methods of baumwelch.jl:
 
       train_model(X, state_matrix, mu0, sigma0)                  one EM step         :362-370
@@ -265,16 +336,25 @@ def train_model(X, *args, callback=None, verbose=0, p0=None, rng=None, postproce
     baumwelch.jl:340-349): `postprocess="reference"` (default) runs the restatement in postprocess.py,
     `None` skips the stage, a callable `postprocess(state_matrix, mu, sigma) -> (state_matrix, mu)`
     replaces it.
+
+    `method="viterbi"` (an extension; the default "baum-welch" is the reference's loop) makes every step a step of
+    Viterbi training (viterbi_step): the loop, the callbacks and the stage between the rounds are the same.  It
+    refines a model and does not find one, so the random-start form refuses it.
     """
+    if method not in ("baum-welch", "viterbi"):
+        raise ValueError("train_model: method must be \"baum-welch\" or \"viterbi\", got %r" % (method,))
+    hard = method == "viterbi"
     X = _signal(X)
     if len(args) >= 1 and isinstance(args[0], StateMatrix):
         state_matrix, mu, sigma = args[0], args[1], float(args[2])
         if len(args) == 3:
+            if hard:
+                return viterbi_step(X, state_matrix, mu, sigma)
             return train_step(X, state_matrix, mu, sigma, verbose=verbose)
         nsteps = int(args[3])
         cb = args[4] if len(args) > 4 else callback
         mu = np.array(mu, dtype=np.float64, order="F", copy=True)
-        em = _EMSession(X)
+        em = _EMSession(X, hard)
         try:
             for _ in range(nsteps):
                 if cb is not None:
@@ -295,6 +375,10 @@ def train_model(X, *args, callback=None, verbose=0, p0=None, rng=None, postproce
             em.close()
         return state_matrix, mu, sigma
     # random initialisation, baumwelch.jl:311-322
+    if hard:
+        raise ValueError("train_model: method=\"viterbi\" needs a model to refine.  From the random start "
+                         "(p0 = 2^(-3K/2)) the decoded path holds no spike, so every template would lose its "
+                         "entry transition on the first step; start from templates, or run Baum-Welch first")
     N = int(args[0]) if len(args) > 0 else 3
     K = int(args[1]) if len(args) > 1 else 60
     resolve_overlaps = bool(args[2]) if len(args) > 2 else False

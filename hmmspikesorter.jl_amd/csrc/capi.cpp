@@ -224,6 +224,7 @@ static int plan_set_model(const char *who, hmmsort_plan *p, int64_t channel, con
     if ((rc = p->eng->set_model(channel, m))) return rc;
     if (!p->models.empty()) p->models[channel] = m;
     if (channel == 0) p->model = std::move(m);
+    p->pu_stale = true;
     return HMMSORT_OK;
 }
 
@@ -298,7 +299,9 @@ int hmmsort_plan_decode_estep(hmmsort_plan *p, const double *d_y, int16_t *d_x, 
 int hmmsort_plan_set_shard(hmmsort_plan *p, int64_t own_lo, int64_t own_hi, int first, int last)
 {
     HS_CHECK(p, HMMSORT_EINVAL, "plan_set_shard: null plan");
-    return p->eng->set_shard(own_lo, own_hi, first != 0, last != 0);
+    int rc = p->eng->set_shard(own_lo, own_hi, first != 0, last != 0);
+    if (rc == HMMSORT_OK) p->sharded = !(own_lo == 0 && own_hi == p->T && first && last);
+    return rc;
 }
 
 int64_t hmmsort_plan_stats_len(const hmmsort_plan *p) { return p ? p->eng->stats_len() : 0; }
@@ -323,6 +326,16 @@ int hmmsort_plan_mstep(hmmsort_plan *p, const double *d_stats, double *d_out, vo
 {
     HS_CHECK(p && d_stats && d_out, HMMSORT_EINVAL, "plan_mstep: null argument");
     return p->eng->mstep(d_stats, d_out, (hipStream_t)stream);
+}
+
+int hmmsort_plan_path_update(hmmsort_plan *p, const double *d_y, const int16_t *d_x, double *d_out,
+                             int64_t *d_counts, void *stream)
+{
+    HS_CHECK(p && d_y && d_x && d_out, HMMSORT_EINVAL, "plan_path_update: null argument");
+    // sigma' needs the means of the whole recording: there is no additive statistics vector to all-reduce
+    HS_CHECK(!p->sharded, HMMSORT_EINVAL, "plan_path_update: the plan is a time shard (hmmsort_plan_set_shard); the "
+                                          "update needs the whole recording");
+    return plan_path_update(p, d_y, d_x, d_out, d_counts, (hipStream_t)stream);
 }
 
 int hmmsort_plan_diagnostics(hmmsort_plan *p, void *stream, int64_t diag[8])

@@ -247,6 +247,7 @@ int generic_engine_create(std::unique_ptr<Engine> *out, const HostModel &m, int6
 // ---- device engines ------------------------------------------------------------------------
 struct GenericDev;  // generic_engine.hip
 struct RingDev;     // ring_engine.hip
+struct PathUpdateDev;  // path_update.hip
 
 // generic (strict) engine: single sequential sweep in the reference's operation order
 // blocked = time-parallel Viterbi over blocks with a certified warm-up (generic_blocked.hip)
@@ -326,6 +327,11 @@ struct hmmsort_plan {
     int64_t T = 0;
     int64_t C = 1;                            // channels (batched wave plans)
     std::unique_ptr<hmmsort::Engine> eng;     // its id is the engine the plan runs on
+    bool sharded = false;                     // hmmsort_plan_set_shard left the plan with part of a recording
+    // path update (path_update.hip): lookup tables of the current model(s) and workspace, made when first needed;
+    // stale after hmmsort_plan_set_model
+    std::shared_ptr<hmmsort::PathUpdateDev> pu;
+    bool pu_stale = true;
 };
 
 namespace hmmsort {
@@ -338,5 +344,9 @@ struct PlanGuard {
     hmmsort_plan *p = nullptr;
     ~PlanGuard() { if (p) hmmsort_plan_destroy(p); }
 };
+// the model re-estimated from the path d_x of d_y (path_update.hip): d_out as hmmsort_plan_mstep writes it, d_counts
+// three device int64 per channel or null; enqueued on st
+int plan_path_update(hmmsort_plan *p, const double *d_y, const int16_t *d_x, double *d_out, int64_t *d_counts,
+                     hipStream_t st);
 void host_slots_trim(size_t keep);   // idle plans of the host-buffer entry points: keep the newest `keep`
 }  // namespace hmmsort

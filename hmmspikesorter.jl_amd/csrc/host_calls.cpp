@@ -813,6 +813,37 @@ int hmmsort_em_step(const double *y, int64_t T, const int16_t *states, int64_t N
         });
 }
 
+// hmmsort_viterbi, then the model re-estimated from the path while signal and path are still in device memory.  The
+// update runs once, in the `out` stage, on whatever path the ladder finally returned.
+int hmmsort_viterbi_step(const double *y, int64_t T, const int16_t *states, int64_t N, int64_t K, int64_t S,
+                         const hmm_trans *tr, int64_t R, double *mu_inout, double sigma, double *sigma_out,
+                         double *lp_out, int64_t lp_cap, int64_t *n_lp_out, double *pp_out, int16_t *x_out,
+                         double *ll_out)
+{
+    HS_CHECK(y && mu_inout && sigma_out && lp_out, HMMSORT_EINVAL, "viterbi_step: null argument");
+    HS_CHECK(T >= 1, HMMSORT_EINVAL, "viterbi_step: empty signal (T = %lld)", (long long)T);
+    return host_call(
+        kViterbi, y, HMMSORT_SAMPLES_F64, T, {states, N, K, S, tr, R, mu_inout, sigma},
+        [&](HostSlot &h) {
+            int rc;
+            if ((rc = h.dx.ensure(T * sizeof(int16_t))) || (rc = h.dll.ensure(sizeof(double)))) return rc;
+            return h.plan->eng->viterbi(h.dy.as<double>(), h.dx.as<int16_t>(), h.dll.as<double>(), h.st);
+        },
+        [&](HostSlot &h) {
+            int rc;
+            // sized for THIS plan, as in em_step
+            if ((rc = h.dout.ensure(hmmsort_plan_mstep_len(h.plan) * sizeof(double)))) return rc;
+            if ((rc = hmmsort_plan_path_update(h.plan, h.dy.as<double>(), h.dx.as<int16_t>(), h.dout.as<double>(),
+                                               nullptr, h.st)))
+                return rc;
+            if (x_out) HS_HIP(hipMemcpyAsync(x_out, h.dx.p, T * sizeof(int16_t), hipMemcpyDeviceToHost, h.st));
+            if (ll_out) HS_HIP(hipMemcpyAsync(ll_out, h.dll.p, sizeof(double), hipMemcpyDeviceToHost, h.st));
+            HS_HIP(hipStreamSynchronize(h.st));
+            return unpack_mstep(h.dout.as<double>(), K, N, S, h.plan->eng->n_lp(), mu_inout, sigma_out, lp_out,
+                                lp_cap, n_lp_out, pp_out);
+        });
+}
+
 int hmmsort_posteriors(const double *y, int64_t T, const int16_t *states, int64_t N, int64_t K, int64_t S,
                        const hmm_trans *tr, int64_t R, const double *mu, double sigma, double *onset, double *occ,
                        double *silent, int16_t *xm, double *logz)

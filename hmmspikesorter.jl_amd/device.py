@@ -125,6 +125,13 @@ class Plan:
     def mstep(self, d_stats, d_out, stream=0):
         check(lib().hmmsort_plan_mstep(self._h, _dptr(d_stats), _dptr(d_out), C.c_void_p(stream)))
 
+    def path_update(self, d_y, d_x, out, counts=None, stream=0):
+        """Viterbi training: the model re-estimated from the path d_x of d_y (hmmsort_plan_path_update), device to
+        device.  `out`: mstep_len() doubles per channel in mstep's layout; `counts`: three int64 per channel
+        (ids outside 1..S, pairs that are no transition of the list, template rows that kept their mean) or None."""
+        check(lib().hmmsort_plan_path_update(self._h, _dptr(d_y), _dptr(d_x), _dptr(out), _dptr(counts),
+                                             C.c_void_p(stream)))
+
     def diagnostics(self, stream=0):
         d = (C.c_int64 * 8)()
         check(lib().hmmsort_plan_diagnostics(self._h, C.c_void_p(stream), d))

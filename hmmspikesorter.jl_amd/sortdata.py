@@ -71,7 +71,7 @@ def _chunk_confidence(templates, dataf, ml_seq, chunksize, jitter):
 
 
 def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_templates=4,
-              chunksize=100_000, confidence=False, jitter=2):
+              chunksize=100_000, confidence=False, jitter=2, refine_steps=0):
     """sort_data(inputfile, datafile, outputfile; dosave, max_templates)   hmmsort.jl:36-104.
 
     Returns the reference's output dictionary; {} when there are more templates than
@@ -86,7 +86,12 @@ def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_temp
     blocked sweep instead (no S x chunksize array; 2 x 60 at the default chunksize is routine).  Larger models
     -- 3 x 60 and 4 x 60, 10 621 and 21 123 states -- take the same sweep with its state columns in device
     memory when option "blocked_hbm_columns" is 1 as well, at the default chunksize; with that option off (the
-    default) they still take the strict path."""
+    default) they still take the strict path.
+
+    `refine_steps=n` (an extension; default 0, output unchanged) runs n steps of Viterbi training
+    (api.viterbi_step) of the overlap model on the channel before the chunked decode: the templates, their entry
+    probabilities and sigma are re-estimated from the spikes the model itself sorts, the decode uses the refined
+    model, and "waveforms", "lp" and "sigma" in the output are the refined ones."""
     spike_forms = np.asarray(spike_forms, dtype=np.float64)
     nstates, _nchannels, ntemplates = spike_forms.shape
     pp = np.atleast_1d(np.asarray(p, dtype=np.float64))
@@ -102,6 +107,17 @@ def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_temp
         data = data[:, 0]                                                      # view(data, :, 1) :80
     # :84-88 converts to Float64 on the host; int16 samples are handed over as they are and widened in HBM
     dataf = np.ascontiguousarray(data) if data.dtype == np.int16 else np.ascontiguousarray(data, dtype=np.float64)
+    if refine_steps > 0:
+        # raw int16 samples are widened for the refinement only; the decode below still takes them as they are
+        em = api._EMSession(np.ascontiguousarray(dataf, dtype=np.float64), hard=True)
+        mu_r = np.array(templates.mu, dtype=np.float64, order="F", copy=True)
+        try:
+            for _ in range(int(refine_steps)):
+                sm, mu_r, sigma = em.step(sm, mu_r, sigma)
+        finally:
+            em.close()
+        templates = api.HMMSpikeTemplateModel(sm, mu_r, sigma)
+        lp, _ii = get_lp(sm)
     modelf = api.fit(templates, dataf, chunksize)                              # :90
     mlseq = api.unroll_mlseq(modelf.ml_seq, sm)                                # :92
     out = {"mlseq": mlseq, "ll": modelf.ll, "waveforms": templates.mu, "lp": lp, "sigma": sigma}

@@ -211,6 +211,16 @@ int hmmsort_em_step(const double *y, int64_t T, const int16_t *states, int64_t N
                     double *sigma_out, double *lp_out, int64_t lp_cap, int64_t *n_lp_out,
                     double *pp_out);
 
+/* One step of Viterbi training: hmmsort_viterbi, then hmmsort_plan_path_update on the signal and path that are
+ * already in device memory.  Argument conventions of hmmsort_em_step (mu_inout rewritten in place, n_lp_out,
+ * lp_cap too small: HMMSORT_EINVAL); same plan cache and escalation ladder as hmmsort_viterbi, the update runs on
+ * whatever path the ladder finally returned, and "last_escalations" means what it means there.  x_out (T) and
+ * ll_out receive the decode of the OLD model; either may be NULL.  No counterpart in the reference. */
+int hmmsort_viterbi_step(const double *y, int64_t T, const int16_t *states, int64_t N, int64_t K, int64_t S,
+                         const hmm_trans *tr, int64_t R, double *mu_inout, double sigma, double *sigma_out,
+                         double *lp_out, int64_t lp_cap, int64_t *n_lp_out, double *pp_out,
+                         int16_t *x_out /* may be NULL */, double *ll_out /* may be NULL */);
+
 /* reconstruct_signal(x, lA, mu, sigma) -> Y2 (sigma is ignored)    reconstruction.jl:1-10 */
 int hmmsort_reconstruct(const int16_t *x, int64_t T, const int16_t *states, int64_t N,
                         int64_t S, const double *mu, int64_t K, double *y_out);
@@ -308,6 +318,22 @@ int hmmsort_plan_set_shard(hmmsort_plan *plan, int64_t own_lo, int64_t own_hi, i
  * (overlap models) take the same three calls estep / all-reduce / mstep; their statistics vector is
  * [G0 (S) | G1 (S) | X | Gamma0 | sum y^2]. */
 int hmmsort_plan_mstep(hmmsort_plan *plan, const double *d_stats, double *d_out, void *stream);
+/* Viterbi training (hard EM; INTEGRATION.md "Viterbi training"): the model re-estimated from a path
+ * d_x of d_y, normally the one hmmsort_plan_viterbi just wrote.  It is update() (baumwelch.jl:205-309) with gamma
+ * and xi the indicators of the path: mu'[k,l] = mean of y over the samples whose state has template l alone active,
+ * at phase k (samples in states with two or more active templates do not enter mu, baumwelch.jl:269-287; a row
+ * (k,l) no sample visits keeps the plan's current value instead of 0/0); sigma' = sqrt(mean (y - _mu'[x])^2) with
+ * the NEW means, over all states; lp'_i = log(#(1 -> dst_i)) - log(#(x_t = 1, t < T-1)) for the transitions out of
+ * state 1 but the first, -Inf for a count of 0; pp' = 0 at x_0, -Inf elsewhere.  d_out per channel is
+ * hmmsort_plan_mstep_len() doubles in hmmsort_plan_mstep's layout.  d_counts (may be NULL) receives three device
+ * int64 per channel: [0] samples with an id outside 1..S (skipped everywhere), [1] pairs (x_t, x_t+1) that are no
+ * transition of the list -- the path is then not one of this model and d_out is unspecified, though the call stays
+ * inside its buffers and finishes --, [2] rows (k,l) that kept their mean.  Any plan (wave, ring, blocked, strict,
+ * batched: channel-major buffers); a time shard (hmmsort_plan_set_shard with anything but the whole recording):
+ * HMMSORT_EINVAL, because sigma' needs the means of the whole recording.  No floating-point atomics: the same
+ * inputs give the same bits.  Asynchronous on `stream`. */
+int hmmsort_plan_path_update(hmmsort_plan *plan, const double *d_y, const int16_t *d_x, double *d_out,
+                             int64_t *d_counts, void *stream);
 /* doubles hmmsort_plan_mstep writes PER CHANNEL: K*N + 1 + n_lp + S, n_lp = N for wave/ring plans (also when
  * the list has lost a vanished template's entry transitions, types.jl:121: its slot stays, value -Inf or the
  * re-estimate), (#transitions leaving state 1) - 1 for the blocked engine (baumwelch.jl:226,264). */

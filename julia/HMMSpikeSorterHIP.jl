@@ -139,6 +139,29 @@ function train_model(X::Array{Float64,1}, state_matrix::StateMatrix, μ0::Array{
     _finish(state_matrix, μ0, σnew, lp, nlp, pp)
 end
 
+"""
+    viterbi_step(X, state_matrix, μ0, σ0; return_path=false) -> (state_matrix′, μ′, σ′[, x, ll])
+
+One step of Viterbi training (hard EM; an extension, INTEGRATION.md "Viterbi training"): decode `X`, then
+re-estimate the model from the decoded path -- `update` with γ and ξ the indicators of that path.  One call;
+signal and path stay on the GPU between the two halves.  `μ0` is overwritten in place like `train_model`'s.
+It refines a model (templates from a spike sorter, or after Baum-Welch); from a random start the decode holds no
+spike and every template would lose its entry transition.
+"""
+function viterbi_step(X::Array{Float64,1}, state_matrix::StateMatrix, μ0::Array{Float64,2}, σ0::Float64; return_path=false)
+    σnew = Ref{Float64}(0.0); nlp = Ref{Int64}(0); ll = Ref{Float64}(0.0)
+    lp = zeros(length(state_matrix.transitions)); pp = zeros(state_matrix.nstates)
+    x = zeros(Int16, return_path ? length(X) : 0)
+    check(ccall((:hmmsort_viterbi_step, lib), Cint,
+        (Ptr{Float64}, Int64, Ptr{Int16}, Int64, Int64, Int64, Ptr{Cvoid}, Int64, Ptr{Float64}, Float64,
+         Ref{Float64}, Ptr{Float64}, Int64, Ref{Int64}, Ptr{Float64}, Ptr{Int16}, Ref{Float64}),
+        X, length(X), state_matrix.states, state_matrix.N, state_matrix.K, state_matrix.nstates,
+        state_matrix.transitions, length(state_matrix.transitions), μ0, σ0, σnew, lp, length(lp), nlp, pp,
+        return_path ? pointer(x) : Ptr{Int16}(C_NULL), ll))
+    out = _finish(state_matrix, μ0, σnew, lp, nlp, pp)
+    return_path ? (out..., x, ll[]) : out
+end
+
 function reconstruct_signal(x::Array{T,1}, lA::StateMatrix, μ::Array{Float64,2}, σ::Float64) where T <: Integer
     xs = T === Int16 ? x : Int16.(x)
     Y2 = zeros(Float64, length(xs))
