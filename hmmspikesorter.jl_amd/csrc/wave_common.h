@@ -70,7 +70,9 @@ struct WaveDev {
     std::vector<char> ucx;            // per channel
     const double *bound_y = nullptr;
     hipStream_t side = nullptr, side2 = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_a = nullptr, ev_b = nullptr, ev_c = nullptr;
+    // ev_fork / ev_join: s -> side2 -> s (fused call); ev_a / ev_c: s -> side -> s (certificate);
+    // ev_x / ev_b: side2 -> s where the fused call runs ll beside the resolver: x stitched / the resolver done
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_a = nullptr, ev_b = nullptr, ev_c = nullptr, ev_x = nullptr;
     std::vector<ProfEntry> prof;
     int64_t S = 0, K = 0;
     std::vector<RingModel> ring;      // per channel
@@ -418,8 +420,11 @@ int wave_profile_read(WaveDev *r, hipStream_t st, std::vector<std::string> &name
                       std::vector<double> &ms, std::vector<int64_t> &calls);
 // wave_viterbi.hip
 int wave_viterbi_sweep(WaveDev *r, const double *d_y, hipStream_t st);
-// beside: the decode runs next to an E-step's sweeps (decides the backtrace form under option "backtrace" = 0)
-int wave_viterbi_post(WaveDev *r, const double *d_y, int16_t *d_x, double *d_ll, hipStream_t st, bool beside);
+// beside: the decode runs next to an E-step's sweeps (decides the backtrace form under option "backtrace" = 0);
+// ll_beside: the path likelihood runs on ll_st (another stream than st) beside the near-tie resolver; ll_st takes st
+// in behind the resolver and holds the decode's last launches when the function returns.  Otherwise all is on st.
+int wave_viterbi_post(WaveDev *r, const double *d_y, int16_t *d_x, double *d_ll, hipStream_t st, bool beside,
+                      bool ll_beside, hipStream_t ll_st);
 int wave_viterbi(WaveDev *r, const double *d_y, int16_t *d_x, double *d_ll, hipStream_t st);
 // wave_ties.hip
 int wave_tie_resolve(WaveDev *r, const double *d_y, int16_t *d_x, hipStream_t st);

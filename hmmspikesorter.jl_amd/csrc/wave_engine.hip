@@ -318,7 +318,8 @@ int wave_create(WaveDev **out, const std::vector<HostModel> &models, int64_t T, 
         hipEventCreateWithFlags(&r->ev_join, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&r->ev_a, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&r->ev_b, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&r->ev_c, hipEventDisableTiming) != hipSuccess) {
+        hipEventCreateWithFlags(&r->ev_c, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&r->ev_x, hipEventDisableTiming) != hipSuccess) {
         set_error("wave engine: could not create the internal stream/events");
         wave_destroy(r);
         return HMMSORT_EHIP;
@@ -342,6 +343,7 @@ void wave_destroy(WaveDev *r)
     if (r->ev_a) (void)hipEventDestroy(r->ev_a);
     if (r->ev_b) (void)hipEventDestroy(r->ev_b);
     if (r->ev_c) (void)hipEventDestroy(r->ev_c);
+    if (r->ev_x) (void)hipEventDestroy(r->ev_x);
     if (r->side) (void)hipStreamDestroy(r->side);
     if (r->side2) (void)hipStreamDestroy(r->side2);
     for (auto &e : r->prof) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }

@@ -798,8 +798,13 @@ __global__ __launch_bounds__(64) void kw_fb_check(WaveGeom g, double tol, const 
                 dbg[7] = wb; dbg[8] = bi; dbg[9] = tc; dbg[10] = ne;
             }
             if (!(err <= tol)) atomicAdd((unsigned long long *)&diag[3 + 2 * dir], 1ull);
-            if (err == err)
-                atomicMax((unsigned long long *)&diag[4 + 2 * dir], (unsigned long long)__double_as_longlong(err));
+            if (err == err) {
+                // err >= 0, so its bits order like its value.  Most boundaries do not raise the maximum: they read it
+                // and leave (a stale read only costs an atomic that changes nothing).
+                const unsigned long long eb = (unsigned long long)__double_as_longlong(err);
+                if (eb > *reinterpret_cast<volatile unsigned long long *>(&diag[4 + 2 * dir]))
+                    atomicMax((unsigned long long *)&diag[4 + 2 * dir], eb);
+            }
         }
     }
 }
@@ -1094,7 +1099,8 @@ static int wave_lds_attr2(Kern kern, size_t lds)
     return HMMSORT_OK;
 }
 
-static int wave_estep_sweeps(WaveDev *r, const double *d_y, double *d_stats, hipStream_t st)
+// wait_cert = false: the caller orders st behind the certificate (ev_c) itself, after what else it puts on st
+static int wave_estep_sweeps(WaveDev *r, const double *d_y, double *d_stats, hipStream_t st, bool wait_cert = true)
 {
     const WaveGeom &g = r->g;
     const int N = g.N, L = g.L, NL = N * L;
@@ -1203,7 +1209,7 @@ static int wave_estep_sweeps(WaveDev *r, const double *d_y, double *d_stats, hip
     { WPROF(r, "kw_stats_final", st);
       hipLaunchKernelGGL(kw_stats_final, dim3(total, g.C), dim3(64), 0, st, g, rowsG, r->partG, r->partS, d_y, r->Rf,
                          r->virt, r->FA0, r->rho, r->Zc, r->yhead, r->pp, d_stats); }
-    HS_HIP(hipStreamWaitEvent(st, r->ev_c, 0));
+    if (wait_cert) HS_HIP(hipStreamWaitEvent(st, r->ev_c, 0));
     HS_HIP(hipGetLastError());
     return HMMSORT_OK;
 }
@@ -1253,11 +1259,20 @@ int wave_decode_estep(WaveDev *r, const double *d_y, int16_t *d_x, double *d_ll,
         HS_HIP(hipStreamWaitEvent(r->side2, r->ev_fork, 0));
         // the E-step chain is the critical path: its launches are enqueued first (the dozen small launches of the
         // decode would otherwise hold the forward sweep back by their host-side enqueue time, ~0.1 ms)
-        if ((rc = wave_estep_sweeps(r, d_y, d_stats, s))) return rc;
+        if ((rc = wave_estep_sweeps(r, d_y, d_stats, s, false))) return rc;
         if ((rc = wave_viterbi_sweep(r, d_y, r->side2))) return rc;
-        if ((rc = wave_viterbi_post(r, d_y, d_x, d_ll, r->side2, true))) return rc;
-        HS_HIP(hipEventRecord(r->ev_join, r->side2));
-        HS_HIP(hipStreamWaitEvent(s, r->ev_join, 0));
+        // One channel of up to four rings (the backward sweep that sums the statistics itself): the E-step chain and
+        // the decode branch are about equally long and the decode's tail ends the call, so the path likelihood takes
+        // the E-step's own stream behind kw_stats_final, beside the certificate (side) and the near-tie chain
+        // (side2), and the decode branch joins there.  Longer E-step chains (more rings, batched plans) hide the
+        // whole decode branch: there ll stays on side2, where it costs the call nothing.
+        const bool ll_trunk = r->g.C == 1 && r->g.N <= 4;
+        if ((rc = wave_viterbi_post(r, d_y, d_x, d_ll, r->side2, true, ll_trunk, s))) return rc;
+        if (!ll_trunk) {
+            HS_HIP(hipEventRecord(r->ev_join, r->side2));
+            HS_HIP(hipStreamWaitEvent(s, r->ev_join, 0));
+        }
+        HS_HIP(hipStreamWaitEvent(s, r->ev_c, 0));
         return HMMSORT_OK;
     });
 }

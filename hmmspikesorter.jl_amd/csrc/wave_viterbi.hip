@@ -1024,13 +1024,18 @@ __global__ __launch_bounds__(256) void kw_stitch_fix(WaveGeom g, const WaveConst
 
 // ll = sum_{t=1..T-1} T1[x_t, t]  (viterbi.jl:92-96) without the trellis:
 //   T1[x_t,t] = T1[x_0,0] + sum_{u=1..t} inc_u  =>  ll = (T-1) T1[x_0,0] + sum_u (T-u) inc_u.
+// Launched twice per decode (wave_viterbi_post): once beside the near-tie resolver (redo_cnt = nullptr), and once
+// behind it with redo_cnt = the tie counters, where a channel's workgroups return at once unless the resolver
+// rewrote that channel's x; then they compute the same partials again from the final path.
 __global__ __launch_bounds__(256) void kw_ll_partial(WaveGeom g, const WaveConst *__restrict__ cst,
                                                      const double *__restrict__ y, const int16_t *__restrict__ x,
                                                      const double *__restrict__ mean,
-                                                     const double *__restrict__ ctab_all, double *__restrict__ part)
+                                                     const double *__restrict__ ctab_all, double *__restrict__ part,
+                                                     const int64_t *__restrict__ redo_cnt)
 {
     __shared__ double red[4];
     const int ch = blockIdx.y, N = g.N, L = g.L, S = 1 + N * L;
+    if (redo_cnt && redo_cnt[ch * 8 + kTieFlips] == 0) return;   // block-uniform
     const int64_t T = g.T;
     const double *yc = y + (int64_t)ch * T, *mc = mean + (int64_t)ch * S;
     const int16_t *xc = x + (int64_t)ch * T;
@@ -1098,9 +1103,11 @@ int wave_viterbi_sweep(WaveDev *r, const double *d_y, hipStream_t st)
     });
 }
 
-// boundary certificates with exact re-sweeps, final state + backtrace, stitch + x[0], near-ties, ll.  The call has
+// boundary certificates with exact re-sweeps, final state + backtrace, stitch + x[0], near-ties, ll.  With ll_beside
+// the decode's last launches are on ll_st, which has taken st in behind the resolver: the caller goes on there.  The call has
 // zeroed diag, the tie counters and the list heads (wave_zero_bytes): every dependency below is a launch boundary.
-int wave_viterbi_post(WaveDev *r, const double *d_y, int16_t *d_x, double *d_ll, hipStream_t st, bool beside)
+int wave_viterbi_post(WaveDev *r, const double *d_y, int16_t *d_x, double *d_ll, hipStream_t st, bool beside,
+                      bool ll_beside, hipStream_t ll_st)
 {
     const WaveGeom &g = r->g;
     const int nchT = g.C * g.nch;
@@ -1146,13 +1153,39 @@ int wave_viterbi_post(WaveDev *r, const double *d_y, int16_t *d_x, double *d_ll,
                          r->diag, r->tie_cnt);
       hipLaunchKernelGGL(kw_stitch_fix, dim3(1), dim3(256), 0, st, g, r->d_cst, d_y, r->d_mean, r->d_ctab, r->psi, d_x,
                          r->bstate, r->heads + 2, r->heads + 3, r->redo + nsegT, r->diag, r->tie_cnt); }
+    // ll_beside: the path likelihood runs on another stream (ll_st) beside the near-tie chain: x[0] and every stitch
+    // repair are in, and in the common case the resolver leaves x alone.
+    if (ll_beside) {
+        HS_HIP(hipEventRecord(r->ev_x, st));
+        HS_HIP(hipStreamWaitEvent(ll_st, r->ev_x, 0));
+        WPROF(r, "kw_ll_partial", ll_st);
+        hipLaunchKernelGGL(kw_ll_partial, dim3(r->nparts, g.C), dim3(256), 0, ll_st, g, r->d_cst, d_y, d_x, r->d_mean,
+                           r->d_ctab, r->part, nullptr);
+    }
     // flagged near-ties on the decoded path: re-decided with the reference's own arithmetic (no-ops otherwise)
     if ((rc = wave_tie_resolve(r, d_y, d_x, st))) return rc;
-    { WPROF(r, "kw_ll_partial", st);
-      hipLaunchKernelGGL(kw_ll_partial, dim3(r->nparts, g.C), dim3(256), 0, st, g, r->d_cst, d_y, d_x, r->d_mean,
-                         r->d_ctab, r->part); }
-    { WPROF(r, "kw_sum_partials", st);
-      hipLaunchKernelGGL(kw_sum_partials, dim3(g.C), dim3(256), 0, st, r->part, r->nparts, d_ll); }
+    if (!ll_beside) {
+        ll_st = st;
+        WPROF(r, "kw_ll_partial", st);
+        hipLaunchKernelGGL(kw_ll_partial, dim3(r->nparts, g.C), dim3(256), 0, st, g, r->d_cst, d_y, d_x, r->d_mean,
+                           r->d_ctab, r->part, nullptr);
+    } else {
+        // Behind the resolver (ev_b) and, by stream order, behind the launch above (a late workgroup of it must not
+        // overwrite a recomputed partial): the partials of the channels whose x the resolver rewrote are computed
+        // again.  It stays on ll_st, and so does the sum: no launch at the end of the call waits for a signal from
+        // another stream.  The condition is tie_cnt[kTieFlips] != 0: of the whole tie chain only tie_flip
+        // (kw_tie_resolve) stores to x, both of its call sites count a flip first, and the kernel stores its flip
+        // count on every path that can reach them (the early returns come before any flip).  Flips off the decoded
+        // path make the condition a superset.  Same threads, same samples, same order: ll does not depend on which
+        // launch wrote a partial.
+        HS_HIP(hipEventRecord(r->ev_b, st));
+        HS_HIP(hipStreamWaitEvent(ll_st, r->ev_b, 0));
+        WPROF(r, "kw_ll_redo", ll_st);
+        hipLaunchKernelGGL(kw_ll_partial, dim3(r->nparts, g.C), dim3(256), 0, ll_st, g, r->d_cst, d_y, d_x, r->d_mean,
+                           r->d_ctab, r->part, r->tie_cnt);
+    }
+    { WPROF(r, "kw_sum_partials", ll_st);
+      hipLaunchKernelGGL(kw_sum_partials, dim3(g.C), dim3(256), 0, ll_st, r->part, r->nparts, d_ll); }
     HS_HIP(hipGetLastError());
     return HMMSORT_OK;
 }
@@ -1164,7 +1197,8 @@ int wave_viterbi(WaveDev *r, const double *d_y, int16_t *d_x, double *d_ll, hipS
         HS_HIP(hipMemsetAsync(r->diag, 0, wave_zero_bytes(r, true), s));   // diag, the tie counters, the list heads
         if ((rc = wave_prepare(r, d_y, s))) return rc;
         if ((rc = wave_viterbi_sweep(r, d_y, s))) return rc;
-        return wave_viterbi_post(r, d_y, d_x, d_ll, s, false);
+        // (ll behind the resolver, on s: on a stream of its own beside it the decode alone was slower)
+        return wave_viterbi_post(r, d_y, d_x, d_ll, s, false, false, s);
     });
 }
 
