@@ -47,6 +47,7 @@ struct WaveGeom {
     int first, last;
     double thr_scale;        // test aid: multiplier of the near-tie threshold (option "tie_scale")
     int tie_debug;           // test aids (option "tie_debug"): 1 exact prefix folded to the end, 2 resolver off (flagged = unresolved)
+    int cert_rounds;         // test aid (option "cert_rounds"): 1 every certificate round of a decode runs in full
     int backtrace;           // option "backtrace": 0 auto (light form beside an E-step, register rows alone), 1 register rows, 2 light
 };
 
@@ -70,9 +71,8 @@ struct WaveDev {
     std::vector<char> ucx;            // per channel
     const double *bound_y = nullptr;
     hipStream_t side = nullptr, side2 = nullptr;
-    // ev_fork / ev_join: s -> side2 -> s (fused call); ev_a / ev_c: s -> side -> s (certificate);
-    // ev_x / ev_b: side2 -> s where the fused call runs ll beside the resolver: x stitched / the resolver done
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_a = nullptr, ev_b = nullptr, ev_c = nullptr, ev_x = nullptr;
+    // ev_fork / ev_join: s -> side2 -> s (fused call); ev_a / ev_c: s -> side -> s (certificate)
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_a = nullptr, ev_c = nullptr;
     std::vector<ProfEntry> prof;
     int64_t S = 0, K = 0;
     std::vector<RingModel> ring;      // per channel
@@ -94,6 +94,7 @@ struct WaveDev {
     uint32_t *psi = nullptr;          // PW x C x T
     double *vpre = nullptr, *vend = nullptr;   // C*nch x (1 + N*L) Viterbi boundary states
     int32_t *vfail = nullptr;         // C*nch
+    uint64_t *vcert = nullptr;        // C*nch: what the final certificate round filters and maximises, as the last full round found it (kVitNoSpread: filtered out)
     int32_t *bstate = nullptr;        // C*nseg
     int32_t *redo = nullptr;          // 2 x C*nseg: the stitch lists of the first and the second check
     int32_t *final_state = nullptr;   // C
@@ -420,11 +421,8 @@ int wave_profile_read(WaveDev *r, hipStream_t st, std::vector<std::string> &name
                       std::vector<double> &ms, std::vector<int64_t> &calls);
 // wave_viterbi.hip
 int wave_viterbi_sweep(WaveDev *r, const double *d_y, hipStream_t st);
-// beside: the decode runs next to an E-step's sweeps (decides the backtrace form under option "backtrace" = 0);
-// ll_beside: the path likelihood runs on ll_st (another stream than st) beside the near-tie resolver; ll_st takes st
-// in behind the resolver and holds the decode's last launches when the function returns.  Otherwise all is on st.
-int wave_viterbi_post(WaveDev *r, const double *d_y, int16_t *d_x, double *d_ll, hipStream_t st, bool beside,
-                      bool ll_beside, hipStream_t ll_st);
+// beside: the decode runs next to an E-step's sweeps (decides the backtrace form under option "backtrace" = 0)
+int wave_viterbi_post(WaveDev *r, const double *d_y, int16_t *d_x, double *d_ll, hipStream_t st, bool beside);
 int wave_viterbi(WaveDev *r, const double *d_y, int16_t *d_x, double *d_ll, hipStream_t st);
 // wave_ties.hip
 int wave_tie_resolve(WaveDev *r, const double *d_y, int16_t *d_x, hipStream_t st);

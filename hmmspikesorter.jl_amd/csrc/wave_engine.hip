@@ -59,7 +59,7 @@ static int make_geometry(WaveGeom &g, int64_t T, int C, int N, int L, int64_t bl
     g.T = T; g.C = C; g.N = N; g.L = L;
     g.own_lo = 0; g.own_hi = T; g.first = 1; g.last = 1;
     { const Options o = options_get(); g.thr_scale = (double)o.tie_scale; g.tie_debug = (int)o.tie_debug;
-      g.backtrace = (int)o.backtrace; }
+      g.backtrace = (int)o.backtrace; g.cert_rounds = (int)o.cert_rounds; }
     g.W = std::min(L, 64);
     g.RB = (int)wround_up(L + g.W, 32);
     // warm-up: four ring lengths, at least 256 samples; with chains of thousands of samples this is
@@ -244,6 +244,7 @@ int wave_create(WaveDev **out, const std::vector<HostModel> &models, int64_t T, 
     A(&r->vpre, nchT * (1 + N * L));
     A(&r->vend, nchT * (1 + N * L));
     A(&r->vfail, nchT + 8);
+    A(&r->vcert, nchT + 8);
     A(&r->bstate, C * g.nseg);
     A(&r->redo, 2 * C * g.nseg + 8);
     A(&r->vlist, 2 * nchT + 8);
@@ -317,9 +318,7 @@ int wave_create(WaveDev **out, const std::vector<HostModel> &models, int64_t T, 
         hipEventCreateWithFlags(&r->ev_fork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&r->ev_join, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&r->ev_a, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&r->ev_b, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&r->ev_c, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&r->ev_x, hipEventDisableTiming) != hipSuccess) {
+        hipEventCreateWithFlags(&r->ev_c, hipEventDisableTiming) != hipSuccess) {
         set_error("wave engine: could not create the internal stream/events");
         wave_destroy(r);
         return HMMSORT_EHIP;
@@ -332,7 +331,7 @@ void wave_destroy(WaveDev *r)
 {
     if (!r) return;
     void *ptrs[] = {r->d_cst, r->d_mean, r->d_meanT, r->d_cint, r->d_msq, r->d_ctab, r->d_states, r->Rf, r->W2, r->virt, r->ysum,
-                    r->psi, r->vpre, r->vend, r->vfail, r->bstate, r->redo, r->final_state, r->part, r->FA0,
+                    r->psi, r->vpre, r->vend, r->vfail, r->vcert, r->bstate, r->redo, r->final_state, r->part, r->FA0,
                     r->FV, r->FREF, r->fpre, r->bpre, r->bown, r->rho, r->Zc, r->partS, r->partG, r->yhead,
                     r->extra, r->pp, r->diag, r->vlist, r->dbg, r->trash, r->tie_list, r->tie_off, r->tie_walk, r->tie_guess,
                     r->tie_c, r->tie_ok, r->tie_v, r->gsil, r->phead, r->plogz, r->pcnt};
@@ -341,9 +340,7 @@ void wave_destroy(WaveDev *r)
     if (r->ev_fork) (void)hipEventDestroy(r->ev_fork);
     if (r->ev_join) (void)hipEventDestroy(r->ev_join);
     if (r->ev_a) (void)hipEventDestroy(r->ev_a);
-    if (r->ev_b) (void)hipEventDestroy(r->ev_b);
     if (r->ev_c) (void)hipEventDestroy(r->ev_c);
-    if (r->ev_x) (void)hipEventDestroy(r->ev_x);
     if (r->side) (void)hipStreamDestroy(r->side);
     if (r->side2) (void)hipStreamDestroy(r->side2);
     for (auto &e : r->prof) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }

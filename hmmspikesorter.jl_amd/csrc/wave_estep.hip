@@ -1261,17 +1261,11 @@ int wave_decode_estep(WaveDev *r, const double *d_y, int16_t *d_x, double *d_ll,
         // decode would otherwise hold the forward sweep back by their host-side enqueue time, ~0.1 ms)
         if ((rc = wave_estep_sweeps(r, d_y, d_stats, s, false))) return rc;
         if ((rc = wave_viterbi_sweep(r, d_y, r->side2))) return rc;
-        // One channel of up to four rings (the backward sweep that sums the statistics itself): the E-step chain and
-        // the decode branch are about equally long and the decode's tail ends the call, so the path likelihood takes
-        // the E-step's own stream behind kw_stats_final, beside the certificate (side) and the near-tie chain
-        // (side2), and the decode branch joins there.  Longer E-step chains (more rings, batched plans) hide the
-        // whole decode branch: there ll stays on side2, where it costs the call nothing.
-        const bool ll_trunk = r->g.C == 1 && r->g.N <= 4;
-        if ((rc = wave_viterbi_post(r, d_y, d_x, d_ll, r->side2, true, ll_trunk, s))) return rc;
-        if (!ll_trunk) {
-            HS_HIP(hipEventRecord(r->ev_join, r->side2));
-            HS_HIP(hipStreamWaitEvent(s, r->ev_join, 0));
-        }
+        // The whole decode branch stays on side2, ll behind the resolver as in a decode on its own: nothing of it is
+        // enqueued behind kw_stats_final except the join.
+        if ((rc = wave_viterbi_post(r, d_y, d_x, d_ll, r->side2, true))) return rc;
+        HS_HIP(hipEventRecord(r->ev_join, r->side2));
+        HS_HIP(hipStreamWaitEvent(s, r->ev_join, 0));
         HS_HIP(hipStreamWaitEvent(s, r->ev_c, 0));
         return HMMSORT_OK;
     });

@@ -368,29 +368,70 @@ __device__ __forceinline__ VitCert vit_cert(const WaveGeom &g, const double *__r
 // The rounds before the final one also list the chains the next kw_vit_redo launch sweeps again: chain cg failed,
 // its predecessor did not (so the predecessor's end state is final) and it is not a channel's first chain.  The
 // predecessor's verdict is another workgroup's result of this same launch, so a failing chain works it out itself.
+//
+// A round that would repeat the one before it returns at once.  prev_head is the list head of the previous round
+// (nullptr: the first round, or option "cert_rounds" = 1).  When that list is empty no chain failed in the previous
+// round -- the first failing chain of a channel has a passing predecessor (a channel's first chain never fails), so
+// it is always listed -- hence nothing was swept again and every verdict of this round would be the previous
+// round's.  A round before the final one then has nothing to do: vfail is all zeros already, its own list stays
+// empty (the call zeroed the heads), diag[1] gains nothing.  The final round produces diag[2] from vcert, where every
+// full round before it leaves what the final round filters and maximises: the spread's bits, or kVitNoSpread
+// for a chain the filter drops.  Same values, same filter, same "read, then atomicMax only if larger" rule (per 64
+// chains), and a maximum does not depend on the order; vfail and diag[0] (no failure: 0) are as the full round would leave them.
+// The boundaries c <= 3 still run in full there: they write the dbg record.
+constexpr unsigned long long kVitNoSpread = ~0ull;
+
+__device__ __forceinline__ void vit_spread_max(int64_t *__restrict__ diag, unsigned long long sb)
+{
+    // a spread is >= 0, so its bits order like its value.  Most chains do not raise the maximum: they
+    // read it and leave (a stale read only costs an atomic that changes nothing).
+    if (sb > *reinterpret_cast<volatile unsigned long long *>(&diag[2]))
+        atomicMax((unsigned long long *)&diag[2], sb);
+}
+
 __global__ __launch_bounds__(64) void kw_vit_check(WaveGeom g, const double *__restrict__ vpre,
                                                    const double *__restrict__ vend,
                                                    int32_t *__restrict__ vfail, int64_t *__restrict__ diag,
                                                    int final_round, double *__restrict__ dbg,
-                                                   int32_t *__restrict__ head, int32_t *__restrict__ list)
+                                                   int32_t *__restrict__ head, int32_t *__restrict__ list,
+                                                   const int32_t *__restrict__ prev_head,
+                                                   unsigned long long *__restrict__ vcert)
 {
     const int lane = threadIdx.x;
     const int cg = blockIdx.x, c = cg % g.nch;
-    if (c == 0) { if (lane == 0) vfail[cg] = 0; return; }
+    const bool same = prev_head && prev_head[0] == 0;   // uniform over the launch
+    if (same && !final_round) return;
+    if (c == 0 && !same) { if (lane == 0) vfail[cg] = 0; return; }
+    if (same) {
+        // one wave per 64 chains takes the maximum of their stored spreads first: two thousand waves that all leave
+        // at once would all read diag[2] before any of them has raised it, and queue up on the same address
+        if (cg % 64 == 0) {
+            const int j = cg + lane;
+            unsigned long long sb = 0;   // (a spread of 0 raises nothing)
+            if (j < (int)gridDim.x && j % g.nch != 0) {
+                const unsigned long long v = vcert[j];
+                sb = v != kVitNoSpread ? v : 0;
+            }
+            for (int o = 32; o > 0; o >>= 1) {
+                const unsigned long long t = (unsigned long long)__shfl_xor((long long)sb, o);
+                sb = t > sb ? t : sb;
+            }
+            if (lane == 0 && sb) vit_spread_max(diag, sb);
+        }
+        if (c >= 1 && c <= 3) (void)vit_cert(g, vpre, vend, cg, lane, dbg);   // the dbg record of the first boundaries
+        return;
+    }
     const VitCert v = vit_cert(g, vpre, vend, cg, lane, final_round ? dbg : nullptr);
+    const bool counted = !v.anybad && v.spread == v.spread && v.spread < INFINITY;
+    const unsigned long long sb = (unsigned long long)__double_as_longlong(v.spread);
     if (lane == 0) {
         vfail[cg] = v.fail ? 1 : 0;
         if (final_round) {
             if (v.fail) atomicAdd((unsigned long long *)&diag[0], 1ull);
-            if (!v.anybad && v.spread == v.spread && v.spread < INFINITY) {
-                // a spread is >= 0, so its bits order like its value.  Most chains do not raise the maximum: they
-                // read it and leave (a stale read only costs an atomic that changes nothing).
-                const unsigned long long sb = (unsigned long long)__double_as_longlong(v.spread);
-                if (sb > *reinterpret_cast<volatile unsigned long long *>(&diag[2]))
-                    atomicMax((unsigned long long *)&diag[2], sb);
-            }
-        } else if (v.fail) {
-            atomicAdd((unsigned long long *)&diag[1], 1ull);  // chains swept again (all rounds)
+            if (counted) vit_spread_max(diag, sb);
+        } else {
+            vcert[cg] = counted ? sb : kVitNoSpread;
+            if (v.fail) atomicAdd((unsigned long long *)&diag[1], 1ull);  // chains swept again (all rounds)
         }
     }
     if (!final_round && v.fail) {   // wave-uniform
@@ -476,13 +517,17 @@ template <int N> constexpr int bt_tile()
 // dynamic LDS of a light backtrace workgroup: the psi tile (rows padded by four words: a row starts on 16 bytes,
 // and both the 128-bit staging writes and the 128-bit chunk reads of the walk are conflict-free per quarter wave)
 // and the output tile (rows padded by one word)
-template <int N> constexpr size_t bt_lds_bytes()
+template <int N, int SPW> constexpr size_t bt_lds_bytes()
 {
     constexpr int PW = wpsi_words_c(N), TS = bt_tile<N>();
-    return sizeof(uint32_t) * (size_t)(PW * 64 * (TS + 4) + 64 * (TS / 2 + 1));
+    return sizeof(uint32_t) * (size_t)(PW * SPW * (TS + 4) + SPW * (TS / 2 + 1));
 }
 
-template <int N>
+// SPW: segments (tile rows) per workgroup, 64, 32 or 16.  With SPW < 64 the lanes < SPW walk, all 64 lanes stage
+// the tile and move the output tile, a tile is fewer load and store instructions per lane, and 64 / SPW times as
+// many waves are resident; a wave's walk is as many instructions as before, so the device issues 64 / SPW times the
+// walk.  Which SPW a row width runs with is bt_spw (measured beside the backward sweep).
+template <int N, int SPW>
 __device__ __forceinline__ void backtrace_light_body(const WaveGeom &g, const WaveConst *__restrict__ cst,
                                                const double *__restrict__ ysum, const double *__restrict__ vend,
                                                const uint32_t *__restrict__ psi, int32_t *__restrict__ final_state,
@@ -499,20 +544,23 @@ __device__ __forceinline__ void backtrace_light_body(const WaveGeom &g, const Wa
     constexpr int TSP = TS + 4;             // tile row stride in words
     constexpr int LPR = TS / 4;             // lanes per row of a 16-byte load instruction
     constexpr int RPW = 64 / LPR;           // segment rows per 16-byte load instruction (TS / 4 instructions per plane)
-    constexpr int WU = 4;                   // 16-byte loads in flight while a tile is staged (16 registers, dead in the walk)
+    constexpr int WU = SPW / RPW < 4 ? SPW / RPW : 4;   // 16-byte loads in flight while a tile is staged (up to 16 registers, dead in the walk)
     constexpr int SU = 2;                   // row loads in flight on the dword path (planes off 16 bytes)
     constexpr int XU = PW == 4 ? 2 : 4;     // row stores in flight while the output tile leaves (four spill at PW = 4)
     static_assert(CH % 4 == 0 && TS % CH == 0, "chunks are whole 16-byte groups");
-    static_assert(64 % (RPW * WU) == 0, "whole batches of wide loads");
-    static_assert(bt_lds_bytes<N>() <= 32 * 1024, "LDS budget");
-    extern __shared__ __align__(16) uint32_t lds_bt[];    // tile[PW][64][TS + 4] | xt[64][XW + 1]
-    uint32_t (*tile)[64][TSP] = reinterpret_cast<uint32_t (*)[64][TSP]>(lds_bt);
-    uint32_t (*xt)[XW + 1] = reinterpret_cast<uint32_t (*)[XW + 1]>(lds_bt + PW * 64 * TSP);
+    static_assert(SPW == 64 || SPW == 32 || SPW == 16, "segments per workgroup");
+    static_assert(WU >= 1 && SPW % (RPW * WU) == 0, "whole batches of wide loads");
+    static_assert(SPW % RPI == 0 && SPW % XRI == 0, "whole row instructions");
+    static_assert(bt_lds_bytes<N, SPW>() <= 32 * 1024, "LDS budget");
+    extern __shared__ __align__(16) uint32_t lds_bt[];    // tile[PW][SPW][TS + 4] | xt[SPW][XW + 1]
+    uint32_t (*tile)[SPW][TSP] = reinterpret_cast<uint32_t (*)[SPW][TSP]>(lds_bt);
+    uint32_t (*xt)[XW + 1] = reinterpret_cast<uint32_t (*)[XW + 1]>(lds_bt + PW * SPW * TSP);
     const int lane = threadIdx.x, ch = blockIdx.y;
     const int L = g.L, Bb = g.Bb, Hb = g.Hb;
     const int64_t T = g.T;
-    const int64_t sg0 = (int64_t)blockIdx.x * 64, sg = sg0 + lane;
-    const bool active = sg < g.nseg;
+    const int64_t sg0 = (int64_t)blockIdx.x * SPW, sg = sg0 + lane;
+    const bool walker = SPW == 64 || lane < SPW;           // the lanes that hold a row
+    const bool active = walker && sg < g.nseg;
     const int64_t s_lo = sg * Bb;
     const int64_t s_hi = active ? ((s_lo + Bb) < T ? (s_lo + Bb) : T) : s_lo;
     const int64_t te = (s_hi + Hb) < T ? (s_hi + Hb) : T;  // walk starts at te-1
@@ -523,7 +571,7 @@ __device__ __forceinline__ void backtrace_light_body(const WaveGeom &g, const Wa
     // times relative to the segment start: u = t - s_lo
     const int te_rel = active ? (int)(te - s_lo) : 0, hi_rel = (int)(s_hi - s_lo);
     const int t1 = s_lo >= 1 ? 0 : 1;                      // the step at t = 0 has no predecessor
-    const int t2 = s_lo >= 2 ? 0 : (int)(2 - s_lo);        // psi(1) only decides x[0]: kw_first_state
+    const int t2 = 2 * t1;                                 // psi(1) only decides x[0]: kw_first_state (s_lo is 0 or at least Bb)
     // walk state: id = state id at the current sample, rem = steps left inside the ring (0 at a junction),
     // (wi, sh) = word and bit offset of the psi entry the next junction decision reads (entry e = ring + 1)
     int id = 1, rem = 0, wi = 0, sh = 0;
@@ -545,9 +593,11 @@ __device__ __forceinline__ void backtrace_light_body(const WaveGeom &g, const Wa
                     const uint4 t4 = *reinterpret_cast<const uint4 *>(&tile[w][lane][k * CH + i]);
                     rowv[w][i] = t4.x; rowv[w][i + 1] = t4.y; rowv[w][i + 2] = t4.z; rowv[w][i + 3] = t4.w;
                 }
+            // the lane's time marks relative to the chunk: sample i of it is u = ub + i of the segment
+            const int ub = TS * q + k * CH;
+            const int te_c = te_rel - ub, hi_c = hi_rel - ub, t1_c = t1 - ub, t2_c = t1_c + t1;   // t2 = 2 t1: both mark the channel's first segment
 #pragma unroll
             for (int i = CH - 1; i >= 0; i--) {
-                const int u = TS * q + k * CH + i;
                 const bool interior = rem > 0;
                 if (FAST ? OWN : true) {
                     if (i & 1) xr[i / 2] = (uint32_t)id << 16;
@@ -569,9 +619,9 @@ __device__ __forceinline__ void backtrace_light_body(const WaveGeom &g, const Wa
                     wi = interior ? wi : jwi;
                     sh = interior ? sh : jsh;
                 } else {
-                    const bool live = u < te_rel, step = live && u >= t1;
-                    bs = (live && u == hi_rel) ? id : bs;
-                    if (step && !interior && u < hi_rel && u >= t2) nflag += flag;
+                    const bool live = i < te_c, step = live && i >= t1_c;
+                    bs = (live && i == hi_c) ? id : bs;
+                    if (step && !interior && i < hi_c && i >= t2_c) nflag += flag;
                     id = step ? (interior ? id - 1 : jid) : id;
                     rem = step ? (interior ? rem - 1 : jrem) : rem;
                     wi = step ? (interior ? wi : jwi) : wi;
@@ -593,10 +643,10 @@ __device__ __forceinline__ void backtrace_light_body(const WaveGeom &g, const Wa
         // on 16 bytes (rows start at multiples of 64 samples from it) comes in with 16-byte loads, four rows of 64
         // samples per instruction and WU of them in flight; the other planes (T decides where the planes w > 0 and
         // the channels ch > 0 start) and the one group of four samples that T cuts take the dword path.
+        const int64_t tb = sg0 * Bb + (int64_t)TS * q, left = T - tb;
+        const int nrow = g.nseg - sg0 < SPW ? (int)(g.nseg - sg0) : SPW;                // rows that exist
+        const int lim = left < 0 ? 0 : (left < (int64_t)SPW * Bb ? (int)left : SPW * Bb);   // offsets below it are data
         {
-            const int64_t tb = sg0 * Bb + (int64_t)TS * q, left = T - tb;
-            const int nrow = g.nseg - sg0 < 64 ? (int)(g.nseg - sg0) : 64;                  // rows that exist
-            const int lim = left < 0 ? 0 : (left < (int64_t)64 * Bb ? (int)left : 64 * Bb);   // offsets below it are data
 #pragma unroll
             for (int w = 0; w < PW; w++) {
                 const uint32_t *pw = pc + w * planePsi;
@@ -604,7 +654,7 @@ __device__ __forceinline__ void backtrace_light_body(const WaveGeom &g, const Wa
                     const uint32_t *base = pw + (lim >= 4 ? tb : 0);          // no whole group in the tile: all read pw[0..3]
                     const int wr = lane / LPR, wc = 4 * (lane % LPR);
 #pragma unroll 1
-                    for (int r0 = 0; r0 < 64; r0 += RPW * WU) {
+                    for (int r0 = 0; r0 < SPW; r0 += RPW * WU) {
                         uint4 v[WU];
 #pragma unroll
                         for (int j = 0; j < WU; j++) {
@@ -621,9 +671,9 @@ __device__ __forceinline__ void backtrace_light_body(const WaveGeom &g, const Wa
                     }
                     // the group T cuts (staged as zeros above) starts at offset lim & ~3; the lane whose row holds
                     // it in this tile, if there is one, brings in its one to three samples
-                    if (left < (int64_t)64 * Bb && (lim & 3)) {
+                    if (left < (int64_t)SPW * Bb && (lim & 3)) {
                         const int c0 = (lim & ~3) - lane * Bb;
-                        if (c0 >= 0 && c0 < TS) {
+                        if (walker && c0 >= 0 && c0 < TS) {
 #pragma unroll
                             for (int j = 0; j < 3; j++)
                                 if (j < (lim & 3)) tile[w][lane][c0 + j] = pw[tb + (lim & ~3) + j];
@@ -632,7 +682,7 @@ __device__ __forceinline__ void backtrace_light_body(const WaveGeom &g, const Wa
                 } else {
                     const uint32_t *base = pw + (lim > 0 ? tb : 0);
 #pragma unroll SU
-                    for (int rr = 0; rr < 64; rr += RPI) {
+                    for (int rr = 0; rr < SPW; rr += RPI) {
                         const int r = rr + lr, o = r * Bb + lc;
                         const bool ok = r < nrow && o < lim;
                         const uint32_t v = base[ok ? (uint32_t)o : 0u];
@@ -647,32 +697,40 @@ __device__ __forceinline__ void backtrace_light_body(const WaveGeom &g, const Wa
         // wave-uniform choice of the tile body
         const bool lane_fast = u0 >= t1 && u1 <= te_rel &&
                                (own_tile ? (u1 <= hi_rel && u0 >= t2) : (u0 > hi_rel));
-        const bool fast = __all(lane_fast);
-        if (fast && own_tile) walk(q, std::true_type(), std::true_type(), true);
-        else if (fast) walk(q, std::true_type(), std::false_type(), false);
-        else walk(q, std::false_type(), std::false_type(), own_tile);
+        const bool fast = __all(lane_fast || !walker);
+        if (walker) {   // (no barrier and no cross-lane move inside a walk)
+            if (fast && own_tile) walk(q, std::true_type(), std::true_type(), true);
+            else if (fast) walk(q, std::true_type(), std::false_type(), false);
+            else walk(q, std::false_type(), std::false_type(), own_tile);
+        }
         if (own_tile) {  // owned rows: write x out, coalesced
             __syncthreads();
             const int xrw = lane / XW, xcw = lane % XW;
+            int16_t *xb = xc + (lim > 0 ? tb : 0);   // wave-uniform tile origin + 32-bit lane offsets, as the loads
 #pragma unroll XU
-            for (int rr = 0; rr < 64; rr += XRI) {
-                const int r = rr + xrw;
-                const int64_t t = (sg0 + r) * Bb + (int64_t)TS * q + 2 * xcw;
-                if ((sg0 + r) < g.nseg && t < T) {
+            for (int rr = 0; rr < SPW; rr += XRI) {
+                const int r = rr + xrw, o = r * Bb + 2 * xcw;
+                if (r < nrow && o < lim) {
                     const uint32_t v = xt[r][xcw];
-                    if (t + 1 < T && xal) *reinterpret_cast<uint32_t *>(xc + t) = v;
+                    if (o + 1 < lim && xal) *reinterpret_cast<uint32_t *>(xb + o) = v;
                     else {
-                        xc[t] = (int16_t)(v & 0xffffu);
-                        if (t + 1 < T) xc[t + 1] = (int16_t)(v >> 16);
+                        xb[o] = (int16_t)(v & 0xffffu);
+                        if (o + 1 < lim) xb[o + 1] = (int16_t)(v >> 16);
                     }
                 }
             }
         }
         __syncthreads();
     }
-    if (active && hi_rel < te_rel) (bstate + ((int64_t)ch * g.nseg + sg0))[lane] = bs;   // wave-uniform base: sg is not kept
+    // every segment but the channel's last has a successor whose first sample its walk crossed (hi_rel < te_rel);
+    // wave-uniform base and bound: sg is not kept
+    {
+        const int64_t nb = g.nseg - 1 - sg0;
+        const int nbs = nb < SPW ? (int)nb : SPW;
+        if ((int)threadIdx.x < nbs) (bstate + ((int64_t)ch * g.nseg + sg0))[threadIdx.x] = bs;
+    }
     for (int o = 32; o > 0; o >>= 1) nflag += __shfl_xor(nflag, o);
-    if (lane == 0 && nflag) atomicAdd((unsigned long long *)&tie_cnt[ch * 8 + kTieTrig], (unsigned long long)nflag);
+    if (threadIdx.x == 0 && nflag) atomicAdd((unsigned long long *)&tie_cnt[ch * 8 + kTieTrig], (unsigned long long)nflag);
 }
 
 template <int N>
@@ -820,14 +878,14 @@ __global__ __launch_bounds__(64) void kw_backtrace(WaveGeom g, const WaveConst *
 // Six waves per SIMD is an 80-register budget.  The tiles are DYNAMIC shared memory: with a static size the
 // compiler sees that LDS caps the waves per SIMD at two and takes twice the registers that are free beside the
 // backward sweep.
-template <int N>
+template <int N, int SPW>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6)))
 void kw_backtrace_light(WaveGeom g, const WaveConst *__restrict__ cst, const double *__restrict__ ysum,
                         const double *__restrict__ vend, const uint32_t *__restrict__ psi,
                         int32_t *__restrict__ final_state, int16_t *__restrict__ x, int32_t *__restrict__ bstate,
                         int64_t *__restrict__ tie_cnt)
 {
-    backtrace_light_body<N>(g, cst, ysum, vend, psi, final_state, x, bstate, tie_cnt);
+    backtrace_light_body<N, SPW>(g, cst, ysum, vend, psi, final_state, x, bstate, tie_cnt);
 }
 
 __device__ __forceinline__ void wwalk_step(const WaveGeom &g, const uint32_t *__restrict__ pc, int64_t planePsi,
@@ -1024,18 +1082,13 @@ __global__ __launch_bounds__(256) void kw_stitch_fix(WaveGeom g, const WaveConst
 
 // ll = sum_{t=1..T-1} T1[x_t, t]  (viterbi.jl:92-96) without the trellis:
 //   T1[x_t,t] = T1[x_0,0] + sum_{u=1..t} inc_u  =>  ll = (T-1) T1[x_0,0] + sum_u (T-u) inc_u.
-// Launched twice per decode (wave_viterbi_post): once beside the near-tie resolver (redo_cnt = nullptr), and once
-// behind it with redo_cnt = the tie counters, where a channel's workgroups return at once unless the resolver
-// rewrote that channel's x; then they compute the same partials again from the final path.
 __global__ __launch_bounds__(256) void kw_ll_partial(WaveGeom g, const WaveConst *__restrict__ cst,
                                                      const double *__restrict__ y, const int16_t *__restrict__ x,
                                                      const double *__restrict__ mean,
-                                                     const double *__restrict__ ctab_all, double *__restrict__ part,
-                                                     const int64_t *__restrict__ redo_cnt)
+                                                     const double *__restrict__ ctab_all, double *__restrict__ part)
 {
     __shared__ double red[4];
     const int ch = blockIdx.y, N = g.N, L = g.L, S = 1 + N * L;
-    if (redo_cnt && redo_cnt[ch * 8 + kTieFlips] == 0) return;   // block-uniform
     const int64_t T = g.T;
     const double *yc = y + (int64_t)ch * T, *mc = mean + (int64_t)ch * S;
     const int16_t *xc = x + (int64_t)ch * T;
@@ -1082,6 +1135,10 @@ static int wave_lds_attr(Kern kern, size_t lds)
     return HMMSORT_OK;
 }
 
+// Segments per workgroup of the light backtrace, by words per back-pointer row (one-word
+// rows measured with 16, 32 and 64 beside the backward sweep; wider rows keep 64)
+template <int N> constexpr int bt_spw() { return wpsi_words_c(N) == 1 ? 32 : 64; }
+
 constexpr int kVitRounds = 2;  // certificate + re-sweep rounds run unconditionally on device
 
 int wave_viterbi_sweep(WaveDev *r, const double *d_y, hipStream_t st)
@@ -1103,11 +1160,9 @@ int wave_viterbi_sweep(WaveDev *r, const double *d_y, hipStream_t st)
     });
 }
 
-// boundary certificates with exact re-sweeps, final state + backtrace, stitch + x[0], near-ties, ll.  With ll_beside
-// the decode's last launches are on ll_st, which has taken st in behind the resolver: the caller goes on there.  The call has
+// boundary certificates with exact re-sweeps, final state + backtrace, stitch + x[0], near-ties, ll: all on st.  The call has
 // zeroed diag, the tie counters and the list heads (wave_zero_bytes): every dependency below is a launch boundary.
-int wave_viterbi_post(WaveDev *r, const double *d_y, int16_t *d_x, double *d_ll, hipStream_t st, bool beside,
-                      bool ll_beside, hipStream_t ll_st)
+int wave_viterbi_post(WaveDev *r, const double *d_y, int16_t *d_x, double *d_ll, hipStream_t st, bool beside)
 {
     const WaveGeom &g = r->g;
     const int nchT = g.C * g.nch;
@@ -1120,23 +1175,32 @@ int wave_viterbi_post(WaveDev *r, const double *d_y, int16_t *d_x, double *d_ll,
         if constexpr (N <= 4) { if (beside) kern = r->uniform_cx ? kw_vit_redo<N, true, true> : kw_vit_redo<N, false, true>; }
         int rc2 = wave_lds_attr(kern, lds);
         if (rc2) return rc2;
+        // a round whose predecessor listed nothing returns at once (kw_vit_check); option "cert_rounds" = 1: all in full
+        auto prev_head = [&](int round) -> const int32_t * {
+            return (round > 0 && !g.cert_rounds && g.nch > 1) ? r->heads + round - 1 : nullptr;
+        };
         for (int round = 0; round < kVitRounds && g.nch > 1; round++) {
             int32_t *head = r->heads + round, *list = r->vlist + (size_t)round * nchT;
             { WPROF(r, "kw_vit_check", st);
               hipLaunchKernelGGL(kw_vit_check, dim3(nchT), dim3(64), 0, st, g, r->vpre, r->vend, r->vfail, r->diag, 0, nullptr,
-                                 head, list); }
+                                 head, list, prev_head(round), (unsigned long long *)r->vcert); }
             { WPROF(r, "kw_vit_redo", st);
               hipLaunchKernelGGL(kern, dim3(std::min(nchT, kVitRedoGrid)), dim3(64), lds, st, g, r->d_cst, d_y, r->Rf,
                                  r->virt, r->ysum, r->psi, r->vpre, r->vend, (uint32_t *)r->trash, head, list); }
         }
         { WPROF(r, "kw_vit_check", st);
           hipLaunchKernelGGL(kw_vit_check, dim3(nchT), dim3(64), 0, st, g, r->vpre, r->vend, r->vfail, r->diag, 1, r->dbg,
-                             nullptr, nullptr); }
+                             nullptr, nullptr, prev_head(kVitRounds), (unsigned long long *)r->vcert); }
         { WPROF(r, "kw_backtrace", st);
-          auto kb = light ? kw_backtrace_light<N> : kw_backtrace<N>;
-          const size_t ldsb = light ? bt_lds_bytes<N>() : 0;   // the register-row form's tiles are static
-          hipLaunchKernelGGL(kb, dim3((unsigned)((g.nseg + 63) / 64), g.C), dim3(64), ldsb, st, g, r->d_cst, r->ysum, r->vend,
-                             r->psi, r->final_state, d_x, r->bstate, r->tie_cnt); }
+          const dim3 grid_rows((unsigned)((g.nseg + 63) / 64), g.C);
+          constexpr int SPW = bt_spw<N>();
+          if (!light)   // the register-row form's tiles are static
+              hipLaunchKernelGGL(kw_backtrace<N>, grid_rows, dim3(64), 0, st, g, r->d_cst, r->ysum, r->vend, r->psi,
+                                 r->final_state, d_x, r->bstate, r->tie_cnt);
+          else
+              hipLaunchKernelGGL((kw_backtrace_light<N, SPW>), dim3((unsigned)((g.nseg + SPW - 1) / SPW), g.C), dim3(64),
+                                 (bt_lds_bytes<N, SPW>()), st, g, r->d_cst, r->ysum, r->vend, r->psi, r->final_state, d_x,
+                                 r->bstate, r->tie_cnt); }
         HS_HIP(hipGetLastError());
         return HMMSORT_OK;
     });
@@ -1153,39 +1217,13 @@ int wave_viterbi_post(WaveDev *r, const double *d_y, int16_t *d_x, double *d_ll,
                          r->diag, r->tie_cnt);
       hipLaunchKernelGGL(kw_stitch_fix, dim3(1), dim3(256), 0, st, g, r->d_cst, d_y, r->d_mean, r->d_ctab, r->psi, d_x,
                          r->bstate, r->heads + 2, r->heads + 3, r->redo + nsegT, r->diag, r->tie_cnt); }
-    // ll_beside: the path likelihood runs on another stream (ll_st) beside the near-tie chain: x[0] and every stitch
-    // repair are in, and in the common case the resolver leaves x alone.
-    if (ll_beside) {
-        HS_HIP(hipEventRecord(r->ev_x, st));
-        HS_HIP(hipStreamWaitEvent(ll_st, r->ev_x, 0));
-        WPROF(r, "kw_ll_partial", ll_st);
-        hipLaunchKernelGGL(kw_ll_partial, dim3(r->nparts, g.C), dim3(256), 0, ll_st, g, r->d_cst, d_y, d_x, r->d_mean,
-                           r->d_ctab, r->part, nullptr);
-    }
     // flagged near-ties on the decoded path: re-decided with the reference's own arithmetic (no-ops otherwise)
     if ((rc = wave_tie_resolve(r, d_y, d_x, st))) return rc;
-    if (!ll_beside) {
-        ll_st = st;
-        WPROF(r, "kw_ll_partial", st);
-        hipLaunchKernelGGL(kw_ll_partial, dim3(r->nparts, g.C), dim3(256), 0, st, g, r->d_cst, d_y, d_x, r->d_mean,
-                           r->d_ctab, r->part, nullptr);
-    } else {
-        // Behind the resolver (ev_b) and, by stream order, behind the launch above (a late workgroup of it must not
-        // overwrite a recomputed partial): the partials of the channels whose x the resolver rewrote are computed
-        // again.  It stays on ll_st, and so does the sum: no launch at the end of the call waits for a signal from
-        // another stream.  The condition is tie_cnt[kTieFlips] != 0: of the whole tie chain only tie_flip
-        // (kw_tie_resolve) stores to x, both of its call sites count a flip first, and the kernel stores its flip
-        // count on every path that can reach them (the early returns come before any flip).  Flips off the decoded
-        // path make the condition a superset.  Same threads, same samples, same order: ll does not depend on which
-        // launch wrote a partial.
-        HS_HIP(hipEventRecord(r->ev_b, st));
-        HS_HIP(hipStreamWaitEvent(ll_st, r->ev_b, 0));
-        WPROF(r, "kw_ll_redo", ll_st);
-        hipLaunchKernelGGL(kw_ll_partial, dim3(r->nparts, g.C), dim3(256), 0, ll_st, g, r->d_cst, d_y, d_x, r->d_mean,
-                           r->d_ctab, r->part, r->tie_cnt);
-    }
-    { WPROF(r, "kw_sum_partials", ll_st);
-      hipLaunchKernelGGL(kw_sum_partials, dim3(g.C), dim3(256), 0, ll_st, r->part, r->nparts, d_ll); }
+    { WPROF(r, "kw_ll_partial", st);
+      hipLaunchKernelGGL(kw_ll_partial, dim3(r->nparts, g.C), dim3(256), 0, st, g, r->d_cst, d_y, d_x, r->d_mean,
+                         r->d_ctab, r->part); }
+    { WPROF(r, "kw_sum_partials", st);
+      hipLaunchKernelGGL(kw_sum_partials, dim3(g.C), dim3(256), 0, st, r->part, r->nparts, d_ll); }
     HS_HIP(hipGetLastError());
     return HMMSORT_OK;
 }
@@ -1198,7 +1236,7 @@ int wave_viterbi(WaveDev *r, const double *d_y, int16_t *d_x, double *d_ll, hipS
         if ((rc = wave_prepare(r, d_y, s))) return rc;
         if ((rc = wave_viterbi_sweep(r, d_y, s))) return rc;
         // (ll behind the resolver, on s: on a stream of its own beside it the decode alone was slower)
-        return wave_viterbi_post(r, d_y, d_x, d_ll, s, false, false, s);
+        return wave_viterbi_post(r, d_y, d_x, d_ll, s, false);
     });
 }
 
