@@ -8,10 +8,10 @@ from . import _lib, dist, synth
 from ._lib import (ENGINE_AUTO, ENGINE_BLOCKED, ENGINE_RING, ENGINE_STRICT, ENGINE_WAVE, HmmsortError, device_count,
                    get_option, set_option, shutdown)
 from .api import (HMMSpikeTemplateModel, HMMSpikingModel, Posteriors, StateMatrix, backward, extract_spiketimes,
-                  fit, fit_channels, forward,
+                  fit, fit_channels, fit_step_channels, forward,
                   posterior_decode, posteriors, predict, reconstruct_signal, spike_confidence, train_model, train_step, unroll_mlseq, update,
                   viterbi, viterbi_step)
-from .device import Plan
+from .device import Plan, stats_sum
 from .postprocess import (condense_candidates, condense_templates, find_best_overlap, match_templates,
                           prune_templates, remove_small, remove_sparse)
 from .sortdata import get_lp, sort_data
@@ -19,7 +19,7 @@ from .synth import create_signal, create_spike_template
 
 __all__ = ["StateMatrix", "HMMSpikeTemplateModel", "HMMSpikingModel", "forward", "backward",
            "update", "train_model", "train_step", "viterbi", "reconstruct_signal", "unroll_mlseq",
-           "fit", "fit_channels", "predict", "extract_spiketimes", "Plan", "create_signal", "create_spike_template", "HmmsortError",
+           "fit", "fit_channels", "fit_step_channels", "stats_sum", "predict", "extract_spiketimes", "Plan", "create_signal", "create_spike_template", "HmmsortError",
            "set_option", "get_option", "shutdown", "device_count", "ENGINE_AUTO", "ENGINE_STRICT",
            "ENGINE_RING", "ENGINE_BLOCKED", "ENGINE_WAVE", "get_lp", "sort_data", "find_best_overlap",
            "condense_candidates", "condense_templates", "remove_sparse", "remove_small", "prune_templates",

@@ -44,6 +44,12 @@ class Model(C.Structure):
                 ("sigma", _f64)]
 
 
+class StepOut(C.Structure):
+    """struct hmmsort_step_out: what hmmsort_fit_step_channels returns per channel (pooled: record 0 only)"""
+    _fields_ = [("mu", _vp), ("sigma", _vp), ("lp", _vp), ("lp_cap", _i64), ("n_lp", _vp), ("pp", _vp),
+                ("counts", _vp)]
+
+
 # name -> (restype, argtypes); every symbol include/hmmsort.h declares
 SIGNATURES = {
     "hmmsort_last_error": (C.c_char_p, []),
@@ -61,6 +67,8 @@ SIGNATURES = {
     "hmmsort_fit_chunked_i16": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _f64, _vp, _vp]),
     "hmmsort_fit_channels": (_int, [_i64, C.POINTER(_vp), _int, _i64, _i64, C.POINTER(Model), C.POINTER(_int), _i64,
                                     C.POINTER(_vp), _vp, C.POINTER(_int)]),
+    "hmmsort_fit_step_channels": (_int, [_i64, C.POINTER(_vp), _int, _i64, _i64, C.POINTER(Model), C.POINTER(_int),
+                                         _i64, _int, C.POINTER(_vp), _vp, C.POINTER(StepOut), C.POINTER(_int)]),
     "hmmsort_chunk_stitch": (_int, [_vp, _i64, _int, _int, _vp, _vp, _vp]),
     "hmmsort_samples_to_f64": (_int, [_vp, C.c_int, _i64, _i64, _vp, _vp]),
     "hmmsort_forward": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _f64, _vp]),
@@ -94,6 +102,10 @@ SIGNATURES = {
     "hmmsort_plan_mstep": (_int, [_vp, _vp, _vp, _vp]),
     "hmmsort_plan_mstep_len": (_i64, [_vp]),
     "hmmsort_plan_path_update": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "hmmsort_plan_path_stats_len": (_i64, [_vp]),
+    "hmmsort_plan_path_stats": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp]),
+    "hmmsort_plan_path_finish": (_int, [_vp, _vp, _vp, _vp, _vp]),
+    "hmmsort_stats_sum": (_int, [_vp, _i64, _i64, _vp, _vp]),
     "hmmsort_plan_diagnostics": (_int, [_vp, _vp, _pi64]),
     "hmmsort_plan_tie_stats": (_int, [_vp, _vp, _pi64]),
     "hmmsort_plan_extract_spiketimes": (_int, [_vp, _vp, _vp, _i64, _vp, _vp]),

@@ -13,7 +13,7 @@ Reference methods mirrored (file:line relative to the reference root):
   reconstruct_signal                                                  src/reconstruction.jl:1
   unroll_mlseq                                                        src/extraction.jl:4
   fit(HMMSpikingModel, templates, X, chunksize)                       src/fit.jl:11-42
-Extensions (no counterpart in the reference): posteriors, posterior_decode, spike_confidence, viterbi_step and
+Extensions (no counterpart in the reference): posteriors, posterior_decode, spike_confidence, fit_step_channels, viterbi_step and
 train_model(..., method="viterbi").
 """
 import ctypes as C
@@ -537,6 +537,65 @@ def fit_channels(templates, X, chunksize=None, devices=None):
                                     len(devices) if devices else 0, outs, ptr(ll), status)
     check(rc)
     return [HMMSpikingModel(tms[c], ml[c], float(ll[c]), rows[c]) for c in range(nch)]
+
+
+def fit_step_channels(templates, X, chunksize=None, devices=None, pooled=False):
+    """One step of Viterbi training for C recording channels in one native call (hmmsort_fit_step_channels): every
+    channel is decoded exactly as fit_channels decodes it, and the model is re-estimated from the statistics of
+    its stitched path while signal and path are still on the GPU.  Arguments as fit_channels.  `pooled`: the
+    channels' statistics are added in channel order and finished once with the first channel's model (all
+    models must share their state table): one set of templates for all channels.
+
+    Returns (models, steps): the list of HMMSpikingModel of the decode under the OLD models, and one
+    (state_matrix', mu', sigma', counts) per channel, or a single one when pooled.  counts = [ids outside 1..S,
+    pairs that are no transition, template rows that kept their mean]."""
+    rows = [X[c] for c in range(len(X))]
+    if not rows:
+        raise ValueError("fit_step_channels: no channel")
+    raw = all(isinstance(r, np.ndarray) and r.dtype == np.int16 for r in rows)
+    rows = [np.ascontiguousarray(r) if raw else _signal(r) for r in rows]
+    nch, n = len(rows), len(rows[0])
+    if any(r.ndim != 1 or len(r) != n for r in rows):
+        raise ValueError("fit_step_channels: channels must be one-dimensional and of equal length")
+    tms = list(templates) if isinstance(templates, (list, tuple)) else [templates] * nch
+    if len(tms) != nch:
+        raise ValueError("fit_step_channels: %d template models for %d channels" % (len(tms), nch))
+    keep = []
+    models = (_lib.Model * nch)()
+    for c, tm in enumerate(tms):
+        k, m = _model_args(tm.state_matrix, tm.mu, tm.sigma)
+        keep.append(k)
+        models[c] = _lib.Model(*m)
+    ml = [np.zeros(n, dtype=np.int16) for _ in range(nch)]
+    ll = np.zeros(nch)
+    status = (C.c_int * nch)()
+    ys = (C.c_void_p * nch)(*[r.ctypes.data for r in rows])
+    outs = (C.c_void_p * nch)(*[m.ctypes.data for m in ml])
+    dev = (C.c_int * len(devices))(*devices) if devices else None
+    nout = 1 if pooled else nch
+    recs = (_lib.StepOut * nout)()
+    bufs = []
+    for c in range(nout):
+        lA = tms[c].state_matrix
+        b = dict(mu=np.zeros((lA.K, lA.N), order="F"), sigma=np.zeros(1), lp=np.zeros(len(keep[c][1])),
+                 nlp=np.zeros(1, dtype=np.int64), pp=np.zeros(lA.nstates), counts=np.zeros(3, dtype=np.int64))
+        bufs.append(b)
+        # the first column of a pooled step is no channel's: the old one is kept
+        recs[c] = _lib.StepOut(b["mu"].ctypes.data, b["sigma"].ctypes.data, b["lp"].ctypes.data, len(b["lp"]),
+                               b["nlp"].ctypes.data, None if pooled else b["pp"].ctypes.data,
+                               b["counts"].ctypes.data)
+    rc = lib().hmmsort_fit_step_channels(nch, ys, _lib.SAMPLES_I16 if raw else _lib.SAMPLES_F64, n,
+                                         0 if chunksize is None else int(chunksize), models, dev,
+                                         len(devices) if devices else 0, int(bool(pooled)), outs, ptr(ll), recs,
+                                         status)
+    check(rc)
+    steps = []
+    for c, b in enumerate(bufs):
+        lA = tms[c].state_matrix
+        pp = np.asarray(lA.pi, dtype=np.float64) if pooled else b["pp"]
+        lA_new = StateMatrix.from_states(lA.states, pp, lA.K, b["lp"][:int(b["nlp"][0])].copy(), lA.resolve_overlaps)
+        steps.append((lA_new, b["mu"], float(b["sigma"][0]), b["counts"].tolist()))
+    return [HMMSpikingModel(tms[c], ml[c], float(ll[c]), rows[c]) for c in range(nch)], steps
 
 
 def predict(model):

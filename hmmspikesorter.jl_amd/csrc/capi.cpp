@@ -229,6 +229,7 @@ static int plan_set_model(const char *who, hmmsort_plan *p, int64_t channel, con
     if (!p->models.empty()) p->models[channel] = m;
     if (channel == 0) p->model = std::move(m);
     p->pu_stale = true;
+    p->ps_stale = true;
     return HMMSORT_OK;
 }
 
@@ -340,6 +341,34 @@ int hmmsort_plan_path_update(hmmsort_plan *p, const double *d_y, const int16_t *
     HS_CHECK(!p->sharded, HMMSORT_EINVAL, "plan_path_update: the plan is a time shard (hmmsort_plan_set_shard); the "
                                           "update needs the whole recording");
     return plan_path_update(p, d_y, d_x, d_out, d_counts, (hipStream_t)stream);
+}
+
+int64_t hmmsort_plan_path_stats_len(const hmmsort_plan *p) { return p ? plan_path_stats_len(p) : 0; }
+
+int hmmsort_plan_path_stats(hmmsort_plan *p, const double *d_y, const int16_t *d_x, int64_t T, int64_t own_lo,
+                            int64_t own_hi, int first, double *d_stats, void *stream)
+{
+    HS_CHECK(p && d_y && d_x && d_stats, HMMSORT_EINVAL, "plan_path_stats: null argument");
+    HS_CHECK(p->C == 1 || T == p->T, HMMSORT_EINVAL, "plan_path_stats: a batched plan takes [C][T] arrays of its own "
+             "T = %lld, not %lld", (long long)p->T, (long long)T);
+    HS_CHECK(own_lo >= 0 && own_lo <= own_hi && own_hi <= T, HMMSORT_EINVAL,
+             "plan_path_stats: range [%lld, %lld) outside [0, %lld]", (long long)own_lo, (long long)own_hi, (long long)T);
+    return plan_path_stats(p, d_y, d_x, T, own_lo, own_hi, first != 0, d_stats, (hipStream_t)stream);
+}
+
+int hmmsort_plan_path_finish(hmmsort_plan *p, const double *d_stats, double *d_out, int64_t *d_counts, void *stream)
+{
+    HS_CHECK(p && d_stats && d_out, HMMSORT_EINVAL, "plan_path_finish: null argument");
+    return plan_path_finish(p, d_stats, d_out, d_counts, (hipStream_t)stream);
+}
+
+int hmmsort_stats_sum(const double *d_parts, int64_t nparts, int64_t len, double *d_out, void *stream)
+{
+    HS_CHECK(d_parts && d_out && nparts >= 1 && len >= 1, HMMSORT_EINVAL, "stats_sum: null argument or nothing to add");
+    HS_CHECK(len <= (int64_t)2147483647 * 256, HMMSORT_EUNSUP, "stats_sum: vector too long");
+    int rc;
+    if ((rc = need_device())) return rc;
+    return dev_stats_sum(d_parts, nparts, len, d_out, (hipStream_t)stream);
 }
 
 int hmmsort_plan_diagnostics(hmmsort_plan *p, void *stream, int64_t diag[8])

@@ -249,6 +249,7 @@ int generic_engine_create(std::unique_ptr<Engine> *out, const HostModel &m, int6
 struct GenericDev;  // generic_engine.hip
 struct RingDev;     // ring_engine.hip
 struct PathUpdateDev;  // path_update.hip
+struct PathStatsDev;   // path_update.hip
 
 // generic (strict) engine: single sequential sweep in the reference's operation order
 // blocked = time-parallel Viterbi over blocks with a certified warm-up (generic_blocked.hip)
@@ -333,6 +334,9 @@ struct hmmsort_plan {
     // stale after hmmsort_plan_set_model
     std::shared_ptr<hmmsort::PathUpdateDev> pu;
     bool pu_stale = true;
+    // the same for the statistics form (hmmsort_plan_path_stats / _finish); its workspace grows with the arrays
+    std::shared_ptr<hmmsort::PathStatsDev> ps;
+    bool ps_stale = true;
 };
 
 namespace hmmsort {
@@ -349,5 +353,13 @@ struct PlanGuard {
 // three device int64 per channel or null; enqueued on st
 int plan_path_update(hmmsort_plan *p, const double *d_y, const int16_t *d_x, double *d_out, int64_t *d_counts,
                      hipStream_t st);
+// the additive form (path_update.hip): the statistics of samples [own_lo, own_hi) of arrays of length T (per channel
+// plan_path_stats_len doubles), the finish of such a vector with the plan's current model into d_out / d_counts as
+// above, and out = parts[0] + parts[1] + ... in that order for nparts vectors of len doubles
+int64_t plan_path_stats_len(const hmmsort_plan *p);
+int plan_path_stats(hmmsort_plan *p, const double *d_y, const int16_t *d_x, int64_t T, int64_t own_lo, int64_t own_hi,
+                    bool first, double *d_stats, hipStream_t st);
+int plan_path_finish(hmmsort_plan *p, const double *d_stats, double *d_out, int64_t *d_counts, hipStream_t st);
+int dev_stats_sum(const double *d_parts, int64_t nparts, int64_t len, double *d_out, hipStream_t st);
 void host_slots_trim(size_t keep);   // idle plans of the host-buffer entry points: keep the newest `keep`
 }  // namespace hmmsort

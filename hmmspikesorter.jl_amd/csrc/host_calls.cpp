@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -244,8 +245,11 @@ int host_call(const Entry &e, const void *y, int sample_type, int64_t T, const M
     return HMMSORT_OK;
 }
 
+// what a caller may run on the plan, signal and path of a decode before its slot goes back to the cache
+using AfterDecode = std::function<int(hmmsort_plan *, const double *, const int16_t *, hipStream_t)>;
+
 int viterbi_host(const void *y, int sample_type, int64_t T, const ModelArgs &a, int16_t *x_out, double *ll_out,
-                 const Options *snapshot = nullptr)
+                 const Options *snapshot = nullptr, const AfterDecode *after = nullptr)
 {
     HS_CHECK(y && x_out && ll_out, HMMSORT_EINVAL, "viterbi: null argument");
     HS_CHECK(T >= 1, HMMSORT_EINVAL, "viterbi: empty signal (T = %lld)", (long long)T);
@@ -260,7 +264,7 @@ int viterbi_host(const void *y, int sample_type, int64_t T, const ModelArgs &a, 
             HS_HIP(hipMemcpyAsync(x_out, h.dx.p, T * sizeof(int16_t), hipMemcpyDeviceToHost, h.st));
             HS_HIP(hipMemcpyAsync(ll_out, h.dll.p, sizeof(double), hipMemcpyDeviceToHost, h.st));
             HS_HIP(hipStreamSynchronize(h.st));
-            return HMMSORT_OK;
+            return after ? (*after)(h.plan, h.dy.as<double>(), h.dx.as<int16_t>(), h.st) : HMMSORT_OK;
         },
         snapshot);
 }
@@ -275,6 +279,44 @@ int viterbi_host(const void *y, int sample_type, int64_t T, const ModelArgs &a, 
 // compared with ==): the strict engine's own value, or, where a time-parallel engine or the ladder decoded the
 // chunk -- they sum ll in parts, 1e-9 relative -- k_chunk_ll's serial fold along the decoded path.
 bool fit_stops_call(int rc) { return rc == HMMSORT_EHIP || rc == HMMSORT_ENOMEM; }
+
+// ---- Viterbi training on top of the loop (hmmsort_fit_step_channels) -----------------------------------------------
+// A channel that ends well takes the path statistics of its whole recording while signal and stitched path are
+// still in device memory, on a plan of its model (a chunk plan needs no more than the model), and either finishes
+// them into its own record or hands the vector to the caller, who adds the channels' vectors and finishes once.
+enum StepMode { kNoStep = 0, kStepFinish = 1, kStepStats = 2 };
+
+// [mu K*N | sigma | lp nlp | pp S] and the three counts, in host memory, into a caller's record
+int unpack_step(const double *h, const int64_t *counts, int64_t K, int64_t N, int64_t S, int64_t nlp,
+                const hmmsort_step_out &o)
+{
+    if (o.n_lp) *o.n_lp = nlp;
+    HS_CHECK(o.lp_cap >= nlp, HMMSORT_EINVAL, "fit_step_channels: lp too small: need %lld entries, got %lld",
+             (long long)nlp, (long long)o.lp_cap);
+    memcpy(o.mu, h, K * N * sizeof(double));
+    *o.sigma = h[K * N];
+    memcpy(o.lp, h + K * N + 1, nlp * sizeof(double));
+    if (o.pp) memcpy(o.pp, h + K * N + 1 + nlp, S * sizeof(double));
+    if (o.counts) memcpy(o.counts, counts, 3 * sizeof(int64_t));
+    return HMMSORT_OK;
+}
+
+// d_stats (one channel) finished with the plan's model on st, waited for, into the caller's record
+int finish_step(hmmsort_plan *p, const double *d_stats, hipStream_t st, const hmmsort_step_out &o)
+{
+    const HostModel &m = p->model;
+    const int64_t len = hmmsort_plan_mstep_len(p);
+    DevBuf dout, dcnt;
+    int rc;
+    if ((rc = dout.alloc(len * sizeof(double))) || (rc = dcnt.alloc(3 * sizeof(int64_t)))) return rc;
+    if ((rc = plan_path_finish(p, d_stats, dout.as<double>(), dcnt.as<int64_t>(), st))) return rc;
+    std::vector<double> h(len);
+    int64_t counts[3] = {0, 0, 0};
+    HS_HIP(hipMemcpyAsync(h.data(), dout.p, len * sizeof(double), hipMemcpyDeviceToHost, st));
+    HS_HIP(hipMemcpyAsync(counts, dcnt.p, sizeof(counts), hipMemcpyDeviceToHost, st));
+    HS_HIP(hipStreamSynchronize(st));
+    return unpack_step(h.data(), counts, m.K, m.N, m.S, p->eng->n_lp(), o);
+}
 
 struct FitChannel {
     const void *y;
@@ -303,6 +345,13 @@ struct FitChannel {
     bool done = false;
     int status = HMMSORT_OK;      // the channel's code once done
     std::string message;
+
+    // the training step after the decode: what to do with the statistics, where they go, whether they were taken
+    int step_mode = kNoStep;
+    const hmmsort_step_out *step_out = nullptr;
+    std::vector<double> *step_stats = nullptr;
+    DevBuf dstats;
+    bool stepped = false;
 
     FitChannel(const void *y_, int type, int64_t T_, int64_t chunk, const ModelArgs &a_, const Options &o, int16_t *ml,
                double *ll_)
@@ -338,11 +387,49 @@ struct FitChannel {
         return rc;
     }
 
-    int escalated(const void *yc, int64_t n, int16_t *x, double *ll_chunk)
+    int escalated(const void *yc, int64_t n, int16_t *x, double *ll_chunk, const AfterDecode *after = nullptr)
     {
-        int rc = viterbi_host(yc, sample_type, n, a, x, ll_chunk, &opt);
+        int rc = viterbi_host(yc, sample_type, n, a, x, ll_chunk, &opt, after);
         escalations += std::max<int64_t>(last_escalations(), 0);
         return rc;
+    }
+
+    // the statistics of the whole recording (dyp, dxp) on plan p, then this channel's share of the step
+    int step(hmmsort_plan *p, const double *dyp, const int16_t *dxp, hipStream_t s)
+    {
+        const int64_t len = plan_path_stats_len(p);
+        int rc;
+        if ((rc = dstats.ensure(len * sizeof(double)))) return rc;
+        if ((rc = plan_path_stats(p, dyp, dxp, T, 0, T, true, dstats.as<double>(), s))) return rc;
+        stepped = true;
+        if (step_mode == kStepFinish) return finish_step(p, dstats.as<double>(), s, *step_out);
+        step_stats->resize(len);
+        HS_HIP(hipMemcpyAsync(step_stats->data(), dstats.p, len * sizeof(double), hipMemcpyDeviceToHost, s));
+        HS_HIP(hipStreamSynchronize(s));
+        return HMMSORT_OK;
+    }
+
+    // the step of a channel the chunk loop has finished: signal and stitched path are resident, any chunk plan holds
+    // the model.  A one-sample recording never went to the device: it goes now, with a plan made for the purpose.
+    int step_resident()
+    {
+        int rc;
+        if (!path_ready) {
+            if (!st) HS_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+            if ((rc = dy.alloc(T * sizeof(double))) || (rc = dml.alloc(T * sizeof(int16_t)))) return rc;
+            if (sample_type == HMMSORT_SAMPLES_F64) {
+                HS_HIP(hipMemcpyAsync(dy.p, y, T * sizeof(double), hipMemcpyHostToDevice, st));
+            } else {
+                HS_HIP(hipMemcpyAsync(dml.p, y, T * sizeof(int16_t), hipMemcpyHostToDevice, st));
+                if ((rc = dev_widen(dml.p, sample_type, T, 1, dy.as<double>(), st))) return rc;
+            }
+            HS_HIP(hipMemcpyAsync(dml.p, ml_out, T * sizeof(int16_t), hipMemcpyHostToDevice, st));
+        }
+        hmmsort_plan *p = nullptr;
+        for (auto &kv : slots)
+            if (!p && kv.second && kv.second->plan) p = kv.second->plan;
+        if (!p && (rc = plan_for(std::min(chunksize > 0 ? chunksize : T, T), &p))) return rc;
+        return step(p, dy.as<double>(), dml.as<int16_t>(), st);
     }
 
     // uploads the signal, sets the path to ones; a whole-recording decode (chunksize <= 0) is finished here
@@ -350,7 +437,11 @@ struct FitChannel {
     {
         // fit.jl:6-9; one chunk that holds the recording (more than one sample of it) is the same decode
         if (chunksize <= 0 || (chunksize >= T && T > 1)) {
-            int rc = escalated(y, T, ml_out, ll_out);
+            // the step runs on the decode's own slot, before it goes back to the cache
+            const AfterDecode after = [this](hmmsort_plan *p, const double *dyp, const int16_t *dxp, hipStream_t s) {
+                return step(p, dyp, dxp, s);
+            };
+            int rc = escalated(y, T, ml_out, ll_out, step_mode ? &after : nullptr);
             return rc ? guard(rc) : end(HMMSORT_OK);
         }
         if (T == 1) {           // `while j < n` is never entered
@@ -518,6 +609,10 @@ struct FitJob {
     std::vector<std::string> message;
     std::atomic<bool> stop{false};
     std::atomic<int64_t> escalations{0};
+    // hmmsort_fit_step_channels: per-channel records (kStepFinish) or per-channel vectors for the caller (kStepStats)
+    int step_mode = kNoStep;
+    const hmmsort_step_out *step_out = nullptr;
+    std::vector<std::vector<double>> step_stats;
 };
 
 // channels first, first + stride, ... of the job on the current device of the calling thread
@@ -529,7 +624,9 @@ int fit_worker(FitJob &job, int64_t first, int64_t stride)
     int fatal = HMMSORT_OK;
     auto retire = [&](size_t at) {
         FitChannel &ch = *live[at];
-        int rc = ch.collect();
+        int rc = HMMSORT_OK;
+        if (ch.step_mode && ch.status == HMMSORT_OK && !ch.stepped) rc = ch.guard(ch.step_resident());
+        if (!rc) rc = ch.collect();
         job.status[which[at]] = rc ? rc : ch.status;
         job.message[which[at]] = rc ? std::string(last_error()) : ch.message;
         job.escalations += ch.escalations;
@@ -543,6 +640,9 @@ int fit_worker(FitJob &job, int64_t first, int64_t stride)
             live.emplace_back(new FitChannel(job.y[next], job.sample_type, job.T, job.chunksize,
                                              {m.states, m.N, m.K, m.S, m.tr, m.R, m.mu, m.sigma}, job.opt,
                                              job.ml_out[next], &job.ll_out[next]));
+            live.back()->step_mode = job.step_mode;
+            if (job.step_mode == kStepFinish) live.back()->step_out = &job.step_out[next];
+            if (job.step_mode == kStepStats) live.back()->step_stats = &job.step_stats[next];
             which.push_back(next);
             next += stride;
             fatal = live.back()->guard(live.back()->open());
@@ -566,7 +666,8 @@ int fit_worker(FitJob &job, int64_t first, int64_t stride)
 
 int fit_channels_host(int64_t C, const void *const *y, int sample_type, int64_t T, int64_t chunksize,
                       const hmmsort_model *models, const int *devices, int64_t ndev, int16_t *const *ml_out,
-                      double *ll_out, int *status_out, bool prefix)
+                      double *ll_out, int *status_out, bool prefix, int step_mode = kNoStep,
+                      const hmmsort_step_out *step_out = nullptr, std::vector<std::vector<double>> *step_stats = nullptr)
 {
     HS_CHECK(C >= 1 && y && models && ml_out && ll_out, HMMSORT_EINVAL, "fit_channels: null argument or no channel");
     HS_CHECK(T >= 1, HMMSORT_EINVAL, "fit_channels: empty signal (T = %lld)", (long long)T);
@@ -587,6 +688,8 @@ int fit_channels_host(int64_t C, const void *const *y, int sample_type, int64_t 
     job.C = C, job.T = T, job.chunksize = chunksize, job.y = y, job.sample_type = sample_type, job.models = models;
     job.ml_out = ml_out, job.ll_out = ll_out;
     job.opt = options_get();
+    job.step_mode = step_mode, job.step_out = step_out;
+    if (step_mode == kStepStats) job.step_stats.resize(C);
     job.status.assign(C, HMMSORT_EHIP);
     job.message.assign(C, "fit_channels: the call stopped before this channel was decoded");
     last_escalations() = 0;
@@ -631,7 +734,73 @@ int fit_channels_host(int64_t C, const void *const *y, int sample_type, int64_t 
                 set_error("%s", job.message[c].c_str());
             return job.status[c];
         }
+    if (step_stats) *step_stats = std::move(job.step_stats);
     return HMMSORT_OK;
+}
+
+// hmmsort_fit_channels with a Viterbi-training step per channel, or one pooled step for all
+int fit_step_channels_host(int64_t C, const void *const *y, int sample_type, int64_t T, int64_t chunksize,
+                           const hmmsort_model *models, const int *devices, int64_t ndev, bool pooled,
+                           int16_t *const *ml_out, double *ll_out, const hmmsort_step_out *out, int *status_out)
+{
+    HS_CHECK(C >= 1 && y && models && ll_out && out, HMMSORT_EINVAL, "fit_step_channels: null argument or no channel");
+    for (int64_t c = 0; c < (pooled ? 1 : C); c++)
+        HS_CHECK(out[c].mu && out[c].sigma && out[c].lp, HMMSORT_EINVAL,
+                 "fit_step_channels: null pointer in record %lld", (long long)c);
+    for (int64_t c = 0; c < C; c++)
+        HS_CHECK(models[c].states, HMMSORT_EINVAL, "fit_step_channels: null pointer in channel %lld", (long long)c);
+    const hmmsort_model &m0 = models[0];
+    for (int64_t c = 1; pooled && c < C; c++)
+        HS_CHECK(models[c].N == m0.N && models[c].K == m0.K && models[c].S == m0.S &&
+                     !memcmp(models[c].states, m0.states, (size_t)(m0.N * m0.S) * sizeof(int16_t)),
+                 HMMSORT_EINVAL, "fit_step_channels: pooled channels must share N, K, S and the state table (channel %lld "
+                 "differs)", (long long)c);
+    HS_CHECK(T >= 1, HMMSORT_EINVAL, "fit_channels: empty signal (T = %lld)", (long long)T);
+    // a path nobody asked for still has to exist for the statistics
+    std::vector<std::vector<int16_t>> own(C);
+    std::vector<int16_t *> ml(C);
+    for (int64_t c = 0; c < C; c++) {
+        ml[c] = ml_out ? ml_out[c] : nullptr;
+        if (!ml[c]) own[c].resize(T), ml[c] = own[c].data();
+    }
+    std::vector<std::vector<double>> stats;
+    int rc = fit_channels_host(C, y, sample_type, T, chunksize, models, devices, ndev, ml.data(), ll_out, status_out, true,
+                               pooled ? kStepStats : kStepFinish, out, pooled ? &stats : nullptr);
+    if (rc || !pooled) return rc;
+    // the vectors added in channel order; the sum is finished on the device of channel 0 with its model
+    for (int64_t c = 1; c < C; c++) {
+        HS_CHECK(stats[c].size() == stats[0].size(), HMMSORT_EINVAL, "fit_step_channels: channel %lld ended on a plan "
+                 "whose lp' has another layout than channel 0's: its statistics do not pool", (long long)c);
+        for (size_t i = 0; i < stats[0].size(); i++) stats[0][i] += stats[c][i];
+    }
+    int before = 0;
+    HS_HIP(hipGetDevice(&before));
+    if (devices && ndev > 0) HS_HIP(hipSetDevice(devices[0]));
+    const Options opt = options_get();
+    const ModelArgs a = {m0.states, m0.N, m0.K, m0.S, m0.tr, m0.R, m0.mu, m0.sigma};
+    const int64_t n = std::min(chunksize > 0 ? chunksize : T, T);
+    {
+        std::unique_ptr<HostSlot> slot = take_slot(n, a, opt);
+        if (!slot) slot = new_slot(n, opt);
+        if (slot->plan && hmmsort_plan_set_model(slot->plan, a.tr, a.R, a.mu, a.sigma)) slot->drop_plan();
+        if (!slot->plan) rc = plan_create_engine(&slot->plan, n, a.states, a.N, a.K, a.S, a.tr, a.R, a.mu, a.sigma, opt.engine);
+        if (!rc && plan_path_stats_len(slot->plan) != (int64_t)stats[0].size()) {
+            set_error("fit_step_channels: the finishing plan's lp' has another layout than the channels' statistics");
+            rc = HMMSORT_EINVAL;
+        }
+        if (!rc) rc = slot->dstats.ensure(stats[0].size() * sizeof(double));
+        if (!rc && hipMemcpyAsync(slot->dstats.p, stats[0].data(), stats[0].size() * sizeof(double), hipMemcpyHostToDevice,
+                                  slot->st) != hipSuccess) {
+            set_error("fit_step_channels: upload of the pooled statistics failed");
+            (void)hipGetLastError();
+            rc = HMMSORT_EHIP;
+        }
+        if (!rc) rc = finish_step(slot->plan, slot->dstats.as<double>(), slot->st, out[0]);
+        if (slot->st) (void)hipStreamSynchronize(slot->st);   // the host vector leaves scope below
+        if (!rc) give_slot(std::move(slot), opt);
+    }
+    if (devices && ndev > 0) (void)hipSetDevice(before);
+    return rc;
 }
 
 int fit_chunked_host(const void *y, int sample_type, int64_t T, int64_t chunksize, const ModelArgs &a,
@@ -731,6 +900,14 @@ int hmmsort_fit_channels(int64_t C, const void *const *y, int sample_type, int64
 {
     return fit_channels_host(C, y, sample_type, T, chunksize, models, devices, ndev, ml_seq_out, ll_out, status_out,
                              true);
+}
+
+int hmmsort_fit_step_channels(int64_t C, const void *const *y, int sample_type, int64_t T, int64_t chunksize,
+                              const hmmsort_model *models, const int *devices, int64_t ndev, int pooled,
+                              int16_t *const *ml_seq_out, double *ll_out, hmmsort_step_out *out, int *status_out)
+{
+    return fit_step_channels_host(C, y, sample_type, T, chunksize, models, devices, ndev, pooled != 0, ml_seq_out,
+                                  ll_out, out, status_out);
 }
 
 int hmmsort_forward(const double *y, int64_t T, const int16_t *states, int64_t N, int64_t K,

@@ -17,6 +17,12 @@ def _dptr(t):
     return C.c_void_p(t.data_ptr())
 
 
+def stats_sum(d_parts, nparts, length, d_out, stream=0):
+    """d_out[i] = sum over p of d_parts[p][i], p ascending, for `nparts` contiguous device vectors of `length`
+    doubles (hmmsort_stats_sum): the fixed-order, on-device alternative to an all-reduce of statistics vectors."""
+    check(lib().hmmsort_stats_sum(_dptr(d_parts), int(nparts), int(length), _dptr(d_out), C.c_void_p(stream)))
+
+
 class Plan:
     """One recording channel of length T with a fixed model shape."""
 
@@ -130,6 +136,24 @@ class Plan:
         device.  `out`: mstep_len() doubles per channel in mstep's layout; `counts`: three int64 per channel
         (ids outside 1..S, pairs that are no transition of the list, template rows that kept their mean) or None."""
         check(lib().hmmsort_plan_path_update(self._h, _dptr(d_y), _dptr(d_x), _dptr(out), _dptr(counts),
+                                             C.c_void_p(stream)))
+
+    def path_stats_len(self):
+        """doubles per channel of the path statistics: 3 N (K-1) + S + n_lp + 6 (hmmsort_plan_path_stats_len)"""
+        return int(lib().hmmsort_plan_path_stats_len(self._h))
+
+    def path_stats(self, d_y, d_x, T, own_lo, own_hi, first, d_stats, stream=0):
+        """Additive statistics of Viterbi training over samples [own_lo, own_hi) of the arrays d_y / d_x of length
+        T (hmmsort_plan_path_stats).  T is the arrays' length, not the plan's: a plan of chunk length serves a
+        whole recording.  The vectors of shards, chunks or channels add (all-reduce, stats_sum); path_finish
+        turns the sum into the new model."""
+        check(lib().hmmsort_plan_path_stats(self._h, _dptr(d_y), _dptr(d_x), int(T), int(own_lo), int(own_hi),
+                                            int(bool(first)), _dptr(d_stats), C.c_void_p(stream)))
+
+    def path_finish(self, d_stats, out, counts=None, stream=0):
+        """path statistics and the plan's current model -> `out` and `counts` as path_update writes them
+        (hmmsort_plan_path_finish)"""
+        check(lib().hmmsort_plan_path_finish(self._h, _dptr(d_stats), _dptr(out), _dptr(counts),
                                              C.c_void_p(stream)))
 
     def diagnostics(self, stream=0):

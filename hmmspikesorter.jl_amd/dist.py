@@ -51,7 +51,9 @@ def time_shard_plan(y, rank, world_size, lA, mu, sigma, halo=2048):
 
 
 def allreduce_stats(stats, group=None):
-    """In-place SUM all-reduce of a statistics vector (torch tensor on the rank's device)."""
+    """In-place SUM all-reduce of a statistics vector (torch tensor on the rank's device).  It serves the E-step's
+    vectors (Plan.estep) and, as it is, the path statistics of Viterbi training (Plan.path_stats): both are plain
+    sums over time, and the counts of the latter are doubles that add exactly in any order."""
     import torch.distributed as dist
     if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
         dist.all_reduce(stats, op=dist.ReduceOp.SUM, group=group)

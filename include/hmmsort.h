@@ -147,8 +147,9 @@ int hmmsort_viterbi_i16(const int16_t *y, int64_t T, const int16_t *states, int6
  *     the chunk is written or its log-likelihood added;
  *   - fit.jl:41, a chunk's last silent sample is its first one (or it has none), so the next chunk would not
  *     advance (the reference loops forever): found after the chunk is written and its log-likelihood added.
- * Out of scope here: a channels form of hmmsort_em_step, any collective between devices, spike extraction from
- * the resident path, speculative decoding of dependent chunks. */
+ * A training step on top of this loop is hmmsort_fit_step_channels (Viterbi training of one or many channels, C = 1
+ * included).  Out of scope here: a channels form of the soft hmmsort_em_step, any collective between devices, spike
+ * extraction from the resident path, speculative decoding of dependent chunks. */
 int hmmsort_fit_chunked(const double *y, int64_t T, int64_t chunksize, const int16_t *states, int64_t N,
                         int64_t K, int64_t S, const hmm_trans *tr, int64_t R, const double *mu, double sigma,
                         int16_t *ml_seq_out, double *ll_out);
@@ -182,6 +183,33 @@ typedef struct hmmsort_model {
 int hmmsort_fit_channels(int64_t C, const void *const *y, int sample_type, int64_t T, int64_t chunksize,
                          const hmmsort_model *models, const int *devices, int64_t ndev,
                          int16_t *const *ml_seq_out, double *ll_out, int *status_out);
+
+/* what hmmsort_fit_step_channels returns per channel (pooled: record 0 only) */
+typedef struct hmmsort_step_out {
+    double *mu;            /* K x N, receives mu' */
+    double *sigma;         /* 1 */
+    double *lp;            /* lp_cap entries; *n_lp receives the number written (hmmsort_em_step's convention) */
+    int64_t lp_cap;
+    int64_t *n_lp;         /* may be NULL */
+    double *pp;            /* S, may be NULL */
+    int64_t *counts;       /* 3 as hmmsort_plan_path_update's d_counts, may be NULL */
+} hmmsort_step_out;
+
+/* One step of Viterbi training for C channels over a device list: every channel is decoded exactly as
+ * hmmsort_fit_channels decodes it (same arguments, workers, streams, ladder, ml_seq and ll; ml_seq_out or any entry
+ * of it may be NULL here), and while its signal and stitched path are still in device memory the path statistics
+ * of the whole recording are taken (hmmsort_plan_path_stats on a plan of that channel's model: a chunk plan needs
+ * no more than the model) and finished (hmmsort_plan_path_finish).
+ *   pooled == 0: each channel is finished with its own model into out[c].
+ *   pooled != 0: all models must share N, K, S and the state table (else HMMSORT_EINVAL before any GPU work); the
+ *     vectors come to the host, are added in ascending channel order in fp64, go to the device of channel 0 and are
+ *     finished there with models[0] into out[0]: one set of templates for all channels.  Any failing channel fails
+ *     the call.  x0 adds like every slot, so pp' of a pooled step is no channel's first column: pass pp = NULL.
+ * lp_cap too small: HMMSORT_EINVAL.  C = 1 is the hard step inside the chunked native call.  There is no
+ * collective inside the library: the vectors are a few hundred KB at most.  No counterpart in the reference. */
+int hmmsort_fit_step_channels(int64_t C, const void *const *y, int sample_type, int64_t T, int64_t chunksize,
+                              const hmmsort_model *models, const int *devices, int64_t ndev, int pooled,
+                              int16_t *const *ml_seq_out, double *ll_out, hmmsort_step_out *out, int *status_out);
 
 /* forward(V, lA::StateMatrix, mu, sigma) -> alpha (S x T)            baumwelch.jl:25-51 */
 int hmmsort_forward(const double *y, int64_t T, const int16_t *states, int64_t N, int64_t K,
@@ -334,6 +362,40 @@ int hmmsort_plan_mstep(hmmsort_plan *plan, const double *d_stats, double *d_out,
  * inputs give the same bits.  Asynchronous on `stream`. */
 int hmmsort_plan_path_update(hmmsort_plan *plan, const double *d_y, const int16_t *d_x, double *d_out,
                              int64_t *d_counts, void *stream);
+/* The same update from additive statistics, for time shards, chunked paths and pooled channels.
+ * hmmsort_plan_path_stats takes the statistics of samples [own_lo, own_hi) of the arrays d_y / d_x of length T.
+ * T is the length of the ARRAYS, not of the plan: the call uses the plan's model and nothing of its engine, so a
+ * plan of chunk length serves the stitched path of a whole recording (workspace grows on demand).  Batched plans
+ * take channel-major [C][T] arrays and T must be the plan's (HMMSORT_EINVAL otherwise).  The range is explicit and
+ * independent of hmmsort_plan_set_shard, so it exists on blocked and strict plans too; 0 <= own_lo <= own_hi <= T
+ * (else HMMSORT_EINVAL), an empty range gives a zero vector.  Pairs (t, t+1) are counted for t owned and t+1 < T:
+ * an interior shard reads x[own_hi] in its halo and owns that pair.  `first`: the arrays start the recording.
+ * d_stats receives hmmsort_plan_path_stats_len() doubles PER CHANNEL, with NE = N (K-1) and n_lp as in
+ * hmmsort_plan_mstep_len:
+ *   [ c (NE) | s (NE) | sm (NE) | n_j (S) | ent (n_lp) | b | sum_y2 | n | x0 | bad0 | bad1 ]    3 NE + S + n_lp + 6
+ *   c, s    count and sum of y per entry e = l (K-1) + (k-2) over samples whose state has template l alone, at phase k
+ *   sm      sum of y over samples in states with two or more active templates, entered once per active template
+ *   n_j     samples in each such state j (0 for the other states)
+ *   ent, b  the counts behind lp': transitions 1 -> dst_i, and samples in state 1 that have a successor
+ *   sum_y2, n   over the owned samples with a valid id;  bad0, bad1: counts [0] and [1] of hmmsort_plan_path_update
+ *   x0      the id x[0] when `first`, own_lo == 0 and the id is valid, else 0
+ * Counts are doubles (exact to 2^53), so the vectors of shards, chunks or channels add in any order without error
+ * in the integer slots: SUM all-reduce, or hmmsort_stats_sum.  No floating-point atomics: the vector is a fixed
+ * function of (y, x, model, range).
+ * hmmsort_plan_path_finish turns one such vector per channel and the plan's current model (kept rows, slot order)
+ * into d_out / d_counts as hmmsort_plan_path_update writes them.  sigma'^2 = (sum_y2 - 2 sum_e mu'_e (s_e + sm_e)
+ * + sum_e c_e mu'_e^2 + sum_j n_j M_j^2) / n with M_j the state means of the new templates, clamped at 0.
+ * For own = [0, T), first = 1 and T the plan's, mu', lp', pp' and the counts equal hmmsort_plan_path_update's bit
+ * for bit (same tiles, same order); sigma' agrees within the rounding of the four sums.
+ * One statistics call at a time per plan (they share its workspace).  All asynchronous on `stream`. */
+int64_t hmmsort_plan_path_stats_len(const hmmsort_plan *plan);              /* per channel */
+int hmmsort_plan_path_stats(hmmsort_plan *plan, const double *d_y, const int16_t *d_x, int64_t T, int64_t own_lo,
+                            int64_t own_hi, int first, double *d_stats, void *stream);
+int hmmsort_plan_path_finish(hmmsort_plan *plan, const double *d_stats, double *d_out, int64_t *d_counts,
+                             void *stream);
+/* d_out[i] = d_parts[0][i] + d_parts[1][i] + ... in ascending order, for nparts contiguous device vectors of len
+ * doubles: the on-device, fixed-order alternative to an all-reduce, for any statistics vector of the library. */
+int hmmsort_stats_sum(const double *d_parts, int64_t nparts, int64_t len, double *d_out, void *stream);
 /* doubles hmmsort_plan_mstep writes PER CHANNEL: K*N + 1 + n_lp + S, n_lp = N for wave/ring plans (also when
  * the list has lost a vanished template's entry transitions, types.jl:121: its slot stays, value -Inf or the
  * re-estimate), (#transitions leaving state 1) - 1 for the blocked engine (baumwelch.jl:226,264). */

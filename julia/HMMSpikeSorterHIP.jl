@@ -162,6 +162,64 @@ function viterbi_step(X::Array{Float64,1}, state_matrix::StateMatrix, μ0::Array
     return_path ? (out..., x, ll[]) : out
 end
 
+# struct hmmsort_step_out (include/hmmsort.h): what hmmsort_fit_step_channels returns per channel
+struct CStepOut
+    mu::Ptr{Float64}; sigma::Ptr{Float64}; lp::Ptr{Float64}; lp_cap::Int64; n_lp::Ptr{Int64}
+    pp::Ptr{Float64}; counts::Ptr{Int64}
+end
+
+"""
+    fit_step_channels(templates, X, chunksize; devices=Int[], pooled=false) -> (models, steps)
+
+One step of Viterbi training for several channels in one call (`hmmsort_fit_step_channels`, INTEGRATION.md
+"Viterbi training"): every channel is decoded as `fit_channels` decodes it, and re-estimated from the statistics of
+its stitched path while signal and path are on the GPU.  `steps[c] = (state_matrix′, μ′, σ′)`; with `pooled` the
+channels' statistics are added in channel order and finished with the first channel's model: `steps` has one entry
+(its first column is the old model's).
+"""
+function fit_step_channels(templates::Vector{HMMSpikeTemplateModel}, X::Vector{Vector{T}}, chunksize::Integer;
+                           devices::Vector{<:Integer}=Int[], pooled::Bool=false) where T <: Union{Float64,Int16}
+    C = length(X); n = length(X[1]); nout = pooled ? 1 : C
+    length(templates) == C && all(length(x) == n for x in X) || error("fit_step_channels: one model per channel, equal lengths")
+    ml = [zeros(Int16, n) for _ in 1:C]; ll = zeros(Float64, C); status = zeros(Cint, C)
+    dev = Cint.(devices)
+    sms = [t.state_matrix for t in templates[1:nout]]
+    μs = [zeros(Float64, s.K, s.N) for s in sms]; σs = [zeros(Float64, 1) for _ in sms]
+    lps = [zeros(Float64, length(s.transitions)) for s in sms]; nlps = [zeros(Int64, 1) for _ in sms]
+    pps = [zeros(Float64, s.nstates) for s in sms]
+    GC.@preserve templates X ml dev μs σs lps nlps pps begin
+        models = [CModel(pointer(t.state_matrix.states), t.state_matrix.N, t.state_matrix.K, t.state_matrix.nstates,
+                         Ptr{Cvoid}(pointer(t.state_matrix.transitions)), length(t.state_matrix.transitions),
+                         pointer(t.μ), t.σ) for t in templates]
+        recs = [CStepOut(pointer(μs[c]), pointer(σs[c]), pointer(lps[c]), length(lps[c]), pointer(nlps[c]),
+                         pooled ? Ptr{Float64}(C_NULL) : pointer(pps[c]), Ptr{Int64}(C_NULL)) for c in 1:nout]
+        ys = [Ptr{Cvoid}(pointer(x)) for x in X]; outs = [pointer(m) for m in ml]
+        check(ccall((:hmmsort_fit_step_channels, lib), Cint,
+            (Int64, Ptr{Ptr{Cvoid}}, Cint, Int64, Int64, Ptr{CModel}, Ptr{Cint}, Int64, Cint, Ptr{Ptr{Int16}},
+             Ptr{Float64}, Ptr{CStepOut}, Ptr{Cint}),
+            C, ys, T === Int16 ? HMMSORT_SAMPLES_I16 : HMMSORT_SAMPLES_F64, n, chunksize, models,
+            isempty(dev) ? Ptr{Cint}(C_NULL) : pointer(dev), length(dev), pooled ? 1 : 0, outs, ll, recs, status))
+    end
+    steps = [_finish(sms[c], μs[c], Ref(σs[c][1]), lps[c], Ref(nlps[c][1]), pooled ? sms[c].π : pps[c]) for c in 1:nout]
+    [HMMSpikingModel(templates[c], ml[c], ll[c], X[c]) for c in 1:C], steps
+end
+
+# The additive statistics of Viterbi training on the device-resident plan API (include/hmmsort.h): `plan` is a
+# hmmsort_plan*, the arrays are device pointers, `stream` a hipStream_t or C_NULL.  T is the length of the arrays.
+path_stats_len(plan::Ptr{Cvoid}) = ccall((:hmmsort_plan_path_stats_len, lib), Int64, (Ptr{Cvoid},), plan)
+path_stats!(plan::Ptr{Cvoid}, d_y::Ptr{Float64}, d_x::Ptr{Int16}, T::Integer, own_lo::Integer, own_hi::Integer,
+            first::Bool, d_stats::Ptr{Float64}, stream::Ptr{Cvoid}=C_NULL) =
+    check(ccall((:hmmsort_plan_path_stats, lib), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Int16}, Int64, Int64, Int64, Cint, Ptr{Float64}, Ptr{Cvoid}),
+        plan, d_y, d_x, T, own_lo, own_hi, first ? 1 : 0, d_stats, stream))
+path_finish!(plan::Ptr{Cvoid}, d_stats::Ptr{Float64}, d_out::Ptr{Float64}, d_counts::Ptr{Int64}=Ptr{Int64}(C_NULL),
+             stream::Ptr{Cvoid}=C_NULL) =
+    check(ccall((:hmmsort_plan_path_finish, lib), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Cvoid}), plan, d_stats, d_out, d_counts, stream))
+stats_sum!(d_parts::Ptr{Float64}, nparts::Integer, len::Integer, d_out::Ptr{Float64}, stream::Ptr{Cvoid}=C_NULL) =
+    check(ccall((:hmmsort_stats_sum, lib), Cint, (Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Cvoid}),
+        d_parts, nparts, len, d_out, stream))
+
 function reconstruct_signal(x::Array{T,1}, lA::StateMatrix, μ::Array{Float64,2}, σ::Float64) where T <: Integer
     xs = T === Int16 ? x : Int16.(x)
     Y2 = zeros(Float64, length(xs))

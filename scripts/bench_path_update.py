@@ -1,6 +1,7 @@
 """Viterbi training, device-resident (plan API): per model the decode (hmmsort_plan_viterbi), the path update
-(hmmsort_plan_path_update) and, for comparison, the soft step of the same plan (hmmsort_plan_estep +
-hmmsort_plan_mstep).  HIP events on the current stream, median of the timed calls after warm-up; one JSON line per
+(hmmsort_plan_path_update), the same update from additive statistics (hmmsort_plan_path_stats +
+hmmsort_plan_path_finish: one pass over the signal) and, for comparison, the soft step of the same plan
+(hmmsort_plan_estep + hmmsort_plan_mstep).  HIP events on the current stream, median of the timed calls after warm-up; one JSON line per
 model.  The update's byte floor is two passes over 10 bytes per sample (8 of y, 2 of x).
 
     python scripts/bench_path_update.py [--samples 10000000] [--reps 11] [--soft-samples-big 200000] [--models ring4,ov2,ov4]
@@ -67,6 +68,20 @@ def run(name, T, reps, soft_T):
         res["update_fraction_of_floor"] = (2 * 10 * T / HBM_PEAK) / med
         res["update_over_decode"] = res["path_update_ms"][0] / res["viterbi_ms"][0]
         res["hard_step_Msamples_s"] = T / ((res["viterbi_ms"][0] + res["path_update_ms"][0]) * 1e-3) / 1e6
+        # the statistics form: one pass over (y, x), then a finish that does not touch the signal
+        stats = torch.zeros(plan.path_stats_len(), dtype=torch.float64, device="cuda")
+        out2 = torch.zeros(plan.mstep_len(), dtype=torch.float64, device="cuda")
+
+        def stats_finish():
+            plan.path_stats(dy, dx, T, 0, T, True, stats)
+            plan.path_finish(stats, out2, cnt)
+        res["path_stats_ms"] = timed(lambda: plan.path_stats(dy, dx, T, 0, T, True, stats), reps)
+        res["path_finish_ms"] = timed(lambda: plan.path_finish(stats, out2, cnt), reps)
+        res["stats_finish_ms"] = timed(stats_finish, reps)
+        res["stats_finish_over_update"] = res["stats_finish_ms"][0] / res["path_update_ms"][0]
+        K, nn = sm.K, sm.N
+        res["same_mu_lp_pp"] = bool(torch.equal(out[:K * nn], out2[:K * nn]) and torch.equal(out[K * nn + 1:], out2[K * nn + 1:]))
+        res["sigma_update_stats"] = [float(out[K * nn]), float(out2[K * nn])]
     finally:
         plan.close()
     # the soft step of the same plan; the 21 123-state model at a length that finishes
