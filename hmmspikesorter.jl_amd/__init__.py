@@ -7,11 +7,11 @@ import it through the root-level shim:  `import hmmsort_amd`.
 from . import _lib, dist, synth
 from ._lib import (ENGINE_AUTO, ENGINE_BLOCKED, ENGINE_RING, ENGINE_STRICT, ENGINE_WAVE, HmmsortError, device_count,
                    get_option, set_option, shutdown)
-from .api import (HMMSpikeTemplateModel, HMMSpikingModel, Posteriors, StateMatrix, backward, extract_spiketimes,
-                  fit, fit_channels, fit_step_channels, forward,
-                  posterior_decode, posteriors, predict, reconstruct_signal, spike_confidence, train_model, train_step, unroll_mlseq, update,
+from .api import (HMMSpikeTemplateModel, HMMSpikingModel, ModelTrack, Posteriors, StateMatrix, backward,
+                  extract_spiketimes, fit, fit_adaptive, fit_channels, fit_step_channels, forward,
+                  posterior_decode, posteriors, predict, reconstruct_signal, reconstruct_tracked, spike_confidence, train_model, train_step, unroll_mlseq, update,
                   viterbi, viterbi_step)
-from .device import Plan, stats_sum
+from .device import Plan, stats_blend, stats_sum
 from .postprocess import (condense_candidates, condense_templates, find_best_overlap, match_templates,
                           prune_templates, remove_small, remove_sparse)
 from .sortdata import get_lp, sort_data
@@ -24,4 +24,4 @@ __all__ = ["StateMatrix", "HMMSpikeTemplateModel", "HMMSpikingModel", "forward",
            "ENGINE_RING", "ENGINE_BLOCKED", "ENGINE_WAVE", "get_lp", "sort_data", "find_best_overlap",
            "condense_candidates", "condense_templates", "remove_sparse", "remove_small", "prune_templates",
            "match_templates", "Posteriors", "posteriors", "posterior_decode", "spike_confidence",
-           "viterbi_step"]
+           "viterbi_step", "fit_adaptive", "reconstruct_tracked", "ModelTrack", "stats_blend"]

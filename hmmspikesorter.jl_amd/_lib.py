@@ -50,6 +50,16 @@ class StepOut(C.Structure):
                 ("counts", _vp)]
 
 
+class Adapt(C.Structure):
+    """struct hmmsort_adapt: how hmmsort_fit_adaptive forgets and when it starts to re-estimate"""
+    _fields_ = [("halflife", _f64), ("warmup", _i64), ("update_sigma", _int), ("update_lp", _int)]
+
+
+class Track(C.Structure):
+    """struct hmmsort_track: the caller's arrays of `cap` records hmmsort_fit_adaptive fills, one per chunk"""
+    _fields_ = [("cap", _i64), ("n", _vp), ("first", _vp), ("own", _vp), ("w", _vp), ("mu", _vp), ("sigma", _vp)]
+
+
 # name -> (restype, argtypes); every symbol include/hmmsort.h declares
 SIGNATURES = {
     "hmmsort_last_error": (C.c_char_p, []),
@@ -69,6 +79,10 @@ SIGNATURES = {
                                     C.POINTER(_vp), _vp, C.POINTER(_int)]),
     "hmmsort_fit_step_channels": (_int, [_i64, C.POINTER(_vp), _int, _i64, _i64, C.POINTER(Model), C.POINTER(_int),
                                          _i64, _int, C.POINTER(_vp), _vp, C.POINTER(StepOut), C.POINTER(_int)]),
+    "hmmsort_fit_adaptive": (_int, [_vp, _int, _i64, _i64, C.POINTER(Model), C.POINTER(Adapt), _vp, _vp,
+                                    C.POINTER(Track), C.POINTER(StepOut)]),
+    "hmmsort_stats_blend": (_int, [_vp, _f64, _vp, _i64, _i64, _vp]),
+    "hmmsort_reconstruct_tracked": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
     "hmmsort_chunk_stitch": (_int, [_vp, _i64, _int, _int, _vp, _vp, _vp]),
     "hmmsort_samples_to_f64": (_int, [_vp, C.c_int, _i64, _i64, _vp, _vp]),
     "hmmsort_forward": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _f64, _vp]),

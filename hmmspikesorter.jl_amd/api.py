@@ -13,8 +13,8 @@ Reference methods mirrored (file:line relative to the reference root):
   reconstruct_signal                                                  src/reconstruction.jl:1
   unroll_mlseq                                                        src/extraction.jl:4
   fit(HMMSpikingModel, templates, X, chunksize)                       src/fit.jl:11-42
-Extensions (no counterpart in the reference): posteriors, posterior_decode, spike_confidence, fit_step_channels, viterbi_step and
-train_model(..., method="viterbi").
+Extensions (no counterpart in the reference): posteriors, posterior_decode, spike_confidence, fit_step_channels, viterbi_step,
+train_model(..., method="viterbi"), fit_adaptive and reconstruct_tracked.
 """
 import ctypes as C
 from dataclasses import dataclass
@@ -596,6 +596,92 @@ def fit_step_channels(templates, X, chunksize=None, devices=None, pooled=False):
         lA_new = StateMatrix.from_states(lA.states, pp, lA.K, b["lp"][:int(b["nlp"][0])].copy(), lA.resolve_overlaps)
         steps.append((lA_new, b["mu"], float(b["sigma"][0]), b["counts"].tolist()))
     return [HMMSpikingModel(tms[c], ml[c], float(ll[c]), rows[c]) for c in range(nch)], steps
+
+
+@dataclass
+class ModelTrack:
+    """What fit_adaptive's chunk loop did, one entry per decoded chunk (struct hmmsort_track)."""
+    n: int               # chunks decoded
+    first: np.ndarray    # n, fit.jl's i of each chunk (1-based)
+    own: np.ndarray      # n x 2, the 0-based range [lo, hi) whose statistics the chunk contributed
+    w: np.ndarray        # n, the weight the accumulator was multiplied by before the chunk's statistics were added
+    mu: np.ndarray       # n x K x N, the templates each chunk was DECODED with
+    sigma: np.ndarray    # n
+    final: tuple = None  # (state_matrix', mu', sigma', counts): the full re-estimate after the last chunk
+
+
+def _fit_adaptive_call(templates, X, chunksize, halflife, warmup, update_sigma, update_lp, cap=None, want_final=True):
+    """hmmsort_fit_adaptive without raising: (rc, ml_seq, ll, ModelTrack of the first `cap` records, X as passed)"""
+    raw = isinstance(X, np.ndarray) and X.dtype == np.int16 and X.ndim == 1
+    X = np.ascontiguousarray(X) if raw else _signal(X)
+    lA = templates.state_matrix
+    keep, margs = _model_args(lA, templates.mu, templates.sigma)
+    model = _lib.Model(*margs)
+    n = len(X)
+    cs = 0 if chunksize is None else int(chunksize)
+    grow = cap is None   # a guessed capacity is corrected by a second run; a caller's own is kept
+    if grow:
+        cap = 2 * (n // cs + 1) + 2 if cs > 0 else 1
+    K, N, S = lA.K, lA.N, lA.nstates
+    while True:
+        ml = np.zeros(n, dtype=np.int16)
+        ll = np.zeros(1)
+        b = dict(n=np.zeros(1, dtype=np.int64), first=np.zeros(cap, dtype=np.int64),
+                 own=np.zeros((cap, 2), dtype=np.int64), w=np.zeros(cap), mu=np.zeros((cap, K * N)), sigma=np.zeros(cap))
+        track = _lib.Track(cap, *[b[k].ctypes.data for k in ("n", "first", "own", "w", "mu", "sigma")])
+        f = dict(mu=np.zeros((K, N), order="F"), sigma=np.zeros(1), lp=np.zeros(len(keep[1])),
+                 nlp=np.zeros(1, dtype=np.int64), pp=np.zeros(S), counts=np.zeros(3, dtype=np.int64))
+        rec = _lib.StepOut(f["mu"].ctypes.data, f["sigma"].ctypes.data, f["lp"].ctypes.data, len(f["lp"]),
+                           f["nlp"].ctypes.data, f["pp"].ctypes.data, f["counts"].ctypes.data)
+        opt = _lib.Adapt(float(halflife), int(warmup), int(bool(update_sigma)), int(bool(update_lp)))
+        rc = lib().hmmsort_fit_adaptive(ptr(X), _lib.SAMPLES_I16 if raw else _lib.SAMPLES_F64, n, cs, C.byref(model),
+                                        C.byref(opt), ptr(ml), ptr(ll), C.byref(track),
+                                        C.byref(rec) if want_final else None)
+        nrec = int(b["n"][0])
+        if rc == 0 and nrec > cap and grow:   # more chunks than guessed: the loop is deterministic, run it again
+            cap = nrec
+            continue
+        break
+    m = min(nrec, cap)
+    final = None
+    if rc == 0 and want_final:
+        lA_new = StateMatrix.from_states(lA.states, f["pp"], K, f["lp"][:int(f["nlp"][0])].copy(), lA.resolve_overlaps)
+        final = (lA_new, f["mu"], float(f["sigma"][0]), f["counts"].tolist())
+    tk = ModelTrack(nrec, b["first"][:m], b["own"][:m], b["w"][:m],
+                    b["mu"][:m].reshape((m, N, K)).transpose(0, 2, 1), b["sigma"][:m], final)
+    return rc, ml, float(ll[0]), tk, X
+
+
+def fit_adaptive(templates, X, chunksize, halflife, warmup=0, update_sigma=True, update_lp=False):
+    """Drift-tracking chunked decode (hmmsort_fit_adaptive; an extension, INTEGRATION.md "Drift tracking"): fit(...,
+    chunksize) with the model re-estimated between chunks from exponentially weighted statistics of the decoded
+    path, so that templates follow slow changes of the recording.  `halflife`: samples after which a statistic
+    weighs one half (inf: never forget); `warmup`: samples that must have entered the statistics before the model
+    is first replaced; `update_sigma` / `update_lp`: whether the noise level and the transition list follow too.
+    With `update_lp` a template that does not fire within memory loses its entry transition and cannot come back:
+    off by default.
+
+    Returns (HMMSpikingModel, ModelTrack): the stitched path and the sum of the chunks' log-likelihoods, each under
+    the model its chunk was decoded with, beside the caller's templates; and the model track (reconstruct_tracked
+    gives the reconstruction that goes with it)."""
+    rc, ml, ll, tk, X = _fit_adaptive_call(templates, X, chunksize, halflife, warmup, update_sigma, update_lp)
+    check(rc)
+    return HMMSpikingModel(templates, ml, ll, X), tk
+
+
+def reconstruct_tracked(x, lA, track):
+    """reconstruct_signal under a model track: sample t takes the templates of the last chunk of `track` whose
+    first sample is <= t (hmmsort_reconstruct_tracked).  State ids outside 1..S give NaN."""
+    x = np.ascontiguousarray(x, dtype=np.int16)
+    st = np.asfortranarray(lA.states, dtype=np.int16)
+    first = np.ascontiguousarray(track.first, dtype=np.int64)
+    mu = np.ascontiguousarray(np.asarray(track.mu, dtype=np.float64).transpose(0, 2, 1))   # [n][K*N], column-major each
+    if mu.ndim != 3 or mu.shape != (len(first), lA.N, lA.K):
+        raise ValueError("reconstruct_tracked: track.mu must be n x K x N = %d x %d x %d" % (len(first), lA.K, lA.N))
+    out = np.zeros(len(x), dtype=np.float64)
+    check(lib().hmmsort_reconstruct_tracked(ptr(x), len(x), ptr(st), lA.N, lA.nstates, lA.K, len(first), ptr(first),
+                                            ptr(mu), ptr(out)))
+    return out
 
 
 def predict(model):

@@ -371,6 +371,18 @@ int hmmsort_stats_sum(const double *d_parts, int64_t nparts, int64_t len, double
     return dev_stats_sum(d_parts, nparts, len, d_out, (hipStream_t)stream);
 }
 
+int hmmsort_stats_blend(double *d_acc, double w, const double *d_new, int64_t len, int64_t plain_tail, void *stream)
+{
+    HS_CHECK(w >= 0.0 && w <= 1.0, HMMSORT_EINVAL, "stats_blend: weight %g outside [0, 1]", w);
+    HS_CHECK(plain_tail >= 0 && len >= plain_tail, HMMSORT_EINVAL, "stats_blend: %lld entries, %lld of them unweighted",
+             (long long)len, (long long)plain_tail);
+    HS_CHECK(len == 0 || (d_acc && d_new), HMMSORT_EINVAL, "stats_blend: null argument");
+    HS_CHECK(len <= (int64_t)2147483647 * 256, HMMSORT_EUNSUP, "stats_blend: vector too long");
+    int rc;
+    if ((rc = need_device())) return rc;
+    return dev_stats_blend(d_acc, w, d_new, len, plain_tail, (hipStream_t)stream);
+}
+
 int hmmsort_plan_diagnostics(hmmsort_plan *p, void *stream, int64_t diag[8])
 {
     HS_CHECK(p && diag, HMMSORT_EINVAL, "plan_diagnostics: null argument");
@@ -460,6 +472,43 @@ int hmmsort_reconstruct(const int16_t *x, int64_t T, const int16_t *states, int6
     HS_HIP(hipMemcpy(dmu.p, mu, K * N * sizeof(double), hipMemcpyHostToDevice));
     rc = dev_reconstruct(dx.as<int16_t>(), T, dst.as<int16_t>(), N, S, dmu.as<double>(), K,
                          dout.as<double>(), nullptr);
+    if (rc) return rc;
+    HS_HIP(hipDeviceSynchronize());
+    HS_HIP(hipMemcpy(y_out, dout.p, T * sizeof(double), hipMemcpyDeviceToHost));
+    return HMMSORT_OK;
+}
+
+int hmmsort_reconstruct_tracked(const int16_t *x, int64_t T, const int16_t *states, int64_t N, int64_t S, int64_t K,
+                                int64_t nchunks, const int64_t *first, const double *mu_track, double *y_out)
+{
+    HS_CHECK(states && first && mu_track && (T == 0 || (x && y_out)), HMMSORT_EINVAL,
+             "reconstruct_tracked: null argument");
+    HS_CHECK(T >= 0 && N >= 1 && S >= 1 && K >= 1 && nchunks >= 1, HMMSORT_EINVAL, "reconstruct_tracked: bad sizes");
+    HS_CHECK(first[0] >= 1, HMMSORT_EINVAL, "reconstruct_tracked: first[0] = %lld is no 1-based sample number",
+             (long long)first[0]);
+    for (int64_t c = 1; c < nchunks; c++)
+        HS_CHECK(first[c] > first[c - 1], HMMSORT_EINVAL, "reconstruct_tracked: chunk starts must ascend (first[%lld] = "
+                 "%lld after %lld)", (long long)c, (long long)first[c], (long long)first[c - 1]);
+    HS_CHECK(nchunks <= kTrackChunks, HMMSORT_EUNSUP, "reconstruct_tracked: %lld chunks (at most %lld)",
+             (long long)nchunks, (long long)kTrackChunks);
+    if (T == 0) return HMMSORT_OK;
+    int rc = need_device();
+    if (rc) return rc;
+    // every phase the table names must be a row of the templates: the device code indexes with it
+    for (int64_t i = 0; i < N * S; i++)
+        HS_CHECK(states[i] >= 1 && states[i] <= K, HMMSORT_EINVAL, "reconstruct_tracked: states[%lld] = %d outside 1..K",
+                 (long long)i, (int)states[i]);
+    DevBuf dx, dst, dfirst, dmu, dout;
+    if ((rc = dx.alloc(T * sizeof(int16_t))) || (rc = dst.alloc(N * S * sizeof(int16_t))) ||
+        (rc = dfirst.alloc(nchunks * sizeof(int64_t))) || (rc = dmu.alloc(nchunks * K * N * sizeof(double))) ||
+        (rc = dout.alloc(T * sizeof(double))))
+        return rc;
+    HS_HIP(hipMemcpy(dx.p, x, T * sizeof(int16_t), hipMemcpyHostToDevice));
+    HS_HIP(hipMemcpy(dst.p, states, N * S * sizeof(int16_t), hipMemcpyHostToDevice));
+    HS_HIP(hipMemcpy(dfirst.p, first, nchunks * sizeof(int64_t), hipMemcpyHostToDevice));
+    HS_HIP(hipMemcpy(dmu.p, mu_track, nchunks * K * N * sizeof(double), hipMemcpyHostToDevice));
+    rc = dev_reconstruct_tracked(dx.as<int16_t>(), T, dst.as<int16_t>(), N, S, K, nchunks, dfirst.as<int64_t>(),
+                                 dmu.as<double>(), dout.as<double>(), nullptr);
     if (rc) return rc;
     HS_HIP(hipDeviceSynchronize());
     HS_HIP(hipMemcpy(y_out, dout.p, T * sizeof(double), hipMemcpyDeviceToHost));

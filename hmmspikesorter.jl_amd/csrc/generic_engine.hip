@@ -249,6 +249,41 @@ __global__ void k_reconstruct(const int16_t *__restrict__ x, int64_t T,
     }
 }
 
+// reconstruct_signal under a model track: the chunk starts (1-based, ascending) sit in LDS and every thread looks up
+// the last one that is <= its sample by bisection; that chunk's templates are read from mu_track [nchunks][K*N]
+__global__ __launch_bounds__(256) void k_reconstruct_tracked(const int16_t *__restrict__ x, int64_t T,
+                                                             const int16_t *__restrict__ states, int N, int S, int K,
+                                                             int nchunks, const int64_t *__restrict__ first,
+                                                             const double *__restrict__ mu_track,
+                                                             double *__restrict__ out)
+{
+    extern __shared__ int64_t s_first[];
+    for (int c = threadIdx.x; c < nchunks; c += blockDim.x) s_first[c] = first[c];
+    __syncthreads();
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; i < T; i += stride) {
+        // chunks [0, lo) start at or before sample i + 1
+        int lo = 0, hi = nchunks;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (s_first[mid] <= i + 1)
+                lo = mid + 1;
+            else
+                hi = mid;
+        }
+        const int xs = x[i];
+        double a = 0.0;
+        if (lo >= 1 && xs >= 1 && xs <= S) {
+            const double *mu = mu_track + (int64_t)(lo - 1) * K * N;
+            for (int j = 0; j < N; j++) a += mu[(states[j + N * (xs - 1)] - 1) + K * j];
+        } else {
+            a = NAN;
+        }
+        out[i] = a;
+    }
+}
+
 __global__ void k_unroll(const int16_t *__restrict__ x, int64_t T,
                          const int16_t *__restrict__ states, int N, int S,
                          int16_t *__restrict__ out)
@@ -325,6 +360,21 @@ int dev_reconstruct(const int16_t *d_x, int64_t T, const int16_t *d_states, int6
     int blocks = (int)std::min<int64_t>((T + 255) / 256, 4096);
     hipLaunchKernelGGL(k_reconstruct, dim3(blocks), dim3(256), 0, st, d_x, T, d_states, (int)N,
                        (int)S, d_mu, (int)K, d_out);
+    HS_HIP(hipGetLastError());
+    return HMMSORT_OK;
+}
+
+int dev_reconstruct_tracked(const int16_t *d_x, int64_t T, const int16_t *d_states, int64_t N, int64_t S, int64_t K,
+                            int64_t nchunks, const int64_t *d_first, const double *d_mu_track, double *d_out,
+                            hipStream_t st)
+{
+    if (T <= 0) return HMMSORT_OK;
+    HS_CHECK(nchunks >= 1 && nchunks <= kTrackChunks, HMMSORT_EUNSUP,
+             "reconstruct_tracked: %lld chunks (the table of chunk starts holds 1..%lld)", (long long)nchunks,
+             (long long)kTrackChunks);
+    int blocks = (int)std::min<int64_t>((T + 255) / 256, 4096);
+    hipLaunchKernelGGL(k_reconstruct_tracked, dim3(blocks), dim3(256), (size_t)nchunks * sizeof(int64_t), st, d_x, T,
+                       d_states, (int)N, (int)S, (int)K, (int)nchunks, d_first, d_mu_track, d_out);
     HS_HIP(hipGetLastError());
     return HMMSORT_OK;
 }

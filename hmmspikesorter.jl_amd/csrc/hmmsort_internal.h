@@ -296,6 +296,12 @@ bool ring_supported(const HostModel &m, int64_t T, std::string *why);
 // misc device helpers (generic_engine.hip)
 int dev_reconstruct(const int16_t *d_x, int64_t T, const int16_t *d_states, int64_t N, int64_t S,
                     const double *d_mu, int64_t K, double *d_out, hipStream_t st);
+// the same under a model track: sample t takes the templates of the last chunk whose 1-based first sample is <= t + 1
+// (d_first: nchunks <= kTrackChunks ascending values, d_mu_track: [nchunks][K*N])
+constexpr int64_t kTrackChunks = 8192;
+int dev_reconstruct_tracked(const int16_t *d_x, int64_t T, const int16_t *d_states, int64_t N, int64_t S, int64_t K,
+                            int64_t nchunks, const int64_t *d_first, const double *d_mu_track, double *d_out,
+                            hipStream_t st);
 int dev_widen(const void *d_in, int dtype, int64_t T, int64_t stride, double *d_out, hipStream_t st);
 constexpr int kSpikeChunkHost = 4096;
 int dev_spike_compact(const int16_t *d_x, int64_t T, const uint32_t *d_match, int N, int S, int pass,
@@ -361,5 +367,7 @@ int plan_path_stats(hmmsort_plan *p, const double *d_y, const int16_t *d_x, int6
                     bool first, double *d_stats, hipStream_t st);
 int plan_path_finish(hmmsort_plan *p, const double *d_stats, double *d_out, int64_t *d_counts, hipStream_t st);
 int dev_stats_sum(const double *d_parts, int64_t nparts, int64_t len, double *d_out, hipStream_t st);
+// acc[i] = w * acc[i] + new[i] in two rounded steps for i < len - plain_tail, acc[i] += new[i] for the rest
+int dev_stats_blend(double *d_acc, double w, const double *d_new, int64_t len, int64_t plain_tail, hipStream_t st);
 void host_slots_trim(size_t keep);   // idle plans of the host-buffer entry points: keep the newest `keep`
 }  // namespace hmmsort

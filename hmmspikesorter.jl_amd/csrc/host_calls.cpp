@@ -4,6 +4,7 @@
 // certificates fail.  No CPU compute path exists here.
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <cstring>
 #include <functional>
 #include <map>
@@ -322,7 +323,7 @@ struct FitChannel {
     const void *y;
     const int sample_type;
     const int64_t T, chunksize;
-    const ModelArgs a;
+    ModelArgs a;                  // the caller's model; a channel that re-estimates it points this at its own copy
     const Options &opt;
     int16_t *const ml_out;
     double *const ll_out;
@@ -432,6 +433,14 @@ struct FitChannel {
         return step(p, dy.as<double>(), dml.as<int16_t>(), st);
     }
 
+    bool has_twins() const
+    {
+        for (int64_t p = 0; p < a.N; p++)
+            for (int64_t q = p + 1; q < a.N; q++)
+                if (std::equal(a.mu + a.K * p, a.mu + a.K * (p + 1), a.mu + a.K * q)) return true;
+        return false;
+    }
+
     // uploads the signal, sets the path to ones; a whole-recording decode (chunksize <= 0) is finished here
     int open()
     {
@@ -449,9 +458,7 @@ struct FitChannel {
             *ll_out = 0.0;
             return end(HMMSORT_OK);
         }
-        for (int64_t p = 0; p < a.N && !twins; p++)
-            for (int64_t q = p + 1; q < a.N && !twins; q++)
-                twins = std::equal(a.mu + a.K * p, a.mu + a.K * (p + 1), a.mu + a.K * q);
+        twins = has_twins();
         int rc;
         HS_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
         HS_HIP(hipHostMalloc(&pin, 3 * sizeof(int64_t), hipHostMallocDefault));
@@ -471,13 +478,13 @@ struct FitChannel {
         return HMMSORT_OK;
     }
 
-    // the plan's model tables to the device, once per channel (the plan and its model outlive the copies: the slot
-    // stays with the channel)
+    // the plan's model tables to the device, once per channel and again after the channel's model was replaced (the
+    // plan and its model outlive the copies: the slot stays with the channel)
     int upload_tables(const HostModel &m)
     {
         int rc;
-        if ((rc = dmean.alloc(m.mean.size() * sizeof(double))) || (rc = dinptr.alloc(m.in_ptr.size() * sizeof(int32_t))) ||
-            (rc = dinsrc.alloc(m.in_src.size() * sizeof(int32_t))) || (rc = dinlp.alloc(m.in_lp.size() * sizeof(double))))
+        if ((rc = dmean.ensure(m.mean.size() * sizeof(double))) || (rc = dinptr.ensure(m.in_ptr.size() * sizeof(int32_t))) ||
+            (rc = dinsrc.ensure(m.in_src.size() * sizeof(int32_t))) || (rc = dinlp.ensure(m.in_lp.size() * sizeof(double))))
             return rc;
         HS_HIP(hipMemcpyAsync(dmean.p, m.mean.data(), m.mean.size() * sizeof(double), hipMemcpyHostToDevice, st));
         HS_HIP(hipMemcpyAsync(dinptr.p, m.in_ptr.data(), m.in_ptr.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
@@ -811,6 +818,177 @@ int fit_chunked_host(const void *y, int sample_type, int64_t T, int64_t chunksiz
     return fit_channels_host(1, &y, sample_type, T, chunksize, &m, nullptr, 0, &ml_out, ll_out, nullptr, false);
 }
 
+// ---- drift tracking on top of the loop (hmmsort_fit_adaptive) -------------------------------------------------------
+// The channel owns its model.  After every finished chunk it takes the path statistics of the range that chunk
+// contributed (from the trim points, hence a second wait), blends them into an exponentially weighted accumulator,
+// finishes the accumulator under the current model and decodes the next chunk with the result: every chunk plan is
+// re-armed, the tables k_chunk_ll folds along go up again, and the ladder sees the new ModelArgs.  Nothing here runs
+// for the other chunked calls.
+struct AdaptiveChannel : FitChannel {
+    const hmmsort_adapt ad;
+    hmmsort_track *const track;
+    const hmmsort_step_out *const final_model;
+    std::vector<hmm_trans> tr_own;   // what the next chunk is decoded with
+    std::vector<double> mu_own;
+    DevBuf dacc, dnew, dfin, dcnt;
+    std::vector<double> hfin;
+    int64_t len = 0;                 // doubles of the statistics vector, the same for every chunk plan
+    int64_t nchunks = 0, owned = 0;  // finished chunks; samples that entered the statistics, undecayed
+
+    AdaptiveChannel(const void *y_, int type, int64_t T_, int64_t chunk, const ModelArgs &a_, const Options &o, int16_t *ml,
+                    double *ll_, const hmmsort_adapt &ad_, hmmsort_track *track_, const hmmsort_step_out *fin)
+        : FitChannel(y_, type, T_, chunk, a_, o, ml, ll_), ad(ad_), track(track_), final_model(fin),
+          tr_own(a_.tr, a_.tr + a_.R), mu_own(a_.mu, a_.mu + a_.K * a_.N)
+    {
+        a.tr = tr_own.data();
+        a.mu = mu_own.data();
+        if (track && track->n) *track->n = 0;
+    }
+
+    // record c of the track: the chunk that started at fit.jl's i0, decoded with the current model
+    void record(int64_t i0, int64_t lo, int64_t hi, double w)
+    {
+        const int64_t c = nchunks++;
+        if (!track) return;
+        if (track->n) *track->n = nchunks;
+        if (c >= track->cap) return;
+        if (track->first) track->first[c] = i0;
+        if (track->own) track->own[2 * c] = lo, track->own[2 * c + 1] = hi;
+        if (track->w) track->w[c] = w;
+        if (track->mu) memcpy(track->mu + c * a.K * a.N, a.mu, a.K * a.N * sizeof(double));
+        if (track->sigma) track->sigma[c] = a.sigma;
+    }
+
+    double weight(int64_t n) const { return std::exp2(-(double)n / ad.halflife); }
+
+    // the chunk that started at i0 is finished (stitched, its ll added): its share of the statistics, and the model
+    // the next chunk is decoded with.  pin still holds the chunk's trim points.
+    int after_chunk(int64_t i0, bool last)
+    {
+        const int64_t l = pin_lk()[0], kk = pin_lk()[1];
+        const int64_t lo = i0 + l - 2, hi = last ? T : i0 + kk - 2;
+        HS_CHECK(0 <= lo && lo <= hi && hi <= T, HMMSORT_EINVAL, "fit_adaptive: the chunk at sample %lld owns [%lld, %lld) "
+                 "of %lld samples", (long long)i0, (long long)lo, (long long)hi, (long long)T);
+        const double w = weight(hi - lo);
+        record(i0, lo, hi, w);
+        int rc;
+        const int64_t n = plan_path_stats_len(plan);
+        if (!len) {
+            len = n;
+            if ((rc = dacc.alloc(len * sizeof(double))) || (rc = dnew.alloc(len * sizeof(double)))) return rc;
+            HS_HIP(hipMemsetAsync(dacc.p, 0, len * sizeof(double), st));
+        }
+        HS_CHECK(n == len, HMMSORT_EUNSUP, "fit_adaptive: the plan of the chunk at sample %lld has %lld statistics, the "
+                 "channel's accumulator %lld (another lp' layout): they do not blend", (long long)i0, (long long)n,
+                 (long long)len);
+        if ((rc = plan_path_stats(plan, dy.as<double>(), dml.as<int16_t>(), T, lo, hi, i0 == 1, dnew.as<double>(), st)) ||
+            (rc = dev_stats_blend(dacc.as<double>(), w, dnew.as<double>(), len, 3, st)))
+            return rc;
+        owned += hi - lo;
+        const bool replace = !done && owned >= ad.warmup, report = done && final_model;
+        if (!replace && !report) return HMMSORT_OK;
+        const int64_t KN = a.K * a.N, nlp = plan->eng->n_lp(), mlen = hmmsort_plan_mstep_len(plan);
+        if ((rc = dfin.ensure(mlen * sizeof(double))) || (rc = dcnt.ensure(3 * sizeof(int64_t)))) return rc;
+        if ((rc = plan_path_finish(plan, dacc.as<double>(), dfin.as<double>(), dcnt.as<int64_t>(), st))) return rc;
+        hfin.resize(mlen);
+        int64_t counts[3] = {0, 0, 0};
+        // a replacement needs mu', sigma' and lp' only, not the S entries of pp'
+        HS_HIP(hipMemcpyAsync(hfin.data(), dfin.p, (report ? mlen : KN + 1 + nlp) * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (report) HS_HIP(hipMemcpyAsync(counts, dcnt.p, sizeof(counts), hipMemcpyDeviceToHost, st));
+        HS_HIP(hipStreamSynchronize(st));   // the second wait of this chunk
+        if (report) return unpack_step(hfin.data(), counts, a.K, a.N, a.S, nlp, *final_model);
+        return replace_model(hfin.data(), hfin[KN], hfin.data() + KN + 1, nlp);
+    }
+
+    int replace_model(const double *mu_new, double sigma_new, const double *lp_new, int64_t nlp)
+    {
+        std::copy(mu_new, mu_new + a.K * a.N, mu_own.begin());
+        if (ad.update_sigma && std::isfinite(sigma_new) && sigma_new > 0.0) a.sigma = sigma_new;
+        if (ad.update_lp) {
+            // the rebuild after a hard step (baumwelch.jl:265 feeds xb[2:end] back as lp); entries that are not finite
+            // leave the list (types.jl:121)
+            const int overlaps = a.S > 1 + a.N * (a.K - 1);
+            const int64_t R = hmmsort_build_transitions(a.N, a.K, lp_new, nlp, overlaps, nullptr, 0);
+            if (R < 0) return (int)R;
+            HS_CHECK(R >= 1, HMMSORT_EINVAL, "fit_adaptive: the re-estimated transition list is empty");
+            tr_own.resize(R);
+            hmmsort_build_transitions(a.N, a.K, lp_new, nlp, overlaps, tr_own.data(), R);
+            a.tr = tr_own.data();
+            a.R = R;
+        }
+        // every chunk plan of the channel; one that refuses (a list of another length on a generic plan) is made anew
+        // when its chunk length comes up again
+        hmmsort_plan *live = nullptr;
+        for (auto &kv : slots) {
+            if (!kv.second || !kv.second->plan) continue;
+            if (hmmsort_plan_set_model(kv.second->plan, a.tr, a.R, a.mu, a.sigma))
+                kv.second->drop_plan();
+            else
+                live = kv.second->plan;
+        }
+        plan = nullptr;
+        tables = false;
+        if (live) {
+            int rc = upload_tables(live->model);
+            if (rc) return rc;
+        }
+        twins = has_twins();
+        return HMMSORT_OK;
+    }
+};
+
+int fit_adaptive_host(const void *y, int sample_type, int64_t T, int64_t chunksize, const hmmsort_model *model,
+                      const hmmsort_adapt *ad, int16_t *ml_out, double *ll_out, hmmsort_track *track,
+                      const hmmsort_step_out *final_model)
+{
+    HS_CHECK(y && model && ad && ml_out && ll_out, HMMSORT_EINVAL, "fit_adaptive: null argument");
+    HS_CHECK(model->states && model->tr && model->mu, HMMSORT_EINVAL, "fit_adaptive: null pointer in the model");
+    HS_CHECK(ad->halflife > 0.0, HMMSORT_EINVAL, "fit_adaptive: halflife must be > 0 (+Inf: never forget), got %g",
+             ad->halflife);
+    HS_CHECK(ad->warmup >= 0, HMMSORT_EINVAL, "fit_adaptive: warmup must be >= 0, got %lld", (long long)ad->warmup);
+    HS_CHECK(T >= 1, HMMSORT_EINVAL, "fit_adaptive: empty signal (T = %lld)", (long long)T);
+    HS_CHECK(sample_type == HMMSORT_SAMPLES_F64 || sample_type == HMMSORT_SAMPLES_I16, HMMSORT_EINVAL,
+             "fit_adaptive: samples must be HMMSORT_SAMPLES_F64 or HMMSORT_SAMPLES_I16");
+    HS_CHECK(!track || track->cap >= 0, HMMSORT_EINVAL, "fit_adaptive: track of %lld records",
+             (long long)(track ? track->cap : 0));
+    HS_CHECK(!final_model || (final_model->mu && final_model->sigma && final_model->lp), HMMSORT_EINVAL,
+             "fit_adaptive: null pointer in final_model");
+    HS_CHECK(model->N >= 1 && model->K >= 1 && model->S >= 1 && model->R >= 1, HMMSORT_EINVAL,
+             "fit_adaptive: need N, K, S, R >= 1");
+    int rc;
+    if ((rc = need_device())) return rc;
+    const Options opt = options_get();
+    last_escalations() = 0;
+    const hmmsort_model &m = *model;
+    AdaptiveChannel ch(y, sample_type, T, chunksize, {m.states, m.N, m.K, m.S, m.tr, m.R, m.mu, m.sigma}, opt, ml_out,
+                       ll_out, *ad, track, final_model);
+    // a recording that open() finishes (one decode, or one sample) takes its step as hmmsort_fit_step_channels does
+    if (final_model) ch.step_mode = kStepFinish, ch.step_out = final_model;
+    rc = ch.guard(ch.open());
+    if (!rc && ch.done && ch.status == HMMSORT_OK) {
+        if (T > 1) ch.record(1, 0, T, ch.weight(T));
+        if (final_model && !ch.stepped) rc = ch.guard(ch.step_resident());
+    }
+    while (!rc && !ch.done) {
+        if ((rc = ch.guard(ch.enqueue_chunk())) || ch.done) break;
+        const int64_t i0 = ch.i;
+        const bool last = !ch.trail;
+        rc = ch.guard(ch.finish_chunk());
+        if (!rc && ch.status == HMMSORT_OK) rc = ch.guard(ch.after_chunk(i0, last));
+    }
+    if (rc) {
+        if (ch.st) (void)hipStreamSynchronize(ch.st);
+        (void)hipGetLastError();
+        return rc;
+    }
+    const std::string message = ch.message;
+    rc = ch.collect();
+    last_escalations() = ch.escalations;
+    if (rc) return rc;
+    if (ch.status) set_error("%s", message.c_str());
+    return ch.status;
+}
+
 int fwd_bwd_host(bool fwd, const double *y, int64_t T, const ModelArgs &a, double *out)
 {
     HS_CHECK(y && out, HMMSORT_EINVAL, "forward/backward: null argument");
@@ -908,6 +1086,13 @@ int hmmsort_fit_step_channels(int64_t C, const void *const *y, int sample_type, 
 {
     return fit_step_channels_host(C, y, sample_type, T, chunksize, models, devices, ndev, pooled != 0, ml_seq_out,
                                   ll_out, out, status_out);
+}
+
+int hmmsort_fit_adaptive(const void *y, int sample_type, int64_t T, int64_t chunksize, const hmmsort_model *model,
+                         const hmmsort_adapt *opt, int16_t *ml_seq_out, double *ll_out, hmmsort_track *track,
+                         hmmsort_step_out *final_model)
+{
+    return fit_adaptive_host(y, sample_type, T, chunksize, model, opt, ml_seq_out, ll_out, track, final_model);
 }
 
 int hmmsort_forward(const double *y, int64_t T, const int16_t *states, int64_t N, int64_t K,

@@ -691,6 +691,17 @@ __global__ __launch_bounds__(256) void k_stats_sum(const double *__restrict__ pa
     out[i] = a;
 }
 
+// acc <- w acc + new on the first nweighted entries, product and sum rounded one after the other (the file is built
+// with contraction off; the intrinsics say so where it matters), acc <- acc + new on the rest
+__global__ __launch_bounds__(256) void k_stats_blend(double *__restrict__ acc, double w, const double *__restrict__ nw,
+                                                     int64_t len, int64_t nweighted)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= len) return;
+    const double a = acc[i], b = nw[i];
+    acc[i] = i < nweighted ? __dadd_rn(__dmul_rn(w, a), b) : __dadd_rn(a, b);
+}
+
 // state -> the entries l (K-1) + (k-2) of its active rows in neuron order, -1 padded, for states with two or more;
 // all -1 for the others
 void multi_table(const HostModel &m, std::vector<int32_t> &tab)
@@ -713,18 +724,14 @@ void multi_table(const HostModel &m, std::vector<int32_t> &tab)
 struct PathStatsDev {
     std::vector<int32_t> h_single, h_multi, h_slot, h_inptr, h_insrc;
     std::vector<double> h_mu;
-    hipEvent_t uploaded = nullptr;
     int nslot = 0, rstride = 1;
-    ~PathStatsDev()
-    {
-        if (uploaded) (void)hipEventDestroy(uploaded);
-    }
     DevBuf single, multi, states, slot, inptr, insrc, mu, part_sum, part_sm, part_cnt, part_y2, ints, nj;
 };
 
 namespace {
 
-// the plan's PathStatsDev with the tables of its current model(s) on the device, ordered before what follows on st
+// the plan's PathStatsDev with the tables of its current model(s) on the device (uploaded on st and waited for when
+// the model has changed since the last call)
 int path_stats_tables(hmmsort_plan *p, hipStream_t st, PathStatsDev **out)
 {
     const HostModel &m0 = p->model;
@@ -745,13 +752,11 @@ int path_stats_tables(hmmsort_plan *p, hipStream_t st, PathStatsDev **out)
         HS_HIP(hipMemcpy(d->single.p, d->h_single.data(), S * sizeof(int32_t), hipMemcpyHostToDevice));
         HS_HIP(hipMemcpy(d->multi.p, d->h_multi.data(), d->h_multi.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         HS_HIP(hipMemcpy(d->states.p, m0.states.data(), N * S * sizeof(int16_t), hipMemcpyHostToDevice));
-        HS_HIP(hipEventCreateWithFlags(&d->uploaded, hipEventDisableTiming));
         p->ps = d;
         p->ps_stale = true;
     }
     PathStatsDev &d = *p->ps;
     if (p->ps_stale) {
-        HS_HIP(hipEventSynchronize(d.uploaded));   // the previous upload has left the host images
         int64_t rmax = 1;
         for (int64_t ch = 0; ch < C; ch++) rmax = std::max(rmax, (C > 1 ? p->models[ch] : m0).R);
         d.nslot = (int)nslot;
@@ -774,10 +779,12 @@ int path_stats_tables(hmmsort_plan *p, hipStream_t st, PathStatsDev **out)
         HS_HIP(hipMemcpyAsync(d.inptr.p, d.h_inptr.data(), d.h_inptr.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
         HS_HIP(hipMemcpyAsync(d.insrc.p, d.h_insrc.data(), d.h_insrc.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
         HS_HIP(hipMemcpyAsync(d.mu.p, d.h_mu.data(), d.h_mu.size() * sizeof(double), hipMemcpyHostToDevice, st));
-        HS_HIP(hipEventRecord(d.uploaded, st));
+        // waited for here: the host images are free for the next model, a call on another stream finds the tables
+        // there, and nothing of the plan refers to `st` once it is gone (a cached plan outlives its channel's stream;
+        // an event last recorded on a destroyed stream made hipEventSynchronize fail now and then)
+        HS_HIP(hipStreamSynchronize(st));
         p->ps_stale = false;
     }
-    HS_HIP(hipStreamWaitEvent(st, d.uploaded, 0));   // a call on another stream than the upload's
     *out = &d;
     return HMMSORT_OK;
 }
@@ -859,6 +866,15 @@ int plan_path_finish(hmmsort_plan *p, const double *d_stats, double *d_out, int6
 int dev_stats_sum(const double *d_parts, int64_t nparts, int64_t len, double *d_out, hipStream_t st)
 {
     hipLaunchKernelGGL(k_stats_sum, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, st, d_parts, nparts, len, d_out);
+    HS_HIP(hipGetLastError());
+    return HMMSORT_OK;
+}
+
+int dev_stats_blend(double *d_acc, double w, const double *d_new, int64_t len, int64_t plain_tail, hipStream_t st)
+{
+    if (len <= 0) return HMMSORT_OK;
+    hipLaunchKernelGGL(k_stats_blend, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, st, d_acc, w, d_new, len,
+                       len - plain_tail);
     HS_HIP(hipGetLastError());
     return HMMSORT_OK;
 }

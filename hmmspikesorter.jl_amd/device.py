@@ -23,6 +23,14 @@ def stats_sum(d_parts, nparts, length, d_out, stream=0):
     check(lib().hmmsort_stats_sum(_dptr(d_parts), int(nparts), int(length), _dptr(d_out), C.c_void_p(stream)))
 
 
+def stats_blend(d_acc, w, d_new, length, plain_tail=3, stream=0):
+    """d_acc[i] = w * d_acc[i] + d_new[i] in two rounded steps for i < length - plain_tail, d_acc[i] += d_new[i] for
+    the last `plain_tail` entries (hmmsort_stats_blend): exponentially weighted statistics, in place on the device.
+    plain_tail = 3 is a path-statistics vector's x0, bad0, bad1."""
+    check(lib().hmmsort_stats_blend(_dptr(d_acc), float(w), _dptr(d_new), int(length), int(plain_tail),
+                                    C.c_void_p(stream)))
+
+
 class Plan:
     """One recording channel of length T with a fixed model shape."""
 

@@ -71,7 +71,7 @@ def _chunk_confidence(templates, dataf, ml_seq, chunksize, jitter):
 
 
 def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_templates=4,
-              chunksize=100_000, confidence=False, jitter=2, refine_steps=0):
+              chunksize=100_000, confidence=False, jitter=2, refine_steps=0, adapt_halflife=None):
     """sort_data(inputfile, datafile, outputfile; dosave, max_templates)   hmmsort.jl:36-104.
 
     Returns the reference's output dictionary; {} when there are more templates than
@@ -91,7 +91,13 @@ def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_temp
     `refine_steps=n` (an extension; default 0, output unchanged) runs n steps of Viterbi training
     (api.viterbi_step) of the overlap model on the channel before the chunked decode: the templates, their entry
     probabilities and sigma are re-estimated from the spikes the model itself sorts, the decode uses the refined
-    model, and "waveforms", "lp" and "sigma" in the output are the refined ones."""
+    model, and "waveforms", "lp" and "sigma" in the output are the refined ones.
+
+    `adapt_halflife=h` (an extension; default None, output unchanged) decodes with the drift-tracking loop
+    (api.fit_adaptive: the templates and sigma are re-estimated after every chunk from statistics that lose half
+    their weight every h samples) and adds "waveforms_track" (chunks x nstates x ntemplates, the templates each chunk
+    was decoded with), "sigma_track" and "chunk_first" (1-based first sample of each chunk).  "waveforms" and
+    "sigma" stay the model the decode started from."""
     spike_forms = np.asarray(spike_forms, dtype=np.float64)
     nstates, _nchannels, ntemplates = spike_forms.shape
     pp = np.atleast_1d(np.asarray(p, dtype=np.float64))
@@ -118,9 +124,16 @@ def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_temp
             em.close()
         templates = api.HMMSpikeTemplateModel(sm, mu_r, sigma)
         lp, _ii = get_lp(sm)
-    modelf = api.fit(templates, dataf, chunksize)                              # :90
+    track = None
+    if adapt_halflife is not None:
+        modelf, track = api.fit_adaptive(templates, dataf, chunksize, float(adapt_halflife))
+    else:
+        modelf = api.fit(templates, dataf, chunksize)                          # :90
     mlseq = api.unroll_mlseq(modelf.ml_seq, sm)                                # :92
     out = {"mlseq": mlseq, "ll": modelf.ll, "waveforms": templates.mu, "lp": lp, "sigma": sigma}
+    if track is not None:
+        out["waveforms_track"], out["sigma_track"] = np.ascontiguousarray(track.mu), np.array(track.sigma)
+        out["chunk_first"] = np.array(track.first)
     if confidence:
         st, cf = _chunk_confidence(templates, dataf, modelf.ml_seq, chunksize or len(dataf), jitter)
         out["spiketimes"], out["confidence"] = np.empty(len(st), dtype=object), np.empty(len(cf), dtype=object)

@@ -211,6 +211,62 @@ int hmmsort_fit_step_channels(int64_t C, const void *const *y, int sample_type, 
                               const hmmsort_model *models, const int *devices, int64_t ndev, int pooled,
                               int16_t *const *ml_seq_out, double *ll_out, hmmsort_step_out *out, int *status_out);
 
+/* Drift tracking: how hmmsort_fit_adaptive forgets and when it starts to re-estimate */
+typedef struct hmmsort_adapt {
+    double halflife;   /* samples after which a statistic weighs 1/2; > 0, +Inf = never forget */
+    int64_t warmup;    /* owned samples that must have entered the statistics before the model is first replaced; >= 0 */
+    int update_sigma;  /* 0: sigma stays the caller's */
+    int update_lp;     /* 0: the transition list stays the caller's, bit for bit */
+} hmmsort_adapt;
+
+/* The model track of hmmsort_fit_adaptive: the caller's arrays of `cap` records, one per decoded chunk; any pointer
+ * may be NULL.  Chunks beyond cap are counted in *n and not recorded. */
+typedef struct hmmsort_track {
+    int64_t cap;
+    int64_t *n;        /* chunks decoded (all of them, also beyond cap) */
+    int64_t *first;    /* [cap]     fit.jl's i of chunk c, 1-based */
+    int64_t *own;      /* [cap][2]  0-based range [lo, hi) whose statistics chunk c contributed */
+    double *w;         /* [cap]     weight the accumulator was multiplied by before chunk c's statistics were added */
+    double *mu;        /* [cap][K*N] the model chunk c was DECODED with */
+    double *sigma;     /* [cap] */
+} hmmsort_track;
+
+/* The chunked decode with Viterbi training inside the loop: hmmsort_fit_chunked, with the model re-estimated from
+ * exponentially weighted path statistics after every chunk, so that templates follow slow changes of the recording
+ * (electrode drift).  One channel, host buffers; sample_type HMMSORT_SAMPLES_F64 or HMMSORT_SAMPLES_I16.  No
+ * counterpart in the reference.
+ * Per chunk the loop is hmmsort_fit_chunked's (plan per chunk length, decode, stitch, the reference-rounded chunk
+ * ll, diagnostics, ladder, the HMMSORT_ENOSILENT rules).  After a chunk [i, j] (fit.jl's 1-based i, j) is finished
+ * with trim points l, kk (hmmsort_chunk_stitch):
+ *   owned range  lo = i + l - 2;  hi = i + kk - 2 when the chunk does not end the recording, hi = T when it does
+ *                (0-based, [lo, hi)).  The chunk's last written sample is silent and is the next chunk's first: it is
+ *                left out here and the pair (hi-1, hi) reads it.  Samples a later chunk skips (fit.jl:24-28: leading
+ *                non-silent samples of a chunk) belong to nobody.
+ *   statistics   hmmsort_plan_path_stats over [lo, hi) of the resident signal and stitched path (first = (i == 1)),
+ *                blended into the channel's accumulator, which starts at zero, by hmmsort_stats_blend with
+ *                w = exp2(-(hi - lo) / halflife) (computed on the host, reported in the track) and plain_tail = 3.
+ *   replacement  once the undecayed number of owned samples has reached `warmup`: hmmsort_plan_path_finish of the
+ *                accumulator under the current model (rows no sample visited keep their mean); mu <- mu';
+ *                sigma <- sigma' if update_sigma (and sigma' is finite and > 0: an accumulator that holds no sample yet
+ *                leaves sigma alone); if update_lp the list is rebuilt by hmmsort_build_transitions(N, K, lp', n_lp,
+ *                S > 1 + N (K-1)) as after a hard step: non-finite entries leave the list (types.jl:121), so a template
+ *                that did not fire within memory can vanish, and on a plan of the generic engines a later lp' is then
+ *                shorter than N and the call ends with HMMSORT_EINVAL.  With update_lp == 0 the list is never touched.
+ *                The next chunk is decoded with the new model, its ll is taken under it.
+ * ll_out: the sum of the chunks' reference-rounded values, each under the model that chunk was decoded with.
+ * track (may be NULL): record c describes chunk c; with a stationary signal the path is hmmsort_fit_chunked's only
+ * as far as the re-estimated templates decode it alike.  final_model (may be NULL; mu, sigma, lp required as in
+ * hmmsort_fit_step_channels): the full finish of the accumulator after the last chunk under the last model -- mu',
+ * sigma', lp', pp', counts, whatever warmup, update_sigma and update_lp say.
+ * chunksize <= 0, or one chunk that holds the recording: exactly hmmsort_fit_chunked's result, *track->n = 1 with
+ * own = [0, T), final_model from the statistics of [0, T).  T == 1: [1], ll = 0, *track->n = 0.
+ * HMMSORT_ENOSILENT: ml_seq_out, ll_out and the track hold what the loop had (records of the chunks that were
+ * finished); final_model is not written.  halflife <= 0 or NaN, warmup < 0, opt == NULL: HMMSORT_EINVAL before any
+ * GPU work.  The range comes from l and kk, so the loop waits for the device twice per chunk. */
+int hmmsort_fit_adaptive(const void *y, int sample_type, int64_t T, int64_t chunksize, const hmmsort_model *model,
+                         const hmmsort_adapt *opt, int16_t *ml_seq_out, double *ll_out, hmmsort_track *track,
+                         hmmsort_step_out *final_model /* may be NULL: the model after the last chunk */);
+
 /* forward(V, lA::StateMatrix, mu, sigma) -> alpha (S x T)            baumwelch.jl:25-51 */
 int hmmsort_forward(const double *y, int64_t T, const int16_t *states, int64_t N, int64_t K,
                     int64_t S, const hmm_trans *tr, int64_t R, const double *mu, double sigma,
@@ -252,6 +308,15 @@ int hmmsort_viterbi_step(const double *y, int64_t T, const int16_t *states, int6
 /* reconstruct_signal(x, lA, mu, sigma) -> Y2 (sigma is ignored)    reconstruction.jl:1-10 */
 int hmmsort_reconstruct(const int16_t *x, int64_t T, const int16_t *states, int64_t N,
                         int64_t S, const double *mu, int64_t K, double *y_out);
+
+/* reconstruct_signal under a model track (hmmsort_fit_adaptive's): y2[t] = sum_l mu_c(t)[states[l, x_t], l], where
+ * c(t) is the last chunk whose first sample is <= t.  first: nchunks 1-based sample numbers, strictly ascending
+ * (at most 8192; HMMSORT_EUNSUP beyond); mu_track: [nchunks][K*N].  State ids outside 1..S, and samples before
+ * first[0], give NaN (the device code's answer; hmmsort_reconstruct refuses such ids on the host).  No counterpart
+ * in the reference. */
+int hmmsort_reconstruct_tracked(const int16_t *x, int64_t T, const int16_t *states, int64_t N, int64_t S, int64_t K,
+                                int64_t nchunks, const int64_t *first /* 1-based, ascending */,
+                                const double *mu_track /* [nchunks][K*N] */, double *y_out);
 
 /* unroll_mlseq(mlseq, state_matrix) -> N x T Int16                   extraction.jl:4-13 */
 int hmmsort_unroll_mlseq(const int16_t *mlseq, int64_t T, const int16_t *states, int64_t N,
@@ -387,7 +452,8 @@ int hmmsort_plan_path_update(hmmsort_plan *plan, const double *d_y, const int16_
  * + sum_e c_e mu'_e^2 + sum_j n_j M_j^2) / n with M_j the state means of the new templates, clamped at 0.
  * For own = [0, T), first = 1 and T the plan's, mu', lp', pp' and the counts equal hmmsort_plan_path_update's bit
  * for bit (same tiles, same order); sigma' agrees within the rounding of the four sums.
- * One statistics call at a time per plan (they share its workspace).  All asynchronous on `stream`. */
+ * One statistics call at a time per plan (they share its workspace).  All asynchronous on `stream`, except that the
+ * first call after plan creation or hmmsort_plan_set_model waits for `stream` once, behind the upload of its tables. */
 int64_t hmmsort_plan_path_stats_len(const hmmsort_plan *plan);              /* per channel */
 int hmmsort_plan_path_stats(hmmsort_plan *plan, const double *d_y, const int16_t *d_x, int64_t T, int64_t own_lo,
                             int64_t own_hi, int first, double *d_stats, void *stream);
@@ -396,6 +462,13 @@ int hmmsort_plan_path_finish(hmmsort_plan *plan, const double *d_stats, double *
 /* d_out[i] = d_parts[0][i] + d_parts[1][i] + ... in ascending order, for nparts contiguous device vectors of len
  * doubles: the on-device, fixed-order alternative to an all-reduce, for any statistics vector of the library. */
 int hmmsort_stats_sum(const double *d_parts, int64_t nparts, int64_t len, double *d_out, void *stream);
+/* Exponentially weighted statistics, in place on device vectors of len doubles: d_acc[i] = w * d_acc[i] + d_new[i]
+ * for i < len - plain_tail, the product rounded, then the sum rounded (never a fused multiply-add: two IEEE
+ * operations on the host give the same bits); d_acc[i] += d_new[i] for the last plain_tail entries.  A
+ * path-statistics vector takes plain_tail = 3: x0, bad0 and bad1 are an identifier and diagnostics, not weights.
+ * One thread per entry, asynchronous on `stream`.  w outside [0, 1] or NaN, len < plain_tail, plain_tail < 0:
+ * HMMSORT_EINVAL. */
+int hmmsort_stats_blend(double *d_acc, double w, const double *d_new, int64_t len, int64_t plain_tail, void *stream);
 /* doubles hmmsort_plan_mstep writes PER CHANNEL: K*N + 1 + n_lp + S, n_lp = N for wave/ring plans (also when
  * the list has lost a vanished template's entry transitions, types.jl:121: its slot stays, value -Inf or the
  * re-estimate), (#transitions leaving state 1) - 1 for the blocked engine (baumwelch.jl:226,264). */

@@ -220,6 +220,63 @@ stats_sum!(d_parts::Ptr{Float64}, nparts::Integer, len::Integer, d_out::Ptr{Floa
     check(ccall((:hmmsort_stats_sum, lib), Cint, (Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Cvoid}),
         d_parts, nparts, len, d_out, stream))
 
+stats_blend!(d_acc::Ptr{Float64}, w::Float64, d_new::Ptr{Float64}, len::Integer, plain_tail::Integer=3,
+             stream::Ptr{Cvoid}=C_NULL) =
+    check(ccall((:hmmsort_stats_blend, lib), Cint, (Ptr{Float64}, Float64, Ptr{Float64}, Int64, Int64, Ptr{Cvoid}),
+        d_acc, w, d_new, len, plain_tail, stream))
+
+# struct hmmsort_adapt / hmmsort_track (include/hmmsort.h)
+struct CAdapt
+    halflife::Float64; warmup::Int64; update_sigma::Cint; update_lp::Cint
+end
+struct CTrack
+    cap::Int64; n::Ptr{Int64}; first::Ptr{Int64}; own::Ptr{Int64}; w::Ptr{Float64}; mu::Ptr{Float64}; sigma::Ptr{Float64}
+end
+
+"""
+    fit_adaptive(templates, X, chunksize, halflife; warmup=0, update_sigma=true, update_lp=false, cap=...)
+        -> (model, track, final)
+
+The chunked decode with the model re-estimated between chunks (`hmmsort_fit_adaptive`; an extension, INTEGRATION.md
+"Drift tracking"): templates follow slow changes of the recording.  `track` = (n, first, own, w, μ, σ) with one entry
+per chunk (`μ[:, :, c]` is what chunk `c` was decoded with); `final` = (state_matrix′, μ′, σ′), the full re-estimate
+after the last chunk.  `cap` records are kept (default: twice the chunks of an even split, plus two).
+"""
+function fit_adaptive(templates::HMMSpikeTemplateModel, X::Vector{T}, chunksize::Integer, halflife::Real;
+                      warmup::Integer=0, update_sigma::Bool=true, update_lp::Bool=false,
+                      cap::Integer=chunksize > 0 ? 2 * (length(X) ÷ chunksize + 1) + 2 : 1) where T <: Union{Float64,Int16}
+    sm = templates.state_matrix; n = length(X)
+    ml = zeros(Int16, n); ll = Ref{Float64}(0.0)
+    nrec = zeros(Int64, 1); first = zeros(Int64, cap); own = zeros(Int64, 2, cap); w = zeros(Float64, cap)
+    μt = zeros(Float64, sm.K, sm.N, cap); σt = zeros(Float64, cap)
+    μf = zeros(Float64, sm.K, sm.N); σf = zeros(Float64, 1); lpf = zeros(Float64, length(sm.transitions))
+    nlpf = zeros(Int64, 1); ppf = zeros(Float64, sm.nstates)
+    GC.@preserve templates X ml nrec first own w μt σt μf σf lpf nlpf ppf begin
+        model = Ref(CModel(pointer(sm.states), sm.N, sm.K, sm.nstates, Ptr{Cvoid}(pointer(sm.transitions)),
+                           length(sm.transitions), pointer(templates.μ), templates.σ))
+        opt = Ref(CAdapt(Float64(halflife), warmup, update_sigma ? 1 : 0, update_lp ? 1 : 0))
+        track = Ref(CTrack(cap, pointer(nrec), pointer(first), pointer(own), pointer(w), pointer(μt), pointer(σt)))
+        fin = Ref(CStepOut(pointer(μf), pointer(σf), pointer(lpf), length(lpf), pointer(nlpf), pointer(ppf),
+                           Ptr{Int64}(C_NULL)))
+        check(ccall((:hmmsort_fit_adaptive, lib), Cint,
+            (Ptr{Cvoid}, Cint, Int64, Int64, Ref{CModel}, Ref{CAdapt}, Ptr{Int16}, Ref{Float64}, Ref{CTrack}, Ref{CStepOut}),
+            X, T === Int16 ? HMMSORT_SAMPLES_I16 : HMMSORT_SAMPLES_F64, n, chunksize, model, opt, ml, ll, track, fin))
+    end
+    m = min(nrec[1], cap)
+    HMMSpikingModel(templates, ml, ll[], X),
+        (n=nrec[1], first=first[1:m], own=own[:, 1:m], w=w[1:m], μ=μt[:, :, 1:m], σ=σt[1:m]),
+        _finish(sm, μf, Ref(σf[1]), lpf, Ref(nlpf[1]), ppf)
+end
+
+"reconstruct_signal under the model track of `fit_adaptive` (`hmmsort_reconstruct_tracked`): sample t takes the templates of the last chunk that starts at or before it"
+function reconstruct_tracked(x::Array{Int16,1}, lA::StateMatrix, first::Vector{Int64}, μtrack::Array{Float64,3})
+    Y2 = zeros(Float64, length(x))
+    check(ccall((:hmmsort_reconstruct_tracked, lib), Cint,
+        (Ptr{Int16}, Int64, Ptr{Int16}, Int64, Int64, Int64, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}),
+        x, length(x), lA.states, lA.N, lA.nstates, lA.K, length(first), first, μtrack, Y2))
+    Y2
+end
+
 function reconstruct_signal(x::Array{T,1}, lA::StateMatrix, μ::Array{Float64,2}, σ::Float64) where T <: Integer
     xs = T === Int16 ? x : Int16.(x)
     Y2 = zeros(Float64, length(xs))
