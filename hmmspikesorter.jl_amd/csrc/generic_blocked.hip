@@ -897,6 +897,10 @@ static int dalloc(Tv **p, size_t n, int64_t *bytes)
     return HMMSORT_OK;
 }
 
+// test aid (HMMSORT_POISON): 0xFF in every work array of the decode that a kernel could read before writing it --
+// NaN as a double, -1 as a state id or a merge point.  d_frame, d_bdiag and d_gapmin start from meaningful values.
+static bool blocked_poison() { return getenv("HMMSORT_POISON") != nullptr; }
+
 int blocked_set_model(GenericDev *g, const HostModel &m)
 {
     const int64_t S = m.S;
@@ -1014,6 +1018,19 @@ int blocked_create(GenericDev *g, const HostModel &m, int64_t block_req, int64_t
     if (!g->blk_cols_lds && !g->blk_onecol && (rc = dalloc(&g->d_blkbuf, nb * 2 * S, &g->bytes)))
         return rc;
     HS_HIP(hipMemset(g->d_bdiag, 0, 8 * sizeof(unsigned long long)));
+    if (blocked_poison()) {
+        HS_HIP(hipMemset(g->d_endv, 0xFF, nb * S * sizeof(double)));
+        HS_HIP(hipMemset(g->d_warmv, 0xFF, nb * S * sizeof(double)));
+        HS_HIP(hipMemset(g->d_fmap, 0xFF, nb * S * sizeof(int16_t)));
+        HS_HIP(hipMemset(g->d_fconst, 0xFF, nb * sizeof(int16_t)));
+        HS_HIP(hipMemset(g->d_merged, 0xFF, nb * sizeof(int64_t)));
+        HS_HIP(hipMemset(g->d_endstate, 0xFF, nb * sizeof(int16_t)));
+        HS_HIP(hipMemset(g->d_llpart, 0xFF, 3 * nb * sizeof(double)));
+        if (g->d_blkbuf) HS_HIP(hipMemset(g->d_blkbuf, 0xFF, nb * 2 * S * sizeof(double)));
+    }
+    // the fills above go to the null stream and the decodes run on the caller's, possibly non-blocking, stream:
+    // nothing else orders them, so creation ends only when they are done
+    HS_HIP(hipStreamSynchronize(nullptr));
     return HMMSORT_OK;
 }
 
@@ -1037,27 +1054,32 @@ static int launch_block_sweep(GenericDev *g, const BlockArgs &a, int threads, si
     return HMMSORT_OK;
 }
 
-int blocked_viterbi(GenericDev *g, const double *d_y, int16_t *d_x, double *d_ll, hipStream_t st)
+// ---- which kernels a decode of this plan launches ----------------------------------------------
+// The ONE place that reads the thresholds: blocked_viterbi launches from its answer and the test aid
+// hmmsort_selftest_blocked_dispatch (generic_engine.hip) prints it, so a test names the row it pins
+// without restating a threshold.
+struct BlockedDispatch {
+    enum Sweep { PAIR, MULTI, ONECOL, GDICT, BLOCK } sweep = BLOCK;
+    // ONECOL: gen_vit_block1<spt>, GDICT: gen_vit_blockG<spt>, BLOCK: gen_vit_block<spt, spec, gcol, tlds>
+    int spt = 0;
+    bool spec = false, gcol = false, tlds = true;
+    int threads = 0, nbthr = 0;
+    size_t lds = 0;
+    // backtrace: by segments (k_seg_walk / k_seg_fix, codes in LDS or global) or by block maps (k_block_map<btm>)
+    bool seg = false, seg_btl = false;
+    int btm = 0, W = 0, map_threads = 0;
+    size_t lds_seg = 0, lds_map = 0;
+    size_t lds_ll = 0;   // k_block_ll_sum: 0 = partial sums read from global memory
+};
+
+static BlockedDispatch blocked_pick(const GenericDev *g)
 {
-    const int64_t T = g->T, S = g->S;
-    if (!g->d_T2) {
-        const double need = (double)std::max(g->nms, 1) * (double)T * 2.0;
-        HS_CHECK(need < 220e9, HMMSORT_ENOMEM,
-                 "Viterbi needs %.1f GB of back-pointers; decode in chunks", need / 1e9);
-        int rc = dalloc(&g->d_T2, (size_t)std::max(g->nms, 1) * T, &g->bytes);
-        if (rc) return rc;
-    }
-    BlockArgs a;
-    a.y = d_y; a.T = T; a.S = (int)S; a.B = (int)g->B; a.H = (int)g->H;
-    a.mean = g->d_mean; a.lp0 = g->d_lp0; a.src0 = g->d_src0; a.tinfo = g->d_tinfo;
-    a.tsrc = g->d_tsrc; a.tlp = g->d_tlp; a.ntail = g->ntail;
-    a.ms = (const MsRec *)g->d_ms; a.nms = g->nms;
-    a.c0 = -kLog2Pi - g->lsig;
-    a.den = 2.0 * (g->sigma * g->sigma);
-    a.rden = 1.0 / a.den;
-    a.T2c = g->d_T2; a.endv = g->d_endv; a.warmv = g->d_warmv; a.gapmin = g->d_gapmin;
-    a.gbuf = g->blk_cols_lds ? nullptr : g->d_blkbuf;
-    size_t lds = (g->blk_cols_lds ? 2 * (S + 1) * 8 : 0) + (g->blk_tail_lds ? (size_t)g->ntail * 12 + 8 : 0);
+    BlockedDispatch d;
+    const int64_t S = g->S;
+    const size_t tail_b = (size_t)g->ntail * 12 + 8;
+    d.gcol = !g->blk_cols_lds;
+    d.tlds = g->blk_tail_lds;
+    d.lds = (g->blk_cols_lds ? 2 * (S + 1) * 8 : 0) + (g->blk_tail_lds ? tail_b : 0);
     // register-cached sweep: wave-specialised (nbthr phase-B threads + phase-A threads with <= 2
     // states each) when that fits 1024 threads, else every thread takes spt <= 4 states
     int threads = (int)std::min<int64_t>(1024, (S + 63) / 64 * 64), spt = 0, nbthr = 0;
@@ -1069,52 +1091,128 @@ int blocked_viterbi(GenericDev *g, const double *d_y, int16_t *d_x, double *d_ll
         }
         if (!spt && S <= 4096) spt = (int)((S + threads - 1) / threads) <= 2 ? (int)((S + threads - 1) / threads) : 4;
     }
-    a.nbthr = nbthr;
+    d.threads = threads;
+    d.nbthr = nbthr;
+    if (g->pair_ok) {
+        d.sweep = g->multi_ok ? BlockedDispatch::MULTI : BlockedDispatch::PAIR;
+    } else if (g->blk_onecol) {
+        d.sweep = BlockedDispatch::ONECOL;
+        d.lds = (size_t)(S + 1) * 8 + tail_b;
+        d.threads = 1024;
+        const int spt1 = (int)((S + 1023) / 1024);
+        d.spt = spt1 <= 6 ? 6 : (spt1 <= 8 ? 8 : (spt1 <= 10 ? 10 : (spt1 <= 11 ? 11 : 12)));
+    } else if (d.gcol && g->ndict > 0 && S <= 21 * 1024 && (size_t)256 * 8 + tail_b <= 150 * 1024) {
+        d.sweep = BlockedDispatch::GDICT;
+        d.lds = (size_t)256 * 8 + tail_b;
+        d.threads = 1024;
+        d.spt = (int)((S + 1023) / 1024) <= 14 ? 14 : 21;
+    } else {
+        d.sweep = BlockedDispatch::BLOCK;
+        d.spt = spt;
+        d.spec = spt > 0 && nbthr > 0;
+    }
+    if (g->nms >= 64 && S > 1) {
+        d.seg = true;
+        d.seg_btl = (size_t)S * 2 <= 64 * 1024;
+        d.lds_seg = d.seg_btl ? (size_t)S * 2 : 0;
+    } else {
+        // rows of T2c staged W at a time; bt in LDS when it fits
+        const int nms1 = std::max(g->nms, 1);
+        d.W = (int)std::max<int64_t>(1, std::min<int64_t>(64, (32 * 1024) / (nms1 * 2)));
+        d.lds_map = (size_t)((S + 3) & ~3) * 2 + (size_t)((d.W * g->nms + 3) & ~3) * 2;
+        d.btm = d.lds_map + (size_t)S * 4 <= 150 * 1024 ? 1 : (d.lds_map + (size_t)S * 2 + 8 <= 150 * 1024 ? 2 : 0);
+        if (d.btm == 1) d.lds_map += (size_t)S * 4;
+        if (d.btm == 2) d.lds_map += (size_t)S * 2 + 8;
+        d.map_threads = S > 8192 ? 1024 : 256;
+    }
+    d.lds_ll = (size_t)g->nblk * 24 <= 60 * 1024 ? (size_t)g->nblk * 24 : 0;
+    return d;
+}
+
+int blocked_describe_dispatch(const GenericDev *g, char *buf, int64_t cap)
+{
+    HS_CHECK(g && g->blocked && buf && cap > 0, HMMSORT_EINVAL, "blocked dispatch: needs a blocked plan and a buffer");
+    const BlockedDispatch d = blocked_pick(g);
+    char sweep[64], back[32];
+    switch (d.sweep) {
+    case BlockedDispatch::PAIR: snprintf(sweep, sizeof sweep, "pair"); break;
+    case BlockedDispatch::MULTI: snprintf(sweep, sizeof sweep, "multi<%d>", (int)g->N); break;
+    case BlockedDispatch::ONECOL: snprintf(sweep, sizeof sweep, "gen_vit_block1<%d>", d.spt); break;
+    case BlockedDispatch::GDICT: snprintf(sweep, sizeof sweep, "gen_vit_blockG<%d>", d.spt); break;
+    default:
+        snprintf(sweep, sizeof sweep, "gen_vit_block<%d,%s,%s,%s>", d.spt, d.spec ? "true" : "false",
+                 d.gcol ? "true" : "false", d.tlds ? "true" : "false");
+    }
+    if (d.seg) snprintf(back, sizeof back, d.seg_btl ? "seg" : "seg<global>");
+    else snprintf(back, sizeof back, "map<%d>", d.btm);
+    const int n = snprintf(buf, (size_t)cap, "sweep=%s backtrace=%s ll=%s", sweep, back, d.lds_ll ? "lds" : "global");
+    HS_CHECK(n >= 0 && n < cap, HMMSORT_EINVAL, "blocked dispatch: buffer of %lld bytes too small", (long long)cap);
+    return HMMSORT_OK;
+}
+
+int blocked_viterbi(GenericDev *g, const double *d_y, int16_t *d_x, double *d_ll, hipStream_t st)
+{
+    const int64_t T = g->T, S = g->S;
+    if (!g->d_T2) {
+        const double need = (double)std::max(g->nms, 1) * (double)T * 2.0;
+        HS_CHECK(need < 220e9, HMMSORT_ENOMEM,
+                 "Viterbi needs %.1f GB of back-pointers; decode in chunks", need / 1e9);
+        int rc = dalloc(&g->d_T2, (size_t)std::max(g->nms, 1) * T, &g->bytes);
+        if (rc) return rc;
+        if (blocked_poison()) HS_HIP(hipMemsetAsync(g->d_T2, 0xFF, (size_t)std::max(g->nms, 1) * T * sizeof(int16_t), st));
+    }
+    const BlockedDispatch d = blocked_pick(g);
+    BlockArgs a;
+    a.y = d_y; a.T = T; a.S = (int)S; a.B = (int)g->B; a.H = (int)g->H;
+    a.mean = g->d_mean; a.lp0 = g->d_lp0; a.src0 = g->d_src0; a.tinfo = g->d_tinfo;
+    a.tsrc = g->d_tsrc; a.tlp = g->d_tlp; a.ntail = g->ntail;
+    a.ms = (const MsRec *)g->d_ms; a.nms = g->nms;
+    a.c0 = -kLog2Pi - g->lsig;
+    a.den = 2.0 * (g->sigma * g->sigma);
+    a.rden = 1.0 / a.den;
+    a.T2c = g->d_T2; a.endv = g->d_endv; a.warmv = g->d_warmv; a.gapmin = g->d_gapmin;
+    a.gbuf = g->blk_cols_lds ? nullptr : g->d_blkbuf;
+    a.nbthr = d.nbthr;
     HS_HIP(hipMemsetAsync(g->d_bdiag, 0, 8 * sizeof(unsigned long long), st));
     HS_HIP(hipMemsetAsync(g->d_gapmin, 0x7f, (size_t)g->nblk * sizeof(unsigned long long), st));  // huge
     int rc;
-    const bool gcol = !g->blk_cols_lds, tl = g->blk_tail_lds;
-    if (g->pair_ok) {
-        rc = g->multi_ok ? multi_sweep_launch(g, d_y, st) : pair_sweep_launch(g, d_y, st);
-    } else if (g->blk_onecol) {
-        const size_t lds1 = (size_t)(S + 1) * 8 + (size_t)g->ntail * 12 + 8;
-        const int spt1 = (int)((S + 1023) / 1024);
+    if (d.sweep == BlockedDispatch::PAIR || d.sweep == BlockedDispatch::MULTI) {
+        rc = d.sweep == BlockedDispatch::MULTI ? multi_sweep_launch(g, d_y, st) : pair_sweep_launch(g, d_y, st);
+    } else if (d.sweep == BlockedDispatch::ONECOL) {
         auto go = [&](auto kern) -> int {
             HS_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds1));
-            hipLaunchKernelGGL(kern, dim3((unsigned)g->nblk), dim3(1024), lds1, st, a);
+                                       (int)d.lds));
+            hipLaunchKernelGGL(kern, dim3((unsigned)g->nblk), dim3(1024), d.lds, st, a);
             HS_HIP(hipGetLastError());
             return HMMSORT_OK;
         };
-        if (spt1 <= 6) rc = go(gen_vit_block1<6>);
-        else if (spt1 <= 8) rc = go(gen_vit_block1<8>);
-        else if (spt1 <= 10) rc = go(gen_vit_block1<10>);
-        else if (spt1 <= 11) rc = go(gen_vit_block1<11>);
+        if (d.spt == 6) rc = go(gen_vit_block1<6>);
+        else if (d.spt == 8) rc = go(gen_vit_block1<8>);
+        else if (d.spt == 10) rc = go(gen_vit_block1<10>);
+        else if (d.spt == 11) rc = go(gen_vit_block1<11>);
         else rc = go(gen_vit_block1<12>);
-    } else if (gcol && g->ndict > 0 && S <= 21 * 1024 && (size_t)256 * 8 + (size_t)g->ntail * 12 + 8 <= 150 * 1024) {
-        const size_t ldsg = (size_t)256 * 8 + (size_t)g->ntail * 12 + 8;
-        const int sptg = (int)((S + 1023) / 1024);
+    } else if (d.sweep == BlockedDispatch::GDICT) {
         auto go = [&](auto kern) -> int {
-            if (ldsg > 64 * 1024)
+            if (d.lds > 64 * 1024)
                 HS_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)ldsg));
-            hipLaunchKernelGGL(kern, dim3((unsigned)g->nblk), dim3(1024), ldsg, st, a, g->d_lpdict, g->ndict,
+                                           (int)d.lds));
+            hipLaunchKernelGGL(kern, dim3((unsigned)g->nblk), dim3(1024), d.lds, st, a, g->d_lpdict, g->ndict,
                                g->d_lpidx);
             HS_HIP(hipGetLastError());
             return HMMSORT_OK;
         };
-        if (sptg <= 14) rc = go(gen_vit_blockG<14>);
+        if (d.spt == 14) rc = go(gen_vit_blockG<14>);
         else rc = go(gen_vit_blockG<21>);
     } else
-    if (spt == 1 && nbthr) rc = launch_block_sweep<1, true, false, true>(g, a, threads, lds, st);
-    else if (spt == 2 && nbthr) rc = launch_block_sweep<2, true, false, true>(g, a, threads, lds, st);
-    else if (spt == 1) rc = launch_block_sweep<1, false, false, true>(g, a, threads, lds, st);
-    else if (spt == 2) rc = launch_block_sweep<2, false, false, true>(g, a, threads, lds, st);
-    else if (spt == 4) rc = launch_block_sweep<4, false, false, true>(g, a, threads, lds, st);
-    else if (!gcol && tl) rc = launch_block_sweep<0, false, false, true>(g, a, threads, lds, st);
-    else if (!gcol) rc = launch_block_sweep<0, false, false, false>(g, a, threads, lds, st);
-    else if (tl) rc = launch_block_sweep<0, false, true, true>(g, a, threads, lds, st);
-    else rc = launch_block_sweep<0, false, true, false>(g, a, threads, lds, st);
+    if (d.spt == 1 && d.spec) rc = launch_block_sweep<1, true, false, true>(g, a, d.threads, d.lds, st);
+    else if (d.spt == 2 && d.spec) rc = launch_block_sweep<2, true, false, true>(g, a, d.threads, d.lds, st);
+    else if (d.spt == 1) rc = launch_block_sweep<1, false, false, true>(g, a, d.threads, d.lds, st);
+    else if (d.spt == 2) rc = launch_block_sweep<2, false, false, true>(g, a, d.threads, d.lds, st);
+    else if (d.spt == 4) rc = launch_block_sweep<4, false, false, true>(g, a, d.threads, d.lds, st);
+    else if (!d.gcol && d.tlds) rc = launch_block_sweep<0, false, false, true>(g, a, d.threads, d.lds, st);
+    else if (!d.gcol) rc = launch_block_sweep<0, false, false, false>(g, a, d.threads, d.lds, st);
+    else if (d.tlds) rc = launch_block_sweep<0, false, true, true>(g, a, d.threads, d.lds, st);
+    else rc = launch_block_sweep<0, false, true, false>(g, a, d.threads, d.lds, st);
     if (rc) return rc;
     const int nb = (int)g->nblk;
     if (nb > 1) {
@@ -1126,7 +1224,7 @@ int blocked_viterbi(GenericDev *g, const double *d_y, int16_t *d_x, double *d_ll
         hipLaunchKernelGGL(k_block_ties, dim3(1), dim3(64), 0, st, g->d_frame, g->d_gapmin, nb, g->d_bdiag);
         HS_HIP(hipGetLastError());
     }
-    if (g->nms >= 64 && S > 1) {
+    if (d.seg) {
         // wide rows: backtrace by segments (k_seg_walk)
         // (test aids: HMMSORT_SEG_WI shortens the walk-in so that guesses fail and k_seg_fix has work,
         // HMMSORT_SEG_PASSES limits the fix passes so that open boundaries reach diag[0], HMMSORT_SEG_LEN sets the segment length)
@@ -1141,13 +1239,14 @@ int blocked_viterbi(GenericDev *g, const double *d_y, int16_t *d_x, double *d_ll
         const int nseg = (int)((T + SEG - 1) / SEG);
         if (!g->d_segbuf) {
             if ((rc = dalloc(&g->d_segbuf, (size_t)2 * nseg + 2, &g->bytes))) return rc;
+            if (blocked_poison()) HS_HIP(hipMemsetAsync(g->d_segbuf, 0xFF, ((size_t)2 * nseg + 2) * sizeof(int16_t), st));
         }
         int16_t *guess = g->d_segbuf, *below = g->d_segbuf + nseg + 1;
         hipLaunchKernelGGL(k_block_compose, dim3(1), dim3(256), 0, st, g->d_endv, g->d_fmap, g->d_fconst,
                            (int)S, nb, g->d_endstate, 0);
         HS_HIP(hipGetLastError());
-        const bool btl = (size_t)S * 2 <= 64 * 1024;
-        const size_t lds_seg = btl ? (size_t)S * 2 : 0;
+        const bool btl = d.seg_btl;
+        const size_t lds_seg = d.lds_seg;
         const dim3 gs((unsigned)((nseg + 255) / 256));
         if (btl) hipLaunchKernelGGL(k_seg_walk<true>, gs, dim3(256), lds_seg, st, g->d_T2, g->d_bt, g->nms, T, (int)S, SEG, WI,
                                     nseg, g->d_endstate + (nb - 1), d_x, guess, below);
@@ -1163,13 +1262,8 @@ int blocked_viterbi(GenericDev *g, const double *d_y, int16_t *d_x, double *d_ll
         }
     } else {
     // backtrace: rows of T2c staged W at a time; bt in LDS when it fits
-        const int nms1 = std::max(g->nms, 1);
-        int W = (int)std::max<int64_t>(1, std::min<int64_t>(64, (32 * 1024) / (nms1 * 2)));
-        size_t lds_map = (size_t)((S + 3) & ~3) * 2 + (size_t)((W * g->nms + 3) & ~3) * 2;
-        const int btm = lds_map + (size_t)S * 4 <= 150 * 1024 ? 1 : (lds_map + (size_t)S * 2 + 8 <= 150 * 1024 ? 2 : 0);
-        if (btm == 1) lds_map += (size_t)S * 4;
-        if (btm == 2) lds_map += (size_t)S * 2 + 8;
-        const int map_threads = S > 8192 ? 1024 : 256;
+        const int W = d.W, btm = d.btm, map_threads = d.map_threads;
+        const size_t lds_map = d.lds_map;
         auto go_map = [&](auto kern) -> int {
             if (lds_map > 64 * 1024)
                 HS_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_map));
@@ -1190,7 +1284,7 @@ int blocked_viterbi(GenericDev *g, const double *d_y, int16_t *d_x, double *d_ll
     hipLaunchKernelGGL(k_block_ll, dim3(nb), dim3(256), 0, st, d_y, d_x, T, (int)S, (int)g->B,
                        g->d_mean, g->d_in_ptr, g->d_in_src, g->d_in_lp, a.c0, a.den, g->d_llpart);
     HS_HIP(hipGetLastError());
-    const size_t lds_ll = (size_t)nb * 24 <= 60 * 1024 ? (size_t)nb * 24 : 0;
+    const size_t lds_ll = d.lds_ll;
     hipLaunchKernelGGL(k_block_ll_sum, dim3(1), dim3(256), lds_ll, st, g->d_llpart, nb, d_ll);
     HS_HIP(hipGetLastError());
     return HMMSORT_OK;

@@ -77,6 +77,8 @@ int blocked_set_model(GenericDev *g, const HostModel &m);
 void blocked_destroy(GenericDev *g);
 int blocked_viterbi(GenericDev *g, const double *d_y, int16_t *d_x, double *d_ll, hipStream_t st);
 int blocked_diagnostics(GenericDev *g, hipStream_t st, int64_t diag[8]);
+// the kernels blocked_viterbi launches for this plan as it stands, as text ("sweep=... backtrace=... ll=..."): test aid
+int blocked_describe_dispatch(const GenericDev *g, char *buf, int64_t cap);
 bool blocked_estep_supported(const GenericDev *g);
 int64_t blocked_stats_len(const GenericDev *g);
 int blocked_estep(GenericDev *g, const double *d_y, double *d_stats, hipStream_t st);

@@ -750,3 +750,14 @@ int generic_engine_create(std::unique_ptr<Engine> *out, const HostModel &m, int6
 }
 
 }  // namespace hmmsort
+
+// Test aid outside the documented ABI (like hmmsort_selftest_scans): which kernels a decode of this blocked plan
+// launches, e.g. "sweep=gen_vit_block1<8> backtrace=seg ll=lds" (generic_blocked.hip, blocked_pick).  Every blocked
+// plan is a GenericEngine (generic_engine_create is the only maker of that engine id).
+extern "C" int hmmsort_selftest_blocked_dispatch(const hmmsort_plan *plan, char *buf, int64_t cap)
+{
+    using namespace hmmsort;
+    HS_CHECK(plan && plan->eng && plan->eng->id == HMMSORT_ENGINE_BLOCKED, HMMSORT_EINVAL,
+             "selftest_blocked_dispatch: needs a plan on the blocked engine");
+    return blocked_describe_dispatch(static_cast<const GenericEngine *>(plan->eng.get())->g, buf, cap);
+}

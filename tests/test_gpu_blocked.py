@@ -55,19 +55,72 @@ def test_reference_viterbi_test_shape(O, H):
     p.close()
 
 
-# (3, 58): 9 919 states, one LDS column updated in place; (4, 40): 9 283 states, constants re-read
-# every sample; (4, 45): 11 837 states with more multi-source states; (4, 48): 13 443 states, columns
-# in global memory with the constants in registers; (4, 56): 18 371 states, columns in
-# global memory again (larger dictionary index range, more rows per thread)
+def blocked_dispatch(H, plan):
+    """the kernels a decode of this blocked plan launches, as the library names them (the undeclared test aid
+    hmmsort_selftest_blocked_dispatch; csrc/generic_blocked.hip, blocked_pick)"""
+    import ctypes as C
+    fn = H._lib.lib().hmmsort_selftest_blocked_dispatch
+    fn.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
+    fn.restype = C.c_int
+    buf = C.create_string_buffer(256)
+    assert fn(plan._h, buf, len(buf)) == 0
+    return buf.value.decode()
+
+
+# Every shape here has K <= 64 and two to five templates, so by default it runs a structured sweep (pair_vit_block for
+# two templates, multi_vit_block for three and four) and the generic sweep only with HMMSORT_PAIR=0, which is what the
+# host ladder drops to after a near-tie.  Both are decoded and each mode asserts the kernels the library says it runs:
+# (3, 20) and (2, 33): two states per lane, wave-specialised; (4, 12): one state per lane; (3, 58), 9 919 states, and
+# (4, 40), 9 283: one LDS column updated in place, ten states per thread; (4, 45): 11 793 states, twelve per thread;
+# (4, 48): 13 443 states, columns in global memory with the constants in registers, 14 per thread; (4, 56): 18 371
+# states, the same with 21 per thread.  All walk back by segments and sum ll from LDS.
+OVERLAP_SHAPES = {   # (N, K): structured sweep, generic sweep
+    (3, 20): ("multi<3>", "gen_vit_block<2,true,false,true>"),
+    (2, 33): ("pair", "gen_vit_block<2,true,false,true>"),
+    (4, 12): ("multi<4>", "gen_vit_block<1,true,false,true>"),
+    (3, 58): ("multi<3>", "gen_vit_block1<10>"),
+    (4, 40): ("multi<4>", "gen_vit_block1<10>"),
+    (4, 45): ("multi<4>", "gen_vit_block1<12>"),
+    (4, 48): ("multi<4>", "gen_vit_blockG<14>"),
+    (4, 56): ("multi<4>", "gen_vit_blockG<21>")}
+
+
 @pytest.mark.parametrize("N,K,T", [(3, 20, 30011), (2, 33, 4097), (4, 12, 25000), (3, 58, 9000),
                                    (4, 40, 6000), (4, 45, 5000), (4, 48, 5000), (4, 56, 3000 + 4096)])
-def test_overlap_shapes(O, H, N, K, T):
+def test_overlap_shapes(O, H, N, K, T, monkeypatch):
+    import torch
+    structured, generic = OVERLAP_SHAPES[N, K]
     temps = _templates(H, K, N)
     pp = [0.01, 0.006, 0.008, 0.005][:N]
     sm = H.StateMatrix.create(N, K, np.log(pp), True)
     y = H.create_signal(T, 0.3, pp, temps, seed=5 + N)
-    _check(O, H, y, sm, temps, 0.3)
+    xo, llo = O.viterbi(y, to_oracle_sm(O, sm), temps, 0.3)
+    # default: the host-buffer entry point, as before, on the structured sweep
+    plan = H.Plan(T, sm, temps, 0.3)
+    assert blocked_dispatch(H, plan) == "sweep=%s backtrace=seg ll=lds" % structured
+    assert plan.overlap_sweep() == (N if N > 2 else 2)
+    plan.close()
+    x, ll = H.viterbi(y, sm, temps, 0.3)
+    assert np.array_equal(x, xo)
+    assert abs(ll - llo) <= LL_RTOL * abs(llo)
     assert H.get_option("last_escalations") == 0
+    # the generic sweep on the same input (plan API: no ladder that could end on another engine)
+    H.shutdown()
+    monkeypatch.setenv("HMMSORT_PAIR", "0")
+    st = torch.cuda.current_stream().cuda_stream
+    plan = H.Plan(T, sm, temps, 0.3)
+    assert blocked_dispatch(H, plan) == "sweep=%s backtrace=seg ll=lds" % generic
+    assert plan.overlap_sweep() == 0
+    dx = torch.zeros(T, dtype=torch.int16, device="cuda")
+    dll = torch.full((1,), np.nan, dtype=torch.float64, device="cuda")
+    plan.viterbi(torch.from_numpy(y).cuda(), dx, dll, st)
+    d = plan.diagnostics(st)
+    plan.close()
+    monkeypatch.delenv("HMMSORT_PAIR", raising=False)
+    assert d[0] == 0, d
+    nbad = int(np.count_nonzero(dx.cpu().numpy() != xo))
+    assert nbad == 0, "generic sweep: path differs at %d samples (diag %s)" % (nbad, d)
+    assert abs(float(dll.cpu()[0]) - llo) <= LL_RTOL * abs(llo)
 
 
 def test_ring_model_through_blocked_engine(O, H):
