@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -126,6 +127,7 @@ struct WaveDev {
     double *gsil = nullptr;           // C x T   gamma_t(silent)
     double *phead = nullptr;          // C x N x L posteriors of the virtual onsets t' = -j ([a*L + j], j = 1..L-1; [a*L] = 0)
     double *plogz = nullptr;          // C       log-likelihood of the recording
+    double *fshift = nullptr;         // C*nch   scale of chain c's forward values against chain c-1's (kw_post_shift)
     double *pcnt = nullptr;           // C*N x kPostParts partial sums of rho (expected spike counts)
     // exact near-tie resolver (wave_ties.hip)
     int64_t *tie_cnt = nullptr;       // C x 8 counters (kTie* below); lives behind diag
@@ -170,6 +172,97 @@ struct WProfScope {
 constexpr int wpsi_bits_c(int N) { int b = 1; while ((1 << b) < N + 1) b++; return b + 1; }
 constexpr int wpsi_epw_c(int N) { return 32 / wpsi_bits_c(N); }
 constexpr int wpsi_words_c(int N) { return (N + 1 + wpsi_epw_c(N) - 1) / wpsi_epw_c(N); }
+
+// ---- which kernels a call launches ---------------------------------------------------------------
+// Every sweep kernel is a template on the number of rings (dispatch_N); on top of that the host chooses among the
+// variants below.  wave_pick is the one place that decides: wave_prepare, wave_viterbi_sweep, wave_viterbi_post and
+// wave_estep_sweeps launch from its answer, and hmmsort_selftest_wave_dispatch (wave_engine.hip) prints it, so a
+// test names the row it pins.
+
+// per-source exit -> entry values take the O(N^2) junction code, which is built for up to kWaveMaxPerSource rings
+// (with 12-13 rings of fewer than 32 states those kernels -- 200+ spilled scalar registers -- gave wrong forward
+// values on gfx950, found by tests/test_gpu_wave_edges.py; such lists go to the blocked / strict engines)
+constexpr int kWaveMaxPerSource = 8;
+
+// rows per thread of the pre-pass.  Measured: N = 4: 4 rows 0.30 ms, 8 rows 0.19 ms, 16 rows 0.24 ms (10 M samples);
+// N = 8: 8 rows 2.44 ms, 4 rows 1.92 ms (40 M)
+constexpr int wave_pre_rows(int N) { return N <= 4 ? 8 : 4; }
+// Segments per workgroup of the light backtrace, by words per back-pointer row (one-word
+// rows measured with 16, 32 and 64 beside the backward sweep; wider rows keep 64)
+constexpr int wave_bt_spw(int N) { return wpsi_words_c(N) == 1 ? 32 : 64; }
+
+enum { kWaveCallDecode = 1, kWaveCallEstep = 2, kWaveCallDecodeEstep = 3, kWaveCallPosteriors = 4 };
+enum { kGsumNone = 0, kGsumFused = 1, kGsumMx = 2, kGsumGeneric = 3 };
+
+struct WavePick {
+    int N = 0, call = 0;
+    bool uc = true;       // UC of kw_vit, kw_vit_redo, kw_fwd, kw_bwd: one exit -> entry value per target ring
+    int pre_rows = 0;     // kw_prepass<N>: consecutive onsets per thread
+    // forward / backward sweeps and statistics (calls 2, 3, 4)
+    bool sweeps = false;
+    bool logdl = false;   // kw_fwd: one delay line per ring, in log form (more than 8 rings)
+    int ft = 0;           // kw_bwd<N, UC, FT>: accumulator tiles of the fused statistics, 0 = unfused
+    bool gs = false;      // kw_bwd<N, UC, 0, true>: the posterior form (keeps rho and gamma(silent) of every sample)
+    int gsum = kGsumNone; // who sums G1: nobody (posterior call), kw_bwd, kw_gsum_mx<N, nt> x ngrp, kw_gsum_generic
+    int nt = 0, ngrp = 0;
+    // decode (calls 1, 3)
+    bool decode = false;
+    bool redo = false;    // certificate rounds with kw_vit_redo run (more than one chain)
+    bool tight = false;   // kw_vit_redo<N, UC, true>: up to 4 rings beside an E-step
+    bool light = false;   // kw_backtrace_light<N, spw> instead of kw_backtrace<N>
+    int spw = 0;
+};
+
+// The HMMSORT_GSUM_GENERIC / HMMSORT_GSUM_SEPARATE switches are read at every call.
+inline WavePick wave_pick(const WaveDev *r, int call)
+{
+    const WaveGeom &g = r->g;
+    const int N = g.N, L = g.L;
+    WavePick p;
+    p.N = N; p.call = call;
+    p.uc = r->uniform_cx || N > kWaveMaxPerSource;   // per-source values: up to 8 rings (wave_supported)
+    p.pre_rows = wave_pre_rows(N);
+    p.sweeps = call != kWaveCallDecode;
+    p.decode = call == kWaveCallDecode || call == kWaveCallDecodeEstep;
+    if (p.sweeps) {
+        p.logdl = N > 8;
+        p.gs = call == kWaveCallPosteriors;
+        const bool generic = getenv("HMMSORT_GSUM_GENERIC") != nullptr;
+        // 3-4 rings of at most 64 states, 5-8 rings of at most 128 (uniform exit -> entry values): the backward
+        // sweep accumulates G1 itself (matrix cores, LDS rings)
+        const bool fuse4 = N == 3 || N == 4, fuse8 = N >= 5 && N <= 8;
+        // posterior calls (wave_post.hip) keep rho of every sample: the unfused sweep
+        const bool sep = generic || p.gs || getenv("HMMSORT_GSUM_SEPARATE") != nullptr;
+        p.ft = sep ? 0 : (fuse4 && L <= 64) ? 1 : (fuse8 && r->uniform_cx && L <= 64) ? 2
+               : (fuse8 && r->uniform_cx && L <= 128) ? 4 : 0;
+        if (p.gs) p.gsum = kGsumNone;               // posterior-only call: no statistics
+        else if (p.ft > 0) p.gsum = kGsumFused;
+        else if (generic) p.gsum = kGsumGeneric;
+        else {
+            // up to 4 accumulator tiles per workgroup for N <= 8 (longer rings take one pass over rho per group of 4);
+            // more than 8 rings (16 lags per tile): up to 16 tiles, so that rings of up to 255 states need ONE pass
+            // over rho (128 B of posteriors per sample and pass at N = 16); HMMSORT_GSUM_TILES = 4 / 8 / 16: tuning aid
+            // (measured at N = 16, L = 255, 40 M samples: 4 tiles and four passes over rho 12.3 ms and 22 GB of HBM
+            // traffic, 16 tiles and one pass 10.2 ms)
+            static const int nt_big = getenv("HMMSORT_GSUM_TILES") ? atoi(getenv("HMMSORT_GSUM_TILES")) : 16;
+            const int want = nt_big >= 16 ? 16 : (nt_big >= 8 ? 8 : 4);
+            const int np = N <= 1 ? 1 : (N <= 2 ? 2 : (N <= 4 ? 4 : (N <= 8 ? 8 : 16)));   // kw_gsum_mx: rings padded to
+            const int lpt = 16 * (16 / np);                                                 // lags per tile
+            const int ntx = (L + lpt - 1) / lpt;
+            p.gsum = kGsumMx;
+            p.nt = N > 8 ? (ntx <= 4 ? 4 : (ntx <= 8 ? (want < 8 ? want : 8) : want)) : (ntx < 4 ? ntx : 4);
+            p.ngrp = (ntx + p.nt - 1) / p.nt;
+        }
+    }
+    if (p.decode) {
+        const bool beside = call == kWaveCallDecodeEstep;
+        p.redo = g.nch > 1;
+        p.tight = N <= 4 && beside;
+        p.light = g.backtrace == 2 || (g.backtrace == 0 && beside);
+        p.spw = wave_bt_spw(N);
+    }
+    return p;
+}
 
 // ---- cross-lane helpers (wave64) -------------------------------------------------------------
 __device__ __forceinline__ double wave_bcast(double v, int lane)

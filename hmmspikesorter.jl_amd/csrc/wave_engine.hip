@@ -2,6 +2,7 @@
 // Design notes: wave_common.h / DESIGN.md section 3.3.
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
@@ -32,11 +33,7 @@ static bool ring_uniform_cx(const RingModel &R)
     return true;
 }
 
-// per-source exit -> entry values take the O(N^2) junction code, which is built for up to kWaveMaxPerSource rings
-// (with 12-13 rings of fewer than 32 states those kernels -- 200+ spilled scalar registers -- gave wrong forward
-// values on gfx950, found by tests/test_gpu_wave_edges.py; such lists go to the blocked / strict engines)
-constexpr int kWaveMaxPerSource = 8;
-
+// (per-source exit -> entry values: up to kWaveMaxPerSource rings, wave_common.h)
 bool wave_supported(const HostModel &m, int64_t T, std::string *why)
 {
     auto no = [&](const char *w) { if (why) *why = w; return false; };
@@ -332,7 +329,7 @@ void wave_destroy(WaveDev *r)
     if (!r) return;
     void *ptrs[] = {r->d_cst, r->d_mean, r->d_meanT, r->d_cint, r->d_msq, r->d_ctab, r->d_states, r->Rf, r->W2, r->virt, r->ysum,
                     r->psi, r->vpre, r->vend, r->vfail, r->vcert, r->bstate, r->redo, r->final_state, r->part, r->FA0,
-                    r->FV, r->FREF, r->fpre, r->bpre, r->bown, r->rho, r->Zc, r->partS, r->partG, r->yhead,
+                    r->FV, r->FREF, r->fpre, r->bpre, r->bown, r->rho, r->Zc, r->fshift, r->partS, r->partG, r->yhead,
                     r->extra, r->pp, r->diag, r->vlist, r->dbg, r->trash, r->tie_list, r->tie_off, r->tie_walk, r->tie_guess,
                     r->tie_c, r->tie_ok, r->tie_v, r->gsil, r->phead, r->plogz, r->pcnt};
     for (void *p : ptrs)
@@ -419,7 +416,7 @@ __device__ __forceinline__ void virtual_onsets(const WaveGeom &g, int ch, const 
 // Grid (1 + tiles, channels): workgroup 0 of a channel computes the virtual onsets (from mean_states, the
 // state-major means; the tiles use the lag-major table `mean`), so tile i is workgroup blockIdx.x = i + 1.
 // ------------------------------------------------------------------------------------------
-template <int N> constexpr int pre_rows() { return N <= 4 ? 8 : 4; }   // measured: N = 4: 4 rows 0.30 ms, 8 rows 0.19 ms, 16 rows 0.24 ms (10 M samples); N = 8: 8 rows 2.44 ms, 4 rows 1.92 ms (40 M)
+template <int N> constexpr int pre_rows() { return wave_pre_rows(N); }   // (wave_common.h, with what was measured)
 
 // dynamic LDS of a pre-pass workgroup: the padded y tile with its tail of max(L, 256) samples
 template <int N> static size_t pre_lds(int L)
@@ -569,8 +566,10 @@ int wave_prepare(WaveDev *r, const double *d_y, hipStream_t st)
     r->bound_y = nullptr;
     const WaveGeom &g = r->g;
     HS_HIP(hipMemsetAsync(r->ysum, 0, 2 * g.C * sizeof(double), st));
+    const WavePick p = wave_pick(r, kWaveCallDecode);   // the pre-pass is the same for every call
     int rc = dispatch_N(g.N, [&](auto n) {
         constexpr int N = decltype(n)::value;
+        HS_CHECK(p.pre_rows == pre_rows<N>(), HMMSORT_EINVAL, "wave pre-pass: no kernel with %d rows per thread", p.pre_rows);
         WPROF(r, "kw_prepass", st);
         constexpr int kPreTile = 256 * pre_rows<N>();
         hipLaunchKernelGGL((kw_prepass<N>), dim3(1 + (unsigned)((g.T + kPreTile - 1) / kPreTile), g.C), dim3(256),
@@ -719,7 +718,56 @@ int wave_engine_create(std::unique_ptr<Engine> *out, const std::vector<HostModel
     return HMMSORT_OK;
 }
 
+// wave_pick's answer for a call in words, e.g.
+//   "prepass<11> fwd<11,uc,logdl> bwd<11,uc,ft0> gsum=mx<11,8>x1 vit<11,uc> redo<11,uc> backtrace=rows<11>"
+// ("ps": per-source exit -> entry values; "gs": posterior form; "gsum=bwd": the backward sweep sums G1 itself),
+// then " | listed=a,b": the chains rounds 0 and 1 of the last decode's certificate listed for a re-sweep
+static int wave_describe_dispatch(const WaveDev *r, int call, char *buf, int64_t cap)
+{
+    HS_CHECK(r && buf && cap > 0, HMMSORT_EINVAL, "wave dispatch: needs a wave plan and a buffer");
+    HS_CHECK(call >= kWaveCallDecode && call <= kWaveCallPosteriors, HMMSORT_EINVAL,
+             "wave dispatch: call %d is none of 1 decode, 2 E-step, 3 decode + E-step, 4 posteriors", call);
+    const WavePick p = wave_pick(r, call);
+    const char *uc = p.uc ? "uc" : "ps";
+    char s[512];
+    int n = snprintf(s, sizeof s, "prepass<%d>", p.N);
+    auto add = [&](const char *fmt, auto... a) {
+        if (n >= 0 && n < (int)sizeof s) n += snprintf(s + n, sizeof s - (size_t)n, fmt, a...);
+    };
+    if (p.sweeps) {
+        add(" fwd<%d,%s%s> bwd<%d,%s,ft%d%s>", p.N, uc, p.logdl ? ",logdl" : "", p.N, uc, p.ft, p.gs ? ",gs" : "");
+        if (p.gsum == kGsumMx) add(" gsum=mx<%d,%d>x%d", p.N, p.nt, p.ngrp);
+        else add(" gsum=%s", p.gsum == kGsumFused ? "bwd" : p.gsum == kGsumGeneric ? "generic" : "none");
+    }
+    if (p.decode) {
+        add(" vit<%d,%s>", p.N, uc);
+        if (p.redo) add(" redo<%d,%s%s>", p.N, uc, p.tight ? ",tight" : "");
+        else add(" redo=%s", "none");
+        if (p.light) add(" backtrace=light<%d,%d>", p.N, p.spw);
+        else add(" backtrace=rows<%d>", p.N);
+        int32_t heads[2] = {0, 0};
+        HS_HIP(hipDeviceSynchronize());
+        HS_HIP(hipMemcpy(heads, r->heads, sizeof heads, hipMemcpyDeviceToHost));
+        add(" | listed=%d,%d", (int)heads[0], (int)heads[1]);
+    }
+    HS_CHECK(n >= 0 && n < (int)sizeof s && n < cap, HMMSORT_EINVAL, "wave dispatch: buffer of %lld bytes too small",
+             (long long)cap);
+    memcpy(buf, s, (size_t)n + 1);
+    return HMMSORT_OK;
+}
+
 }  // namespace hmmsort
+
+// Test aid outside the documented ABI (like hmmsort_selftest_blocked_dispatch): which kernels a call of this wave
+// plan launches (call: 1 decode, 2 E-step, 3 decode + E-step, 4 posteriors), as wave_pick decides at this moment.
+// Every wave plan is a WaveEngine (wave_engine_create is the only maker of that engine id).
+extern "C" int hmmsort_selftest_wave_dispatch(const hmmsort_plan *plan, int call, char *buf, int64_t cap)
+{
+    using namespace hmmsort;
+    HS_CHECK(plan && plan->eng && plan->eng->id == HMMSORT_ENGINE_WAVE, HMMSORT_EINVAL,
+             "selftest_wave_dispatch: needs a plan on the wave engine");
+    return wave_describe_dispatch(static_cast<const WaveEngine *>(plan->eng.get())->w, call, buf, cap);
+}
 
 // ---- self-test of the cross-lane primitives (DPP scans vs their shuffle references) ---------------
 namespace hmmsort {

@@ -882,7 +882,10 @@ __global__ __launch_bounds__(256) void kw_gsum_mx(WaveGeom g, const double *__re
     constexpr int TPS = (Bv + HS + TR - 1) / TR;   // tiles per column group
     // staging indices are split with shifts only: rows per column rounded up to powers of two (the surplus
     // rows are never loaded); integer divisions by 112 or 82 per element cost more than the MFMAs
-    constexpr int RRL = RR <= 64 ? 64 : (RR <= 128 ? 128 : (RR <= 256 ? 256 : 512)), YRL = (YR - 1) <= 128 ? 128 : ((YR - 1) <= 256 ? 256 : 512);
+    constexpr int RRL = RR <= 64 ? 64 : (RR <= 128 ? 128 : (RR <= 256 ? 256 : 512)), YRL = (YR - 1) <= 128 ? 128 : ((YR - 1) <= 256 ? 256 : ((YR - 1) <= 512 ? 512 : 1024));
+    // (one ring with three or four tiles stages 594 / 850 rows of y: capped at 512, the rows behind were never loaded and
+    // the ring's last lags summed stale LDS -- tests/test_gpu_wave_dispatch.py, 1x514, 1x770, 1x1026)
+    static_assert(RR <= RRL && YR - 1 <= YRL, "kw_gsum_mx: a staged column does not fit its power-of-two split");
     constexpr int NRH = NP * RRL * CW / 256, NYM = CW * YRL / 256;
     extern __shared__ double lds[];
     const int L = g.L, ch = blockIdx.y, lag0 = blockIdx.z * NT * LPT;
@@ -1107,34 +1110,33 @@ static int wave_estep_sweeps(WaveDev *r, const double *d_y, double *d_stats, hip
     const int nchT = g.C * g.nch;
     if (!r->keep_post) r->post_valid = false;   // the fused sweep does not keep rho
     int rowsG = 0;
+    // which kernels (wave_common.h): the sweeps of a fused decode + E-step call are those of an E-step
+    const WavePick p = wave_pick(r, r->keep_post ? kWaveCallPosteriors : kWaveCallEstep);
     int rc = dispatch_N(N, [&](auto n) {
         constexpr int NN = decltype(n)::value;
-        const size_t ldsf = ((size_t)(NN > 8 ? 1 : 2) * NN * (g.RB + 1) + 5 + 3 * NN + NN * NN) * sizeof(double);
-        const bool generic = getenv("HMMSORT_GSUM_GENERIC") != nullptr;
-        // 3-4 rings of at most 64 states, 5-8 rings of at most 128 (uniform exit -> entry values): the backward
-        // sweep accumulates G1 itself (matrix cores, LDS rings)
+        const size_t ldsf = ((size_t)(p.logdl ? 1 : 2) * NN * (g.RB + 1) + 5 + 3 * NN + NN * NN) * sizeof(double);
+        const bool generic = p.gsum == kGsumGeneric;
         constexpr bool kFuse4 = NN == 3 || NN == 4, kFuse8 = NN >= 5 && NN <= 8;
-        // posterior calls (wave_post.hip) keep rho of every sample: the unfused sweep
-        const bool sep = generic || r->keep_post || getenv("HMMSORT_GSUM_SEPARATE") != nullptr;
-        const int ft = sep ? 0 : (kFuse4 && L <= 64) ? 1 : (kFuse8 && r->uniform_cx && L <= 64) ? 2
-                       : (kFuse8 && r->uniform_cx && L <= 128) ? 4 : 0;
+        const int ft = p.ft;
+        HS_CHECK(p.logdl == (NN > 8) && (ft == 0 || (kFuse4 && ft == 1) || (kFuse8 && p.uc && (ft == 2 || ft == 4))),
+                 HMMSORT_EINVAL, "wave E-step: no kernel for the picked row (ft %d)", ft);
         const bool fuse = ft > 0;
         const int ym = bwd_yring(ft);
         const size_t ldsb = ((size_t)(NN + 1) * (g.RB + 1) + 4 + 3 * NN + NN * NN +
                              (fuse ? ym + (128 + 8 * (NN <= 4 ? 1 : 2)) * (NN <= 4 ? 4 : 8) : 0)) * sizeof(double);
         auto kf = kw_fwd<NN, true>;
         auto kb = kw_bwd<NN, true>;
-        if constexpr (NN <= 8) {   // per-source exit -> entry values: up to 8 rings (wave_supported)
-            if (!r->uniform_cx) { kf = kw_fwd<NN, false>; kb = kw_bwd<NN, false>; }
+        if constexpr (NN <= kWaveMaxPerSource) {   // per-source exit -> entry values: up to 8 rings (wave_supported)
+            if (!p.uc) { kf = kw_fwd<NN, false>; kb = kw_bwd<NN, false>; }
         }
-        if (r->keep_post) {
+        if (p.gs) {
             kb = kw_bwd<NN, true, 0, true>;
-            if constexpr (NN <= 8) {
-                if (!r->uniform_cx) kb = kw_bwd<NN, false, 0, true>;
+            if constexpr (NN <= kWaveMaxPerSource) {
+                if (!p.uc) kb = kw_bwd<NN, false, 0, true>;
             }
         }
         if constexpr (kFuse4) {
-            if (ft == 1) kb = r->uniform_cx ? kw_bwd<NN, true, 1> : kw_bwd<NN, false, 1>;
+            if (ft == 1) kb = p.uc ? kw_bwd<NN, true, 1> : kw_bwd<NN, false, 1>;
         }
         if constexpr (kFuse8) {
             if (ft == 2) kb = kw_bwd<NN, true, 2>;
@@ -1162,19 +1164,13 @@ static int wave_estep_sweeps(WaveDev *r, const double *d_y, double *d_stats, hip
         if (r->keep_post) return HMMSORT_OK;        // posterior-only call: no statistics
         constexpr int NPx = NN <= 1 ? 1 : (NN <= 2 ? 2 : (NN <= 4 ? 4 : (NN <= 8 ? 8 : 16)));
         constexpr int LPTx = 16 * (16 / NPx), HSx = LPTx - 16;
-        const int ntx = (L + LPTx - 1) / LPTx;
         if (fuse) {
             rowsG = g.nch;                      // partG[ch][chain][N L], written by kw_bwd
         } else if (!generic) {
-            // up to 4 accumulator tiles per workgroup for N <= 8 (longer rings take one pass over rho per group of 4);
-            // more than 8 rings (16 lags per tile): up to 16 tiles, so that rings of up to 255 states need ONE pass
-            // over rho (128 B of posteriors per sample and pass at N = 16); HMMSORT_GSUM_TILES = 4 / 8 / 16: tuning aid
-            // (measured at N = 16, L = 255, 40 M samples: 4 tiles and four passes over rho 12.3 ms and 22 GB of HBM
-            // traffic, 16 tiles and one pass 10.2 ms)
-            static const int nt_big = getenv("HMMSORT_GSUM_TILES") ? atoi(getenv("HMMSORT_GSUM_TILES")) : 16;
-            const int want = nt_big >= 16 ? 16 : (nt_big >= 8 ? 8 : 4);
-            const int ntk = NN > 8 ? (ntx <= 4 ? 4 : (ntx <= 8 ? (want < 8 ? want : 8) : want)) : (ntx < 4 ? ntx : 4);
-            const int ngrp = (ntx + ntk - 1) / ntk;
+            // accumulator tiles per workgroup and passes over rho: wave_pick (wave_common.h)
+            const int ntk = p.nt, ngrp = p.ngrp;
+            HS_CHECK(p.gsum == kGsumMx && ngrp >= 1 && (NN > 8 ? (ntk == 4 || ntk == 8 || ntk == 16) : (ntk >= 1 && ntk <= 4)) &&
+                     (int64_t)ntk * ngrp * LPTx >= L, HMMSORT_EINVAL, "wave E-step: no statistics kernel with %d tiles", ntk);
             rowsG = (int)((g.T + kGxSubs * 8 * (int64_t)kGxBv - 1) / (kGxSubs * 8 * (int64_t)kGxBv));
             constexpr int RRx = kGxTR + HSx, RRPx = RRx + RRx / 16 + 1;
             const size_t l1 = ((size_t)8 * (RRPx * NPx + 2) + (size_t)8 * (kGxTR + 19 + LPTx * (ntk - 1))) * 8;

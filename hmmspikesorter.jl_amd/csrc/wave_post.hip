@@ -22,11 +22,57 @@ namespace hmmsort {
 constexpr int kPT = 2048, kPR = 8;                       // samples per workgroup (256 threads), per thread
 __host__ __device__ __forceinline__ int ppad(int i) { return i + (i >> 3); }   // lanes read at a stride of kPR doubles: one pad per 8
 
+// Scale of chain c's forward values against chain c-1's, F_c - F_{c-1}: the difference between the warm-up copy of a
+// boundary quantity in chain c and chain c-1's own value of it.  Every converged boundary entry gives the same
+// number; it is read where the forward certificate (kw_fb_check, wave_estep.hip) reads its frame constant, at the
+// entry of LARGEST POSTERIOR WEIGHT: the silent state at tc-1 or one of the N L onsets still inside their rings.
+// (The silent entry alone is not enough: where a chain boundary falls inside a certain spike, "silent at tc-1" has a
+// posterior of e^-500, the two sweeps agree on it to no digit -- which the certificate, weighting it by that
+// posterior, rightly ignores -- and logz came out 2-3 % off: 9 and 13 rings of 64 states, tests/test_gpu_wave_dispatch.py.)
+// One wavefront per chain; chain 0 of a channel has no boundary.
+__global__ __launch_bounds__(64) void kw_post_shift(WaveGeom g, const double *__restrict__ FA0,
+                                                    const double *__restrict__ FV, const double *__restrict__ FREF,
+                                                    const double *__restrict__ fpre, const double *__restrict__ rho,
+                                                    double *__restrict__ fshift)
+{
+    const int lane = threadIdx.x;
+    const int cg = blockIdx.x, ch = cg / g.nch, c = cg % g.nch;
+    if (c == 0) { if (lane == 0) fshift[cg] = 0.0; return; }
+    const int N = g.N, L = g.L;
+    const int64_t T = g.T, tc = (int64_t)c * g.B;            // tc >= B >= L + 16: every onset below is inside the data
+    const int64_t FR = 1 + (int64_t)L * (N + 1);
+    const double *FAc = FA0 + (int64_t)ch * T, *FRc = FREF + (int64_t)ch * T, *FVc = FV + (int64_t)ch * N * T;
+    const double *rhoc = rho + (int64_t)ch * N * T;
+    // entry (a, e): the onset t' = tc-1-e of ring a, e = 0..L-1
+    auto diff = [&](int a, int e) {
+        const int64_t tp = tc - 1 - e, jj = tp - (tc - L);
+        const double hv = fpre[cg * FR + 1 + jj * (N + 1) + a], hs = fpre[cg * FR + 1 + jj * (N + 1) + N];
+        const double mv = FVc[(int64_t)a * T + tp], ms = FRc[tp];
+        if (hv == mv && hs == ms) return 0.0;
+        return (hs - ms) + (flog(hv) - flog(mv));
+    };
+    double ringmass = 0.0;
+    for (int idx = lane; idx < N * L; idx += 64) ringmass += rhoc[(int64_t)(idx / L) * T + (tc - 1 - idx % L)];
+    ringmass = wave_sum(ringmass);
+    double wb = lane == 0 ? fmax(1.0 - ringmass, 0.0) : -1.0;   // the silent entry: what the rings leave
+    double db = fpre[cg * FR] - FAc[tc - 1];
+    for (int idx = lane; idx < N * L; idx += 64) {
+        const int a = idx / L, e = idx % L;
+        const double w = rhoc[(int64_t)a * T + (tc - 1 - e)];
+        if (w > wb) { wb = w; db = diff(a, e); }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const double ow = __shfl_xor(wb, o), od = __shfl_xor(db, o);
+        if (ow > wb) { wb = ow; db = od; }
+    }
+    if (lane == 0) fshift[cg] = db;
+}
+
 // one wavefront per channel
 __global__ __launch_bounds__(64) void kw_post_head(WaveGeom g, const WaveConst *__restrict__ cst,
                                                    const double *__restrict__ virt,
                                                    const double *__restrict__ yhead, const double *__restrict__ Zc,
-                                                   const double *__restrict__ fpre, const double *__restrict__ FA0,
+                                                   const double *__restrict__ fshift,
                                                    double *__restrict__ phead, double *__restrict__ plogz)
 {
     const int N = g.N, L = g.L, ch = blockIdx.x, lane = threadIdx.x;
@@ -41,11 +87,9 @@ __global__ __launch_bounds__(64) void kw_post_head(WaveGeom g, const WaveConst *
     // backward values are exact (beta = 0 at the end of the data), so its normaliser is z + F_last, and
     // F_c - F_{c-1} = (warm-up copy of la0(tc-1) in chain c) - (chain c-1's own la0(tc-1)): the pair the forward
     // certificate compares.  The sweeps leave the emission constant A = -log(sigma sqrt(2 pi)) of every sample out
-    // (it cancels in every posterior): T A is added back here.
+    // (it cancels in every posterior): T A is added back here.  The differences: kw_post_shift.
     double s = 0.0;
-    const int64_t FR = 1 + (int64_t)L * (N + 1);
-    for (int c = 1 + lane; c < g.nch; c += 64)
-        s += fpre[((int64_t)ch * g.nch + c) * FR] - FA0[(int64_t)ch * g.T + (int64_t)c * g.B - 1];
+    for (int c = 1 + lane; c < g.nch; c += 64) s += fshift[(int64_t)ch * g.nch + c];
     s = wave_sum(s);
     if (lane == 0) plogz[ch] = (Zc[(int64_t)ch * g.nch + g.nch - 1] - s) + (double)g.T * cst[ch].A;
 }
@@ -272,7 +316,7 @@ static int post_alloc(WaveDev *r)
         return HMMSORT_OK;
     };
     int rc;
-    if ((rc = A(&r->phead, nl)) || (rc = A(&r->plogz, (size_t)g.C)) ||
+    if ((rc = A(&r->phead, nl)) || (rc = A(&r->plogz, (size_t)g.C)) || (rc = A(&r->fshift, (size_t)g.C * g.nch)) ||
         (rc = A(&r->pcnt, (size_t)g.C * g.N * kPostParts)) || (rc = A(&r->gsil, ct)))
         return rc;
     if (getenv("HMMSORT_POISON")) (void)hipMemset(r->gsil, 0xFF, ct * sizeof(double));
@@ -296,7 +340,9 @@ int wave_posteriors(WaveDev *r, const double *d_y, double *d_onset, double *d_oc
     r->post_valid = false;
     if ((rc = wave_post_sweeps(r, d_y, st))) return rc;
     { WPROF(r, "kw_post_head", st);
-      hipLaunchKernelGGL(kw_post_head, dim3(g.C), dim3(64), 0, st, g, r->d_cst, r->virt, r->yhead, r->Zc, r->fpre, r->FA0,
+      hipLaunchKernelGGL(kw_post_shift, dim3(g.C * g.nch), dim3(64), 0, st, g, r->FA0, r->FV, r->FREF, r->fpre, r->rho,
+                         r->fshift);
+      hipLaunchKernelGGL(kw_post_head, dim3(g.C), dim3(64), 0, st, g, r->d_cst, r->virt, r->yhead, r->Zc, r->fshift,
                          r->phead, r->plogz); }
     HS_HIP(hipGetLastError());
     const size_t nct = (size_t)g.C * g.N * g.T * sizeof(double);

@@ -1135,21 +1135,22 @@ static int wave_lds_attr(Kern kern, size_t lds)
     return HMMSORT_OK;
 }
 
-// Segments per workgroup of the light backtrace, by words per back-pointer row (one-word
-// rows measured with 16, 32 and 64 beside the backward sweep; wider rows keep 64)
-template <int N> constexpr int bt_spw() { return wpsi_words_c(N) == 1 ? 32 : 64; }
+// Segments per workgroup of the light backtrace (wave_common.h, with what was measured)
+template <int N> constexpr int bt_spw() { return wave_bt_spw(N); }
 
 constexpr int kVitRounds = 2;  // certificate + re-sweep rounds run unconditionally on device
 
+// (which of the two calls with a decode does not matter to the sweep: wave_pick's uc is the same)
 int wave_viterbi_sweep(WaveDev *r, const double *d_y, hipStream_t st)
 {
     const WaveGeom &g = r->g;
     const int nchT = g.C * g.nch;
+    const WavePick p = wave_pick(r, kWaveCallDecode);
     return dispatch_N(g.N, [&](auto n) {
         constexpr int N = decltype(n)::value;
         const size_t lds = ((size_t)N * (g.RB + 1) + 3 + 2 * N + N * N) * sizeof(double);
         auto kern = kw_vit<N, true>;
-        if constexpr (N <= 8) { if (!r->uniform_cx) kern = kw_vit<N, false>; }   // per-source values: up to 8 rings (wave_supported)
+        if constexpr (N <= kWaveMaxPerSource) { if (!p.uc) kern = kw_vit<N, false>; }   // per-source values: up to 8 rings (wave_supported)
         int rc = wave_lds_attr(kern, lds);
         if (rc) return rc;
         { WPROF(r, "kw_vit", st);
@@ -1166,20 +1167,22 @@ int wave_viterbi_post(WaveDev *r, const double *d_y, int16_t *d_x, double *d_ll,
 {
     const WaveGeom &g = r->g;
     const int nchT = g.C * g.nch;
-    const bool light = g.backtrace == 2 || (g.backtrace == 0 && beside);
+    const WavePick p = wave_pick(r, beside ? kWaveCallDecodeEstep : kWaveCallDecode);
+    const bool light = p.light;
     int rc = dispatch_N(g.N, [&](auto n) {
         constexpr int N = decltype(n)::value;
         const size_t lds = ((size_t)N * (g.RB + 1) + 3 + 2 * N + N * N) * sizeof(double);
         auto kern = kw_vit_redo<N, true, false>;
-        if constexpr (N <= 8) { if (!r->uniform_cx) kern = kw_vit_redo<N, false, false>; }   // per-source values: up to 8 rings (wave_supported)
-        if constexpr (N <= 4) { if (beside) kern = r->uniform_cx ? kw_vit_redo<N, true, true> : kw_vit_redo<N, false, true>; }
+        if constexpr (N <= kWaveMaxPerSource) { if (!p.uc) kern = kw_vit_redo<N, false, false>; }   // per-source values: up to 8 rings (wave_supported)
+        if constexpr (N <= 4) { if (p.tight) kern = p.uc ? kw_vit_redo<N, true, true> : kw_vit_redo<N, false, true>; }
+        HS_CHECK(p.spw == bt_spw<N>() && (N <= 4 || !p.tight), HMMSORT_EINVAL, "wave decode: no kernel for the picked row");
         int rc2 = wave_lds_attr(kern, lds);
         if (rc2) return rc2;
         // a round whose predecessor listed nothing returns at once (kw_vit_check); option "cert_rounds" = 1: all in full
         auto prev_head = [&](int round) -> const int32_t * {
             return (round > 0 && !g.cert_rounds && g.nch > 1) ? r->heads + round - 1 : nullptr;
         };
-        for (int round = 0; round < kVitRounds && g.nch > 1; round++) {
+        for (int round = 0; round < kVitRounds && p.redo; round++) {
             int32_t *head = r->heads + round, *list = r->vlist + (size_t)round * nchT;
             { WPROF(r, "kw_vit_check", st);
               hipLaunchKernelGGL(kw_vit_check, dim3(nchT), dim3(64), 0, st, g, r->vpre, r->vend, r->vfail, r->diag, 0, nullptr,
