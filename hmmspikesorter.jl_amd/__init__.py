@@ -9,12 +9,12 @@ from ._lib import (ENGINE_AUTO, ENGINE_BLOCKED, ENGINE_RING, ENGINE_STRICT, ENGI
                    get_option, set_option, shutdown)
 from .api import (HMMSpikeTemplateModel, HMMSpikingModel, ModelTrack, Posteriors, StateMatrix, backward,
                   extract_spiketimes, fit, fit_adaptive, fit_channels, fit_step_channels, forward,
-                  posterior_decode, posteriors, predict, reconstruct_signal, reconstruct_tracked, spike_confidence, train_model, train_step, unroll_mlseq, update,
+                  posterior_decode, posteriors, predict, reconstruct_signal, reconstruct_tracked, seed_templates, spike_confidence, train_model, train_step, unroll_mlseq, update,
                   viterbi, viterbi_step)
 from .device import Plan, stats_blend, stats_sum
 from .postprocess import (condense_candidates, condense_templates, find_best_overlap, match_templates,
                           prune_templates, remove_small, remove_sparse)
-from .sortdata import get_lp, sort_data
+from .sortdata import get_lp, learn_templates, sort_data
 from .synth import create_signal, create_spike_template
 
 __all__ = ["StateMatrix", "HMMSpikeTemplateModel", "HMMSpikingModel", "forward", "backward",
@@ -24,4 +24,5 @@ __all__ = ["StateMatrix", "HMMSpikeTemplateModel", "HMMSpikingModel", "forward",
            "ENGINE_RING", "ENGINE_BLOCKED", "ENGINE_WAVE", "get_lp", "sort_data", "find_best_overlap",
            "condense_candidates", "condense_templates", "remove_sparse", "remove_small", "prune_templates",
            "match_templates", "Posteriors", "posteriors", "posterior_decode", "spike_confidence",
-           "viterbi_step", "fit_adaptive", "reconstruct_tracked", "ModelTrack", "stats_blend"]
+           "viterbi_step", "fit_adaptive", "reconstruct_tracked", "ModelTrack", "stats_blend", "seed_templates",
+           "learn_templates"]

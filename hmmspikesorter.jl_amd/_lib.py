@@ -60,6 +60,20 @@ class Track(C.Structure):
     _fields_ = [("cap", _i64), ("n", _vp), ("first", _vp), ("own", _vp), ("w", _vp), ("mu", _vp), ("sigma", _vp)]
 
 
+class SeedOpt(C.Structure):
+    """struct hmmsort_seed_opt: negative align / refractory, max_iters <= 0 and a NaN threshold ask for the defaults"""
+    _fields_ = [("threshold", _f64), ("sigma", _f64), ("polarity", _int), ("align", _i64), ("refractory", _i64),
+                ("max_iters", _i64)]
+
+
+class SeedOut(C.Structure):
+    """struct hmmsort_seed_out: host arrays hmmsort_seed_templates fills"""
+    _fields_ = [("mu", _vp), ("sigma", _vp), ("lp", _vp), ("counts", _vp), ("n_events", _vp), ("iters", _vp),
+                ("times", _vp), ("labels", _vp), ("cap", _i64)]
+
+
+SEED_MAX_K, SEED_MAX_N, SEED_MAX_R = 1025, 16, 1024
+
 # name -> (restype, argtypes); every symbol include/hmmsort.h declares
 SIGNATURES = {
     "hmmsort_last_error": (C.c_char_p, []),
@@ -85,6 +99,8 @@ SIGNATURES = {
     "hmmsort_reconstruct_tracked": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
     "hmmsort_chunk_stitch": (_int, [_vp, _i64, _int, _int, _vp, _vp, _vp]),
     "hmmsort_samples_to_f64": (_int, [_vp, C.c_int, _i64, _i64, _vp, _vp]),
+    "hmmsort_seed_templates": (_int, [_vp, _int, _i64, _i64, _i64, C.POINTER(SeedOpt), C.POINTER(SeedOut)]),
+    "hmmsort_seed_templates_device": (_int, [_vp, _i64, _i64, _i64, C.POINTER(SeedOpt), C.POINTER(SeedOut), _vp]),
     "hmmsort_forward": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _f64, _vp]),
     "hmmsort_backward": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _f64, _vp]),
     "hmmsort_update": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _f64,

@@ -14,7 +14,7 @@ Reference methods mirrored (file:line relative to the reference root):
   unroll_mlseq                                                        src/extraction.jl:4
   fit(HMMSpikingModel, templates, X, chunksize)                       src/fit.jl:11-42
 Extensions (no counterpart in the reference): posteriors, posterior_decode, spike_confidence, fit_step_channels, viterbi_step,
-train_model(..., method="viterbi"), fit_adaptive and reconstruct_tracked.
+train_model(..., method="viterbi"), fit_adaptive, reconstruct_tracked, seed_templates and train_model(..., init="detect").
 """
 import ctypes as C
 from dataclasses import dataclass
@@ -322,8 +322,66 @@ class _EMSession:
         return lA_n, mu_n, float(o[K * N])
 
 
+_SEED_OPTS = ("threshold", "sigma", "polarity", "align", "refractory", "max_iters")
+
+
+def _seed_run(call, T, N, K, resolve_overlaps, opts):
+    """hmmsort_seed_templates / _device through `call(opt, out)`; the part after the C ABI that both forms share:
+    empty clusters are dropped and the state matrix is built from the kept entry log-probabilities."""
+    bad = sorted(set(opts) - set(_SEED_OPTS))
+    if bad:
+        raise TypeError("seed_templates: unknown option(s) %s; known: %s" % (", ".join(bad), ", ".join(_SEED_OPTS)))
+    T, N, K = int(T), int(N), int(K)
+    thr = opts.get("threshold")
+    opt = _lib.SeedOpt(float("nan") if thr is None else float(thr), float(opts.get("sigma") or 0.0),
+                       int(opts.get("polarity") or 0), *[-1 if opts.get(k) is None else int(opts[k])
+                                                         for k in ("align", "refractory", "max_iters")])
+    R = opt.refractory if opt.refractory >= 0 else K - 1
+    cap = T // (max(R, 0) + 1) + 1     # events are at least R + 1 apart
+    mu = np.zeros((max(K, 0), max(N, 0)), order="F")
+    sigma, lp, counts = np.zeros(1), np.zeros(max(N, 0)), np.zeros(max(N, 0), dtype=np.int64)
+    ne, iters = np.zeros(1, dtype=np.int64), np.zeros(1, dtype=np.int64)
+    times, labels = np.zeros(cap, dtype=np.int64), np.zeros(cap, dtype=np.int16)
+    out = _lib.SeedOut(*[a.ctypes.data for a in (mu, sigma, lp, counts, ne, iters, times, labels)], cap)
+    check(call(C.byref(opt), C.byref(out)))
+    E = int(ne[0])
+    times, labels = times[:E].copy(), labels[:E].copy()
+    info = {"n_events": E, "iters": int(iters[0]), "times": times, "raw_labels": labels,
+            "raw": {"mu": mu, "lp": lp, "counts": counts}}
+    kept = np.nonzero(counts > 0)[0]
+    info["kept"] = kept
+    info["counts"] = counts[kept].copy()
+    renum = np.full(max(N, 1), -1, dtype=np.int16)
+    renum[kept] = np.arange(len(kept), dtype=np.int16)
+    info["labels"] = renum[labels] if E else labels
+    if len(kept) == 0:
+        return StateMatrix.null(), np.zeros((K, 0), order="F"), float(sigma[0]), info
+    sm = StateMatrix.create(len(kept), K, lp[kept].copy(), resolve_overlaps)
+    return sm, np.asfortranarray(mu[:, kept]), float(sigma[0]), info
+
+
+def seed_templates(X, N=3, K=60, resolve_overlaps=False, **opts):
+    """Templates from the recording alone (hmmsort_seed_templates; an extension, INTEGRATION.md "Template seed"):
+    samples above `threshold` noise scales that are the extremum of their +-`refractory` window are events, the
+    K - 1 samples around each (extremum at snippet index `align`) are clustered into N groups by Lloyd iterations
+    started at amplitude quantiles.  Deterministic; detection and clustering run on the device.
+
+    Options (defaults): threshold (4.0), sigma (0: the robust estimate median|X| / 0.6745), polarity (0: |X|; -1
+    troughs, +1 peaks), align ((K-1)//3), refractory (K-1), max_iters (20).  X: float64 or int16 samples.
+
+    Returns (StateMatrix, mu, sigma, info).  Empty clusters are dropped, so the model may hold fewer than N
+    templates; entry log-probabilities are log(count / T).  No event at all gives StateMatrix.null() and a K x 0 mu.
+    info: "counts", "times" (1-based event samples), "labels" (column of mu per event), "iters", "n_events", "kept"
+    (which of the N clusters survived) and "raw" (mu, lp, counts of all N clusters, as the C ABI returns them)."""
+    raw = isinstance(X, np.ndarray) and X.dtype == np.int16 and X.ndim == 1
+    X = np.ascontiguousarray(X) if raw else _signal(X)
+    st = _lib.SAMPLES_I16 if raw else _lib.SAMPLES_F64
+    return _seed_run(lambda opt, out: lib().hmmsort_seed_templates(ptr(X), st, len(X), int(N), int(K), opt, out),
+                     len(X), N, K, resolve_overlaps, opts)
+
+
 def train_model(X, *args, callback=None, verbose=0, p0=None, rng=None, postprocess="reference",
-                method="baum-welch"):
+                method="baum-welch", init="random", seed_options=None):
     """The three `train_model` methods of baumwelch.jl:
 
       train_model(X, state_matrix, mu0, sigma0)                  one EM step         :362-370
@@ -340,9 +398,18 @@ def train_model(X, *args, callback=None, verbose=0, p0=None, rng=None, postproce
     `method="viterbi"` (an extension; the default "baum-welch" is the reference's loop) makes every step a step of
     Viterbi training (viterbi_step): the loop, the callbacks and the stage between the rounds are the same.  It
     refines a model and does not find one, so the random-start form refuses it.
+
+    `init` chooses the start of the third form.  "random" (default) is the reference's: N random templates with
+    p0 = 2^(-3K/2).  "detect" (an extension) seeds with seed_templates(X, N, K, resolve_overlaps, **seed_options)
+    -- threshold crossings clustered on the device, sigma from the median absolute sample, entry probabilities
+    from the cluster sizes -- and runs the same loop from there; clusters that stay empty are dropped, so the loop
+    may start with fewer than N templates, and a recording without a single event returns the null model.  With a
+    seed there is a model to refine, so "detect" is allowed with either method; p0 and rng are not used.
     """
     if method not in ("baum-welch", "viterbi"):
         raise ValueError("train_model: method must be \"baum-welch\" or \"viterbi\", got %r" % (method,))
+    if init not in ("random", "detect"):
+        raise ValueError("train_model: init must be \"random\" or \"detect\", got %r" % (init,))
     hard = method == "viterbi"
     X = _signal(X)
     if len(args) >= 1 and isinstance(args[0], StateMatrix):
@@ -374,6 +441,17 @@ def train_model(X, *args, callback=None, verbose=0, p0=None, rng=None, postproce
         finally:
             em.close()
         return state_matrix, mu, sigma
+    if init == "detect":
+        N = int(args[0]) if len(args) > 0 else 3
+        K = int(args[1]) if len(args) > 1 else 60
+        resolve_overlaps = bool(args[2]) if len(args) > 2 else False
+        nsteps = int(args[3]) if len(args) > 3 else 8
+        cb = args[4] if len(args) > 4 else callback
+        state_matrix, mu, sigma, _info = seed_templates(X, N, K, resolve_overlaps, **(seed_options or {}))
+        if state_matrix.N == 0:
+            return state_matrix, mu, sigma          # no event above threshold: the null model
+        return train_model(X, state_matrix, mu, sigma, nsteps, cb, verbose=verbose, postprocess=postprocess,
+                           method=method)
     # random initialisation, baumwelch.jl:311-322
     if hard:
         raise ValueError("train_model: method=\"viterbi\" needs a model to refine.  From the random start "

@@ -369,5 +369,17 @@ int plan_path_finish(hmmsort_plan *p, const double *d_stats, double *d_out, int6
 int dev_stats_sum(const double *d_parts, int64_t nparts, int64_t len, double *d_out, hipStream_t st);
 // acc[i] = w * acc[i] + new[i] in two rounded steps for i < len - plain_tail, acc[i] += new[i] for the rest
 int dev_stats_blend(double *d_acc, double w, const double *d_new, int64_t len, int64_t plain_tail, hipStream_t st);
+// template seed (seed_templates.hip): the options with the defaults filled in, checked against the limits of
+// include/hmmsort.h before any GPU work; then the seed of the resident signal d_y into the caller's host arrays
+// (synchronises st)
+struct SeedParams {
+    double threshold, sigma;
+    int polarity;
+    int64_t align, refractory, max_iters;
+};
+int seed_resolve(int64_t T, int64_t N, int64_t K, const hmmsort_seed_opt *opt, const hmmsort_seed_out *out,
+                 SeedParams *p);
+int dev_seed_templates(const double *d_y, int64_t T, int64_t N, int64_t K, const SeedParams &p, hmmsort_seed_out *out,
+                       hipStream_t st);
 void host_slots_trim(size_t keep);   // idle plans of the host-buffer entry points: keep the newest `keep`
 }  // namespace hmmsort

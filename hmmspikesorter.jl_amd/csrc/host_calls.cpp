@@ -1236,4 +1236,38 @@ int hmmsort_posteriors(const double *y, int64_t T, const int16_t *states, int64_
         });
 }
 
+// Template seed (seed_templates.hip).  No plan and no cached slot: the signal goes up once, int16 samples as they are.
+int hmmsort_seed_templates_device(const double *d_y, int64_t T, int64_t N, int64_t K, const hmmsort_seed_opt *opt,
+                                  hmmsort_seed_out *out, void *stream)
+{
+    HS_CHECK(d_y, HMMSORT_EINVAL, "seed_templates_device: null signal");
+    SeedParams p;
+    int rc = seed_resolve(T, N, K, opt, out, &p);
+    if (rc) return rc;
+    if ((rc = need_device())) return rc;
+    return dev_seed_templates(d_y, T, N, K, p, out, (hipStream_t)stream);
+}
+
+int hmmsort_seed_templates(const void *y, int sample_type, int64_t T, int64_t N, int64_t K,
+                           const hmmsort_seed_opt *opt, hmmsort_seed_out *out)
+{
+    HS_CHECK(y, HMMSORT_EINVAL, "seed_templates: null signal");
+    HS_CHECK(sample_type == HMMSORT_SAMPLES_F64 || sample_type == HMMSORT_SAMPLES_I16, HMMSORT_EINVAL,
+             "seed_templates: samples must be HMMSORT_SAMPLES_F64 or HMMSORT_SAMPLES_I16");
+    SeedParams p;
+    int rc = seed_resolve(T, N, K, opt, out, &p);
+    if (rc) return rc;
+    if ((rc = need_device())) return rc;
+    DevBuf draw, dy;
+    if ((rc = dy.alloc((size_t)T * sizeof(double)))) return rc;
+    if (sample_type == HMMSORT_SAMPLES_I16) {
+        if ((rc = draw.alloc((size_t)T * sizeof(int16_t)))) return rc;
+        HS_HIP(hipMemcpy(draw.p, y, (size_t)T * sizeof(int16_t), hipMemcpyHostToDevice));
+        if ((rc = dev_widen(draw.p, sample_type, T, 1, dy.as<double>(), nullptr))) return rc;
+    } else {
+        HS_HIP(hipMemcpy(dy.p, y, (size_t)T * sizeof(double), hipMemcpyHostToDevice));
+    }
+    return dev_seed_templates(dy.as<double>(), T, N, K, p, out, nullptr);
+}
+
 }  // extern "C"

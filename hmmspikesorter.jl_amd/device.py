@@ -31,6 +31,22 @@ def stats_blend(d_acc, w, d_new, length, plain_tail=3, stream=0):
                                     C.c_void_p(stream)))
 
 
+def seed_templates(d_y, N=3, K=60, resolve_overlaps=False, stream=None, **opts):
+    """api.seed_templates for a float64 signal that is already resident (hmmsort_seed_templates_device): same options
+    and the same (StateMatrix, mu, sigma, info), nothing but the results crosses to the host.  `stream`: a raw HIP
+    stream handle, default torch's current one; the call synchronises it."""
+    from .api import _seed_run
+    if stream is None:
+        import torch
+        stream = torch.cuda.current_stream().cuda_stream
+    if not (d_y.is_floating_point() and d_y.element_size() == 8 and d_y.is_contiguous() and d_y.dim() == 1):
+        raise TypeError("seed_templates: d_y must be a contiguous one-dimensional float64 device tensor")
+    T = int(d_y.numel())
+    return _seed_run(lambda opt, out: lib().hmmsort_seed_templates_device(_dptr(d_y), T, int(N), int(K), opt, out,
+                                                                         C.c_void_p(stream)),
+                     T, N, K, resolve_overlaps, opts)
+
+
 class Plan:
     """One recording channel of length T with a fixed model shape."""
 

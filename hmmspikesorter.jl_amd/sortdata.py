@@ -145,20 +145,77 @@ def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_temp
     return out
 
 
+def _entry_lp(sm):
+    """entry log-probability per template in template order, -Inf where the transition has left the list"""
+    lpn = np.full(sm.N, -np.inf)
+    lp, lidx = get_lp(sm)
+    found = lidx > 0
+    lpn[lidx[found] - 1] = lp[found]
+    return lpn
+
+
+def merge_and_prune(sm, mu, sigma):
+    """The reference's stage between the two rounds of steps (condense_templates, remove_sparse, remove_small,
+    baumwelch.jl:340-349) for either kind of model.  The reference runs it on the model it trains, which has no
+    overlaps; an overlap model goes through it as the no-overlap model of the same templates and entry
+    probabilities and is rebuilt from what is left."""
+    from .postprocess import reference_postprocess
+    if not sm.resolve_overlaps:
+        return reference_postprocess(sm, mu, sigma)
+    ring, mu = reference_postprocess(api.StateMatrix.create(sm.N, sm.K, _entry_lp(sm), False), mu, sigma)
+    if ring.N == 0:
+        return ring, mu
+    return api.StateMatrix.create(ring.N, sm.K, _entry_lp(ring), True), mu
+
+
+def learn_templates(data, N=3, K=60, nsteps=4, method="viterbi", resolve_overlaps=True, postprocess=merge_and_prune,
+                    seed_options=None):
+    """The learning stage in front of sort_data (an extension: the reference takes its templates from a file an
+    earlier stage wrote): seed N templates of K states from the channel's threshold crossings (api.seed_templates)
+    and train them with api.train_model(..., init="detect"); `postprocess` is train_model's (default: the reference's
+    merge-and-prune stage, see merge_and_prune).  Returns the dictionary sort_data takes: "spikeForms" (K, 1, n),
+    "cinv" [1 / sigma^2] and "p" (entry probability per template), n <= N being the templates that are left with a
+    finite entry transition."""
+    data = np.asarray(data)
+    if data.ndim == 2:
+        data = data[:, 0]
+    X = np.ascontiguousarray(data, dtype=np.float64)
+    sm, mu, sigma = api.train_model(X, int(N), int(K), bool(resolve_overlaps), int(nsteps), method=method,
+                                    init="detect", postprocess=postprocess, seed_options=seed_options)
+    p = np.exp(_entry_lp(sm)) if sm.N > 0 else np.zeros(0)
+    keep = np.nonzero(p > 0)[0]
+    mu = np.asarray(mu, dtype=np.float64).reshape(int(K), -1)
+    return {"spikeForms": np.ascontiguousarray(mu[:, keep][:, None, :]), "cinv": np.array([1.0 / (sigma * sigma)]),
+            "p": p[keep]}
+
+
 def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser(description="HMM spike sorting of one channel (hmmsort.jl CLI)")
-    ap.add_argument("--sourcefile", required=True, help=".npz/.mat with spikeForms, cinv, p")
+    ap.add_argument("--sourcefile", help=".npz/.mat with spikeForms, cinv, p (not needed with --learn)")
+    ap.add_argument("--learn", type=int, default=0, metavar="N",
+                    help="learn up to N templates from the data itself instead of reading --sourcefile")
+    ap.add_argument("--nstates", type=int, default=60, help="template length for --learn")
     ap.add_argument("--datafile", required=True, help=".npz/.mat with the channel's samples")
     ap.add_argument("--dataname", default="data")
     ap.add_argument("--outfile", default="hmmsort.mat")
     ap.add_argument("--max_templates", type=int, default=4)
     a = ap.parse_args(argv)
-    t = load_templates(a.sourcefile)
+    data = None
+    if a.learn > 0:
+        data = load_data(a.datafile, a.dataname)
+        d = learn_templates(data, a.learn, a.nstates)
+        t = (d["spikeForms"], d["cinv"], d["p"]) if len(d["p"]) else None
+    elif a.sourcefile is None:
+        ap.error("--sourcefile is required without --learn")
+    else:
+        t = load_templates(a.sourcefile)
     if t is None:
         print("No spike forms found. Bailing...")
         return 0
-    out = sort_data(*t, load_data(a.datafile, a.dataname), a.outfile, max_templates=a.max_templates)
+    if data is None:
+        data = load_data(a.datafile, a.dataname)
+    out = sort_data(*t, data, a.outfile, max_templates=a.max_templates)
     print("Done! Results saved to %s" % a.outfile if out else "Too many templates. Bailing out...")
     return 0
 

@@ -587,6 +587,54 @@ int hmmsort_samples_to_f64(const void *d_in, int sample_type, int64_t T, int64_t
 int hmmsort_chunk_stitch(const int16_t *d_x, int64_t k, int lead, int trail, int16_t *d_dst, int64_t *d_lk,
                          void *stream);
 
+/* Template seed: approximate templates from the recording alone (an extension; the reference starts training from
+ * random templates, baumwelch.jl:311-322, and takes sorting templates from a file).  Deterministic, 0-based below:
+ *   D = K - 1 snippet samples (row 0 of mu is the silent row and stays 0).
+ *   noise scale  sigma_n = (order statistic (T-1)/2 of |y|, exact) / 0.6744897501960817, or opt->sigma when > 0.
+ *   v[t] = -y[t], |y[t]| or y[t] for polarity -1, 0, +1.  t is an event iff v[t] > threshold * sigma_n, v[u] < v[t]
+ *   for u in [max(0, t-R), t), v[u] <= v[t] for u in (t, min(T-1, t+R)] (a plateau goes to its earliest sample) and
+ *   the snippet y[t-align .. t-align+D-1] lies inside the recording.  Events are at least R + 1 apart.
+ *   Centres start at the snippets of rank min(E-1, ((2i+1) E) / (2N)) in the order by (v[t], t); then Lloyd
+ *   iterations: squared distance accumulated in ascending sample order (multiply and add rounded separately), label
+ *   = arg min with ties to the lower i, stop when no label changed or after max_iters assignments; a non-empty
+ *   cluster's centre is the mean of its snippets, an empty one keeps its centre.  The sums use no floating-point
+ *   atomics and a fixed order: the same input gives the same bits.
+ * Outputs (host pointers): mu K x N column-major (rows 1..D = centre i), sigma = sigma_n, counts[i], lp[i] =
+ * log(counts[i] / T) (-Inf for an empty cluster), n_events, iters = assignments made, and the first min(n_events, cap)
+ * event times (1-based, ascending) and labels (0-based) -- the cap protocol of hmmsort_extract_spiketimes.  No event at
+ * all is not an error: mu and counts are zero, lp is -Inf.
+ * Limits: 2 <= K <= HMMSORT_SEED_MAX_K, 1 <= N <= HMMSORT_SEED_MAX_N, 1 <= refractory <= HMMSORT_SEED_MAX_R,
+ * align < K - 1, K <= T <= 2^40, polarity in -1..1; anything else is HMMSORT_EINVAL before any GPU work.  No plan is
+ * involved.  The host form uploads the signal once (int16 samples as they are, widened on the device); sample_type is
+ * HMMSORT_SAMPLES_F64 or HMMSORT_SAMPLES_I16.  The device form takes a resident fp64 signal and synchronises the
+ * stream. */
+#define HMMSORT_SEED_MAX_K 1025
+#define HMMSORT_SEED_MAX_N 16
+#define HMMSORT_SEED_MAX_R 1024
+typedef struct hmmsort_seed_opt {
+    double threshold;   /* in units of sigma_n; NaN: 4.0 */
+    double sigma;       /* > 0: used as sigma_n; <= 0: the robust estimate */
+    int polarity;       /* -1, 0, +1 */
+    int64_t align;      /* snippet index of the extremum; < 0: (K - 1) / 3 */
+    int64_t refractory; /* R; < 0: K - 1 */
+    int64_t max_iters;  /* <= 0: 20 */
+} hmmsort_seed_opt;
+typedef struct hmmsort_seed_out {
+    double *mu;         /* K * N */
+    double *sigma;      /* 1 */
+    double *lp;         /* N */
+    int64_t *counts;    /* N */
+    int64_t *n_events;  /* 1, may be NULL */
+    int64_t *iters;     /* 1, may be NULL */
+    int64_t *times;     /* cap, may be NULL */
+    int16_t *labels;    /* cap, may be NULL */
+    int64_t cap;
+} hmmsort_seed_out;
+int hmmsort_seed_templates(const void *y, int sample_type, int64_t T, int64_t N, int64_t K,
+                           const hmmsort_seed_opt *opt /* NULL: defaults */, hmmsort_seed_out *out);
+int hmmsort_seed_templates_device(const double *d_y, int64_t T, int64_t N, int64_t K, const hmmsort_seed_opt *opt,
+                                  hmmsort_seed_out *out, void *stream);
+
 /* Per-kernel timing of the ring engine with HIP events recorded on the caller's stream (used by
  * bench.py for the roofline line).  hmmsort_plan_profile(plan, 1) switches bracketing on;
  * hmmsort_plan_profile_read synchronises the stream and returns, per kernel name, the total

@@ -277,6 +277,66 @@ function reconstruct_tracked(x::Array{Int16,1}, lA::StateMatrix, first::Vector{I
     Y2
 end
 
+# struct hmmsort_seed_opt / hmmsort_seed_out (include/hmmsort.h)
+struct CSeedOpt
+    threshold::Float64; sigma::Float64; polarity::Cint; align::Int64; refractory::Int64; max_iters::Int64
+end
+struct CSeedOut
+    mu::Ptr{Float64}; sigma::Ptr{Float64}; lp::Ptr{Float64}; counts::Ptr{Int64}; n_events::Ptr{Int64}
+    iters::Ptr{Int64}; times::Ptr{Int64}; labels::Ptr{Int16}; cap::Int64
+end
+
+function _seed_finish(N, K, resolve_overlaps, μ, σ, lp, counts, ne, iters, times, labels)
+    E = ne[1]; kept = findall(counts .> 0)
+    info = (counts=counts[kept], times=times[1:E], labels=labels[1:E] .+ Int16(1), iters=iters[1], kept=kept)
+    isempty(kept) && return StateMatrix(), zeros(Float64, K, 0), σ[1], info
+    StateMatrix(length(kept), K, lp[kept], resolve_overlaps), μ[:, kept], σ[1], info
+end
+
+"""
+    seed_templates(X, N=3, K=60, resolve_overlaps=false; threshold=NaN, sigma=0.0, polarity=0, align=-1,
+                   refractory=-1, max_iters=0) -> (state_matrix, μ, σ, info)
+
+Templates from the recording alone (`hmmsort_seed_templates`; an extension with no counterpart in the reference, which
+starts `train_model` from random templates and takes sorting templates from a file; INTEGRATION.md "Template seed"):
+threshold crossings that are the extremum of their ±refractory window, clustered into `N` groups on the device.  The
+keyword defaults ask for the library's (4.0 noise scales, the robust noise estimate, |X|, (K-1)÷3, K-1, 20).  Empty
+clusters are dropped; `info.labels` are 1-based cluster numbers before that, `info.kept` the clusters that survived.
+`seed_templates_device` takes a resident signal.
+"""
+function seed_templates(X::Vector{T}, N::Integer=3, K::Integer=60, resolve_overlaps::Bool=false; threshold=NaN,
+                        sigma=0.0, polarity=0, align=-1, refractory=-1, max_iters=0) where T <: Union{Float64,Int16}
+    n = length(X); cap = n ÷ ((refractory >= 0 ? refractory : K - 1) + 1) + 1
+    μ = zeros(Float64, K, N); σ = zeros(Float64, 1); lp = zeros(Float64, N); counts = zeros(Int64, N)
+    ne = zeros(Int64, 1); iters = zeros(Int64, 1); times = zeros(Int64, cap); labels = zeros(Int16, cap)
+    GC.@preserve X μ σ lp counts ne iters times labels begin
+        opt = Ref(CSeedOpt(threshold, sigma, polarity, align, refractory, max_iters))
+        out = Ref(CSeedOut(pointer(μ), pointer(σ), pointer(lp), pointer(counts), pointer(ne), pointer(iters),
+                           pointer(times), pointer(labels), cap))
+        check(ccall((:hmmsort_seed_templates, lib), Cint,
+            (Ptr{Cvoid}, Cint, Int64, Int64, Int64, Ref{CSeedOpt}, Ref{CSeedOut}),
+            X, T === Int16 ? HMMSORT_SAMPLES_I16 : HMMSORT_SAMPLES_F64, n, N, K, opt, out))
+    end
+    _seed_finish(N, K, resolve_overlaps, μ, σ, lp, counts, ne, iters, times, labels)
+end
+
+"`seed_templates` of a float64 signal of `n` samples in device memory (`hmmsort_seed_templates_device`); synchronises `stream`"
+function seed_templates_device(d_y::Ptr{Float64}, n::Integer, N::Integer=3, K::Integer=60,
+                               resolve_overlaps::Bool=false; stream::Ptr{Cvoid}=C_NULL, threshold=NaN, sigma=0.0,
+                               polarity=0, align=-1, refractory=-1, max_iters=0)
+    cap = n ÷ ((refractory >= 0 ? refractory : K - 1) + 1) + 1
+    μ = zeros(Float64, K, N); σ = zeros(Float64, 1); lp = zeros(Float64, N); counts = zeros(Int64, N)
+    ne = zeros(Int64, 1); iters = zeros(Int64, 1); times = zeros(Int64, cap); labels = zeros(Int16, cap)
+    GC.@preserve μ σ lp counts ne iters times labels begin
+        opt = Ref(CSeedOpt(threshold, sigma, polarity, align, refractory, max_iters))
+        out = Ref(CSeedOut(pointer(μ), pointer(σ), pointer(lp), pointer(counts), pointer(ne), pointer(iters),
+                           pointer(times), pointer(labels), cap))
+        check(ccall((:hmmsort_seed_templates_device, lib), Cint,
+            (Ptr{Float64}, Int64, Int64, Int64, Ref{CSeedOpt}, Ref{CSeedOut}, Ptr{Cvoid}), d_y, n, N, K, opt, out, stream))
+    end
+    _seed_finish(N, K, resolve_overlaps, μ, σ, lp, counts, ne, iters, times, labels)
+end
+
 function reconstruct_signal(x::Array{T,1}, lA::StateMatrix, μ::Array{Float64,2}, σ::Float64) where T <: Integer
     xs = T === Int16 ? x : Int16.(x)
     Y2 = zeros(Float64, length(xs))
