@@ -318,6 +318,31 @@ constexpr int bwd_yring(int ft) { return ft <= 2 ? 256 : 512; }
 #ifndef HS_BWD_W4
 #define HS_BWD_W4 2   // waves per SIMD asked of the compiler for up to 4 rings (3, with a one-deep input pipeline and chains of 3 264 samples: 18 spilled registers, 0.382 against 0.369 ms)
 #endif
+// Round 9: the three parts of the interior form of the fused sweep, each 1 = on, 0 = the parent's form (A/B builds)
+#ifndef HS_BWD_FEED
+#define HS_BWD_FEED 1    // FT = 1: operand addresses of the product = lane constant + wave-uniform offset, rings with a mirrored front
+#endif
+#ifndef HS_BWD_ILOAD
+#define HS_BWD_ILOAD 1   // interior super-steps load through one scalar base per plane and one 32-bit lane offset, no clamps
+#endif
+#ifndef HS_BWD_IPRED
+#define HS_BWD_IPRED 1   // interior super-steps carry no ownership predicates
+#endif
+// FT = 1 with HS_BWD_FEED: each ring of the statistics is preceded by a copy of its last entries (as far back as a
+// lane's operand reaches behind tau), so that no operand address wraps: y ring | spare, rho rows | spare row.
+constexpr int bwd_np(int n) { return n <= 4 ? 4 : 8; }                           // ring columns per delayed copy
+constexpr int bwd_d0(int n) { return 16 * (16 / bwd_np(n) - 1); }                  // delay of the last copy, 16 (NS - 1)
+constexpr int bwd_ymir(int n) { return bwd_d0(n) + 20; }   // largest lag offset + 15 rows + the pair's second product + 1
+constexpr int bwd_rmir(int n) { return bwd_d0(n); }        // the last delayed copy (a multiple of 16: the padding stays aligned)
+constexpr bool bwd_feed(int ft) { return HS_BWD_FEED && ft == 1; }
+constexpr int bwd_stat_doubles(int n, int ft)   // LDS of the fused statistics, in doubles
+{
+    const int np = bwd_np(n), rpad = n <= 4 ? 1 : 2, ym = bwd_yring(ft);
+    if (ft <= 0) return 0;
+    if (!bwd_feed(ft)) return ym + (128 + 8 * rpad) * np;
+    const int re = 128 + bwd_rmir(n);
+    return (ym + bwd_ymir(n) + 2) + (re + rpad * (re >> 4) + 1) * np;
+}
 // GS (posterior calls, wave_post.hip): the sweep also stores gamma_t(silent) of every owned sample; the
 // default instantiations (GS = false) compile to what they were.
 template <int N, bool UC, int FT = 0, bool GS = false>
@@ -339,7 +364,7 @@ __global__ __launch_bounds__(64, N <= 4 ? HS_BWD_W4 : 1) void kw_bwd(WaveGeom g,
     static_assert(!GS || !FUSE, "the silent posterior is stored by the unfused sweep");
     static_assert(!FUSE || (N >= 3 && N <= 8), "the fused statistics are written for delayed copies of 3-8 rings");
     static_assert(!FUSE || N > 4 || FT == 1, "3-4 rings: one tile of 64 lags");
-    constexpr int NPc = N <= 4 ? 4 : 8, NSc = 16 / NPc, LPT = 16 * NSc;   // ring columns per copy, copies, lags per tile
+    constexpr int NPc = bwd_np(N), NSc = 16 / NPc, LPT = 16 * NSc;   // ring columns per copy, copies, lags per tile
     constexpr int RPAD = NPc == 4 ? 1 : 2;                   // padding rows per 16 rows of the rho ring (bank spread of the copies)
     constexpr int RGROWS = 128 + 8 * RPAD;
     constexpr int YM = bwd_yring(FT);                        // y ring: largest lag + two step widths + slack
@@ -372,19 +397,65 @@ __global__ __launch_bounds__(64, N <= 4 ? HS_BWD_W4 : 1) void kw_bwd(WaveGeom g,
     for (int i = lane; i < N * (RB + 1); i += 64) DLv[i] = 1.0;
     for (int i = lane; i < RB + 1; i += 64) DLs[i] = 0.0;
     // fused statistics: y ring (YM steps) | rho ring (128 steps x NPc ring columns, RPAD padding rows per 16)
-    double *YY = DLs + (RB + 1), *RG = YY + YM;
+    double *YY = DLs + (RB + 1), *RG = YY + (bwd_feed(FT) ? YM + bwd_ymir(N) + 2 : YM);
     const int lk = lane >> 4, lj = lane & 15, gla = lj % NPc, glsft = lj / NPc;
     wg_d4 cacc[NACC > 0 ? NACC : 1];
 #pragma unroll
     for (int q = 0; q < NACC; q++) cacc[q] = wg_d4{0.0, 0.0, 0.0, 0.0};
     int gtau = -1;                                       // next tau of the product, -1: no owned step yet
     auto rgrow = [&](int r) { return (r + RPAD * (r >> 4)) * NPc; };
+    // FEED: entry i of the y ring lives at YY[YMIR + i] and, for the last YMIR entries, also at YY[i - (YM - YMIR)]; row r of
+    // the rho ring at row RMIR + r and, for the last RMIR rows, also at row r - (128 - RMIR).  A lane reads entry
+    // (tau & mask) + c with a constant c in [-mirror, 4): never a wrap.  The padding of the rho rows separates, because
+    // tau is a multiple of 4 and c = lk (< 4) mod 16: no carry into the 16s, rgrow(tau + c + RMIR) = rgrow(tau) + rgrow(c + RMIR).
+    constexpr bool FEED = bwd_feed(FT);
+    constexpr int YMIR = bwd_ymir(N), RMIR = bwd_rmir(N), RE = 128 + RMIR;
+    const double *RGl = RG + (rgrow(lk - 16 * glsft + RMIR) + gla);   // lane part of the rho operand's address
+    const double *YYl = YY + (lk - lj + (YMIR - 16 * (NSc - 1) - 4));   // of the y operand's: YMIR + (lk - 16 (NS - 1) - lj) - 4
+    // stores of step sigma (every lane; lanes outside the mirrored span write the spare slot / row)
+    auto ystore = [&](int sigma, double v) {
+        const int i = sigma & (YM - 1);
+        if constexpr (FEED) {
+            YY[YMIR + i] = v;
+            YY[i >= YM - YMIR ? i - (YM - YMIR) : YM + YMIR] = v;
+        } else YY[i] = v;
+    };
+    auto rstore = [&](int sigma, const double (&v)[NPc]) {
+        const int r = sigma & 127;
+        if constexpr (FEED) {
+            double *p0 = RG + rgrow(RMIR + r), *p1 = RG + rgrow(r >= 128 - RMIR ? r - (128 - RMIR) : RE);
+#pragma unroll
+            for (int a = 0; a < NPc; a++) p0[a] = v[a];
+#pragma unroll
+            for (int a = 0; a < NPc; a++) p1[a] = v[a];
+        } else {
+            double *p0 = RG + rgrow(r);
+#pragma unroll
+            for (int a = 0; a < NPc; a++) p0[a] = v[a];
+        }
+    };
     // products for tau = gtau, gtau + 4, ... while tau + 4 <= upto.  FT = 1: two at a time on two accumulator
     // tiles (independent MFMA chains); FT > 1: the FT tiles of one tau are independent of each other.  Reading the
     // operands of a whole super-step first and issuing 16 MFMAs back to back was slower (0.427 vs 0.400 ms: 64
     // more live VGPRs).
     auto gmfma = [&](int upto) {
-        if constexpr (FT <= 1) {
+        if constexpr (FEED) {
+            // the same operands in the same order; the wave-uniform part of every address is scalar arithmetic
+            for (; gtau + 8 <= upto; gtau += 8) {
+                const int s0 = rgrow(gtau & 127), s1 = rgrow((gtau + 4) & 127), sy = (gtau + 4) & (YM - 1);
+                const double b0 = RGl[s0], b1 = RGl[s1];
+                const double a0 = YYl[sy], a1 = YYl[sy + 4];
+                cacc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, cacc[0], 0, 0, 0);
+                cacc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, cacc[1], 0, 0, 0);
+            }
+            if (gtau + 4 <= upto) {
+                const int s0 = rgrow(gtau & 127), sy = (gtau + 4) & (YM - 1);
+                const double b0 = RGl[s0];
+                const double a0 = YYl[sy];
+                cacc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, cacc[0], 0, 0, 0);
+                gtau += 4;
+            }
+        } else if constexpr (FT <= 1) {
             constexpr int D0 = 16 * (NSc - 1);
             for (; gtau + 8 <= upto; gtau += 8) {
                 const int r0 = (gtau + lk - 16 * glsft) & 127, r1 = (gtau + 4 + lk - 16 * glsft) & 127;
@@ -413,7 +484,8 @@ __global__ __launch_bounds__(64, N <= 4 ? HS_BWD_W4 : 1) void kw_bwd(WaveGeom g,
         }
     };
     if (FUSE) {
-        for (int i = lane; i < YM + RGROWS * NPc; i += 64) YY[i] = 0.0;
+        static_assert(!FUSE || FEED || bwd_stat_doubles(N, FT) == YM + RGROWS * NPc, "the launch sizes the rings with bwd_stat_doubles");
+        for (int i = lane; i < bwd_stat_doubles(N, FT); i += 64) YY[i] = 0.0;
     }
     {
         const WaveConst &Kg = cst[ch];
@@ -439,7 +511,28 @@ __global__ __launch_bounds__(64, N <= 4 ? HS_BWD_W4 : 1) void kw_bwd(WaveGeom g,
         if (done < n_warm) return done == 0 ? w0 : W;
         return n_total - done < W ? n_total - done : W;
     };
-    auto load = [&](BIn<N> &d, int done) {
+    // Interior super-steps (MODE 4 of run): full steps whose every live lane has t and t + 1 inside the chain's own
+    // samples [tc, tend) and inside the shard, away from the truncated rings at the end of the recording -- every
+    // ownership predicate is true and no load clamp fires.  The range [ki0, ki1) is fixed below, once per chain;
+    // the input pipeline looks D steps past it, which the loads clamp to its last step (done = imax, wave-uniform).
+    int imax = 0;
+    const unsigned ivo = (unsigned)(W - 1 - (lane < W ? lane : 0)) & 63u;   // lane j reads element W-1-j above the step's lowest sample
+    auto load = [&](BIn<N> &d, int done, auto mode_tag) {
+        if constexpr (decltype(mode_tag)::value == 4 && HS_BWD_ILOAD) {
+            const int dn = done < imax ? done : imax;
+            const int64_t t0 = te - 1 - dn - W;              // t of lane W-1; t + 1 <= tend - 1 and t >= tc for every lane
+            d.y1 = (yc + t0 + 1)[ivo];
+            d.y0 = (yc + t0)[ivo];
+            d.w2 = (W2c + t0 + 1)[ivo];
+            d.fref = (FRc + t0 + 1)[ivo];
+            d.la0 = (FAc + t0)[ivo];
+#pragma unroll
+            for (int a = 0; a < N; a++) {
+                d.R[a] = (Rc + (int64_t)a * T + t0 + 1)[ivo];
+                d.fv[a] = (FVc + (int64_t)a * T + t0 + 1)[ivo];
+            }
+            return;
+        }
         const int nact = done < n_total ? width(done) : 0;
         const int li = lane < nact ? lane : 0;
         int64_t tb = te - 2 - done;                      // time of lane 0; lane j handles tb - j
@@ -464,12 +557,13 @@ __global__ __launch_bounds__(64, N <= 4 ? HS_BWD_W4 : 1) void kw_bwd(WaveGeom g,
     // recording (conditional stores).  Modes 0 and 1 keep global accesses straight-line (exact vmcnt).
     auto run = [&](const BIn<N> &d, int done, auto mode_tag) {
         constexpr int MODE = decltype(mode_tag)::value;
-        const int nact = width(done);
+        constexpr bool IPRED = MODE == 4 && HS_BWD_IPRED;
+        const int nact = MODE == 4 ? W : width(done);
         const bool live = lane < nact;
         const int64_t tb = te - 2 - done;                // time of lane 0
         const int64_t t = tb - lane;                     // step index i = done + 1 + lane, t = te-1-i
-        const bool owned = MODE == 1 || MODE == 3 || (MODE == 2 && done >= n_warm);   // wave-uniform
-        if (FUSE) YY[(done + 1 + lane) & (YM - 1)] = d.y1;    // y of this lane's onset time t+1 (idle lanes: steps still to come)
+        const bool owned = MODE == 1 || MODE == 3 || MODE == 4 || (MODE == 2 && done >= n_warm);   // wave-uniform
+        if (FUSE) ystore(done + 1 + lane, d.y1);          // y of this lane's onset time t+1 (idle lanes: steps still to come)
         int ws = (done + 1) % RB + lane;                 // (done+1) % RB is wave-uniform
         ws = ws >= RB ? ws - RB : ws;
         int rs = ws - L;
@@ -549,31 +643,35 @@ __global__ __launch_bounds__(64, N <= 4 ? HS_BWD_W4 : 1) void kw_bwd(WaveGeom g,
             }
         }
         if (owned) {
-            const double la = t >= tc ? d.la0 : la0pre;
+            // MODE 4 with IPRED: every condition below but `live` is true by the choice of the interior range
+            const double la = (IPRED || t >= tc) ? d.la0 : la0pre;
             double gg[2] = {fmin((la + Mt) - z, 700.0), fmin((d.fref + Mt) - z, 700.0)};
             fexp_n<2>(gg);
             const int64_t t1 = t + 1;
-            if (live && t >= tc && t >= g.own_lo && t < g.own_hi) {
+            const bool osil = IPRED ? live : (live && t >= tc && t >= g.own_lo && t < g.own_hi);
+            if (osil) {
                 const double ga = xt * gg[0];                    // gamma_t(silent)
                 s_all += ga;                                     // baumwelch.jl:303 qq
-                if (!g.last || t < T - 1) s_m += ga;             // :257 bb, t = 1..T-1 of the recording
+                if (IPRED || !g.last || t < T - 1) s_m += ga;    // :257 bb, t = 1..T-1 of the recording
                 s_y2 = __builtin_fma(ga, d.y0 * d.y0, s_y2);     // :302 with the new silent mean (= 0)
             }
             if (GS) *(live && t >= tc ? gsil + (int64_t)ch * T + t : trash + 64 * N + lane) = xt * gg[0];
-            const bool own1 = live && t1 >= g.own_lo && t1 < g.own_hi;
-            const bool bulk = !(g.last && t1 > T - L);           // truncated rings: summed per phase in kw_stats_final
+            const bool own1 = IPRED ? live : (live && t1 >= g.own_lo && t1 < g.own_hi);
+            const bool bulk = IPRED || !(g.last && t1 > T - L);  // truncated rings: summed per phase in kw_stats_final
+            double rvv[NPc];
 #pragma unroll
             for (int a = 0; a < N; a++) {
                 const double rv = own1 ? (d.fv[a] * wa[a]) * gg[1] : 0.0;
-                if (MODE != 3) *(live ? rhoc + (int64_t)a * T + t1 : trash + 64 * a + lane) = rv;
+                if (MODE != 3 && MODE != 4) *(live ? rhoc + (int64_t)a * T + t1 : trash + 64 * a + lane) = rv;
                 ra[a] += bulk ? rv : 0.0;
                 s2[a] = __builtin_fma(rv, d.w2, s2[a]);          // sum_k G2(a,k) (baumwelch.jl:302)
-                sx[a] += (own1 && t >= 0) ? wa[a] * gg[0] : 0.0;  // xi'_a(t+1): silent(t) -> (a,1)(t+1), :240
-                if (FUSE) RG[rgrow((done + 1 + lane) & 127) + a] = rv;   // idle lanes: zeros at steps still to come
+                sx[a] += (own1 && (IPRED || t >= 0)) ? wa[a] * gg[0] : 0.0;  // xi'_a(t+1): silent(t) -> (a,1)(t+1), :240
+                if (a < NPc) rvv[a] = rv;
             }
             if (FUSE) {
 #pragma unroll
-                for (int a = N; a < NPc; a++) RG[rgrow((done + 1 + lane) & 127) + a] = 0.0;
+                for (int a = N; a < NPc; a++) rvv[a] = 0.0;
+                rstore(done + 1 + lane, rvv);                    // idle lanes: zeros at steps still to come
                 if (gtau < 0) gtau = (done + 1) & ~3;            // wave-uniform
                 gmfma(done + 1 + nact);
             }
@@ -659,13 +757,13 @@ __global__ __launch_bounds__(64, N <= 4 ? HS_BWD_W4 : 1) void kw_bwd(WaveGeom g,
     auto sweep = [&](int k0, int k1, auto mode_tag) {
         BIn<N> buf[D];
 #pragma unroll
-        for (int i = 0; i < D; i++) load(buf[i], start(k0 + i));
+        for (int i = 0; i < D; i++) load(buf[i], start(k0 + i), mode_tag);
         int k = k0;
         for (; k + D <= k1; k += D) {
 #pragma unroll
             for (int i = 0; i < D; i++) {
                 run(buf[i], start(k + i), mode_tag);
-                load(buf[i], start(k + i + D));
+                load(buf[i], start(k + i + D), mode_tag);
             }
         }
 #pragma unroll
@@ -682,15 +780,40 @@ __global__ __launch_bounds__(64, N <= 4 ? HS_BWD_W4 : 1) void kw_bwd(WaveGeom g,
         // MODE 3 = MODE 1 without the rho stores for the bulk of the chain
         const int km = kwarm + rk < ko1 ? kwarm + rk : ko1;
         if (km > kwarm) sweep(kwarm, km, std::integral_constant<int, 1>());
-        if (ko1 > km) sweep(km, ko1, std::integral_constant<int, 3>());
+        // interior range [ki0, ki1) of [km, ko1), MODE 4: steps with done = start(k) in [dlo, dhi] (k >= km: start(k) =
+        // w0 + (k - 1) W, also for k = 0, where w0 = W).  Lane j has t = te - 2 - done - j: t + 1 < min(own_hi, tend) for
+        // lane 0 is done >= te - min(own_hi, tend); t >= max(own_lo, tc) for lane W-1 is done <= te - 1 - W - max(own_lo, tc),
+        // which also makes the step full; t + 1 <= T - L on the last shard is done >= te - 1 - (T - L).
+        int ki0 = ko1, ki1 = ko1;
+        if constexpr (HS_BWD_ILOAD || HS_BWD_IPRED) {
+            const int64_t ohi = g.own_hi < tend ? g.own_hi : tend, olo = g.own_lo > tc ? g.own_lo : tc;
+            int64_t dlo = te - ohi, dhi = te - 1 - W - olo;
+            if (g.last && dlo < te - 1 - (T - L)) dlo = te - 1 - (T - L);
+            if (dhi >= dlo && dhi >= 0) {   // dlo >= 0: te >= tend; both at most n_total
+                const int x0 = (int)dlo - w0, x1 = (int)dhi - w0;
+                const int k0i = x0 > 0 ? 1 + (x0 + W - 1) / W : (x0 > -W ? 1 : 0);       // first k with start(k) >= dlo
+                const int k1i = x1 >= 0 ? 2 + x1 / W : (x1 >= -W ? 1 : 0);               // one past the last k with start(k) <= dhi
+                ki0 = k0i > km ? k0i : km;
+                ki1 = k1i < ko1 ? k1i : ko1;
+                if (ki1 <= ki0) ki0 = ki1 = ko1;
+            }
+        }
+        if (ki0 > km) sweep(km, ki0, std::integral_constant<int, 3>());
+        if (ki1 > ki0) {
+            imax = start(ki1 - 1);
+            sweep(ki0, ki1, std::integral_constant<int, 4>());
+        }
+        if (ko1 > ki1) sweep(ki1, ko1, std::integral_constant<int, 3>());
     } else if (ko1 > kwarm) sweep(kwarm, ko1, std::integral_constant<int, 1>());
     if (nsteps > ko1) sweep(ko1, nsteps, std::integral_constant<int, 2>());
     if (FUSE) {
         // drain: the delayed copies of the last steps still meet their y; rho of steps that never come is zero
         const int sig_end = n_total + 1;
         if (gtau >= 0) {
+            double zero[NPc];
 #pragma unroll
-            for (int a = 0; a < NPc; a++) RG[rgrow((sig_end + lane) & 127) + a] = 0.0;
+            for (int a = 0; a < NPc; a++) zero[a] = 0.0;
+            rstore(sig_end + lane, zero);
             gmfma(sig_end + 16 * (NSc - 1) + 4);               // tau up to sig_end + 16 (NS - 1): the last delayed copy
         }
         double *pg = partG + (int64_t)cg * N * L;
@@ -1121,9 +1244,7 @@ static int wave_estep_sweeps(WaveDev *r, const double *d_y, double *d_stats, hip
         HS_CHECK(p.logdl == (NN > 8) && (ft == 0 || (kFuse4 && ft == 1) || (kFuse8 && p.uc && (ft == 2 || ft == 4))),
                  HMMSORT_EINVAL, "wave E-step: no kernel for the picked row (ft %d)", ft);
         const bool fuse = ft > 0;
-        const int ym = bwd_yring(ft);
-        const size_t ldsb = ((size_t)(NN + 1) * (g.RB + 1) + 4 + 3 * NN + NN * NN +
-                             (fuse ? ym + (128 + 8 * (NN <= 4 ? 1 : 2)) * (NN <= 4 ? 4 : 8) : 0)) * sizeof(double);
+        const size_t ldsb = ((size_t)(NN + 1) * (g.RB + 1) + 4 + 3 * NN + NN * NN + bwd_stat_doubles(NN, ft)) * sizeof(double);
         auto kf = kw_fwd<NN, true>;
         auto kb = kw_bwd<NN, true>;
         if constexpr (NN <= kWaveMaxPerSource) {   // per-source exit -> entry values: up to 8 rings (wave_supported)
