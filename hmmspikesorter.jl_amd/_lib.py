@@ -72,6 +72,12 @@ class SeedOut(C.Structure):
                 ("times", _vp), ("labels", _vp), ("cap", _i64)]
 
 
+class SpikeFitOut(C.Structure):
+    """struct hmmsort_spike_fit_out: host arrays hmmsort_spike_fit fills (rows of `cap` entries; counts is required)"""
+    _fields_ = [("times", _vp), ("amp", _vp), ("rss", _vp), ("energy", _vp), ("nused", _vp), ("cap", _i64),
+                ("counts", _vp), ("summary", _vp)]
+
+
 SEED_MAX_K, SEED_MAX_N, SEED_MAX_R = 1025, 16, 1024
 
 # name -> (restype, argtypes); every symbol include/hmmsort.h declares
@@ -147,6 +153,9 @@ SIGNATURES = {
     "hmmsort_plan_expected_counts": (_int, [_vp, _vp, _vp]),
     "hmmsort_posteriors": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _f64, _vp, _vp, _vp, _vp,
                                   _vp]),
+    "hmmsort_spike_fit": (_int, [_vp, _int, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp,
+                                 C.POINTER(SpikeFitOut)]),
+    "hmmsort_plan_spike_fit": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, C.POINTER(SpikeFitOut), _vp]),
     "hmmsort_plan_profile": (_int, [_vp, _int]),
     "hmmsort_plan_profile_read": (_int, [_vp, _vp, C.c_char_p, _i64, C.POINTER(_f64), _pi64, _i64,
                                          _pi64]),

@@ -14,7 +14,8 @@ Reference methods mirrored (file:line relative to the reference root):
   unroll_mlseq                                                        src/extraction.jl:4
   fit(HMMSpikingModel, templates, X, chunksize)                       src/fit.jl:11-42
 Extensions (no counterpart in the reference): posteriors, posterior_decode, spike_confidence, fit_step_channels, viterbi_step,
-train_model(..., method="viterbi"), fit_adaptive, reconstruct_tracked, seed_templates and train_model(..., init="detect").
+train_model(..., method="viterbi"), fit_adaptive, reconstruct_tracked, seed_templates, train_model(..., init="detect"),
+spike_fit and unit_quality.  get_energy mirrors src/utils.jl:112-124 on the host.
 """
 import ctypes as C
 from dataclasses import dataclass
@@ -785,6 +786,120 @@ def extract_spiketimes(model):
         if counts.max(initial=0) <= cap:
             return [times[i, :counts[i]].copy() for i in range(lA.N)]
         cap = int(counts.max())
+
+
+@dataclass
+class SpikeFit:
+    """Per-spike fit of one template (hmmsort_spike_fit; definitions in include/hmmsort.h), aligned element for
+    element with extract_spiketimes."""
+    times: np.ndarray     # 1-based trough samples, ascending
+    amp: np.ndarray       # least-squares amplitude of the template on the overlap-cleaned window (1 = as the template)
+    rss: np.ndarray       # residual sum of squares at unit amplitude (at the fitted one: energy - amp^2 smm)
+    energy: np.ndarray    # sum of squares of the overlap-cleaned window
+    nused: np.ndarray     # phases of the window the path supports; K - 1 for a full event
+    summary: np.ndarray   # 8 + 3 (K-1) doubles: n, n_full, sums over full events, smm, wsum / wsq / wcnt per phase
+
+
+@dataclass
+class UnitQuality:
+    """What unit_quality derives from a template's summary and sigma."""
+    n: int                   # events
+    n_full: int              # events whose whole window the path supports; the figures below are over these
+    mean_amp: float          # sum amp / n_full
+    sd_amp: float            # sqrt(sum amp^2 / n_full - mean_amp^2), the spread around the mean
+    sd_expected: float       # sigma / sqrt(smm): the spread noise alone gives
+    chi2: float              # sum rss / (sigma^2 (K-1) n_full): 1 when the template explains its spikes
+    energy: float            # smm / sigma^2
+    waveform: np.ndarray     # K - 1: overlap-cleaned spike-triggered mean, wsum / wcnt (all events, used phases)
+    waveform_sd: np.ndarray  # K - 1: its spread, sqrt(wsq / wcnt - waveform^2)
+
+
+def _track_args(lA, track):
+    """(nchunks, first, mu_track [n][K*N]) of a ModelTrack, or (0, None, None); the arrays must outlive the call"""
+    if track is None:
+        return 0, None, None
+    first = np.ascontiguousarray(track.first, dtype=np.int64)
+    mu = np.ascontiguousarray(np.asarray(track.mu, dtype=np.float64).transpose(0, 2, 1))   # column-major K x N each
+    if mu.ndim != 3 or mu.shape != (len(first), lA.N, lA.K):
+        raise ValueError("track.mu must be n x K x N = %d x %d x %d" % (len(first), lA.K, lA.N))
+    return len(first), first, mu
+
+
+def _spike_fit_run(call, nC, N, K, cap):
+    """call(byref(hmmsort_spike_fit_out)) -> rc, repeated with a larger cap until every event fits: per channel a
+    list of SpikeFit, one per template"""
+    L = 8 + 3 * (K - 1)
+    while True:
+        b = dict(times=np.zeros((nC, N, cap), dtype=np.int64), amp=np.zeros((nC, N, cap)), rss=np.zeros((nC, N, cap)),
+                 energy=np.zeros((nC, N, cap)), nused=np.zeros((nC, N, cap), dtype=np.int32),
+                 counts=np.zeros((nC, N), dtype=np.int64), summary=np.zeros((nC, N, L)))
+        out = _lib.SpikeFitOut(*[b[k].ctypes.data for k in ("times", "amp", "rss", "energy", "nused")], cap,
+                               b["counts"].ctypes.data, b["summary"].ctypes.data)
+        check(call(C.byref(out)))
+        if b["counts"].max(initial=0) <= cap:
+            break
+        cap = int(b["counts"].max())
+    cnt = b["counts"]
+    return [[SpikeFit(*[b[k][c, a, :cnt[c, a]].copy() for k in ("times", "amp", "rss", "energy", "nused")],
+                      b["summary"][c, a].copy()) for a in range(N)] for c in range(nC)]
+
+
+def spike_fit(model, track=None):
+    """spike_fit(model::HMMSpikingModel[, track::ModelTrack]) -> one SpikeFit per template (an extension,
+    INTEGRATION.md "Spike fit"): for every spike extract_spiketimes reports, the least-squares amplitude of the
+    template on the samples under it once the other templates the path says are active are subtracted, the residual
+    at unit amplitude and the window's energy.  With fit_adaptive's `track` every spike is measured against the
+    templates its chunk was decoded with.  int16 samples go to the device as they are."""
+    tm = model.template_model
+    lA = tm.state_matrix
+    raw = isinstance(model.y, np.ndarray) and model.y.dtype == np.int16 and model.y.ndim == 1
+    y = np.ascontiguousarray(model.y) if raw else _signal(model.y)
+    x = np.ascontiguousarray(model.ml_seq, dtype=np.int16)
+    if len(x) != len(y):
+        raise ValueError("spike_fit: the path has %d samples, the signal %d" % (len(x), len(y)))
+    mu = np.asfortranarray(tm.mu, dtype=np.float64)
+    st = np.asfortranarray(lA.states, dtype=np.int16)
+    nch, first, mut = _track_args(lA, track)
+    stype = _lib.SAMPLES_I16 if raw else _lib.SAMPLES_F64
+    return _spike_fit_run(lambda out: lib().hmmsort_spike_fit(ptr(y), stype, len(y), ptr(x), ptr(st), lA.N, lA.nstates,
+                                                              ptr(mu), mu.shape[0], nch, ptr(first), ptr(mut), out),
+                          1, lA.N, mu.shape[0], max(1, len(x) // 8))[0]
+
+
+def quality_from_summary(summary, K, sigma):
+    """UnitQuality of one template's summary vector (SpikeFit.summary)"""
+    s = np.asarray(summary, dtype=np.float64)
+    P = K - 1
+    n, nf, sa, saa, srss, _sen, _snu, smm = s[:8]
+    wsum, wsq, wcnt = s[8:8 + P], s[8 + P:8 + 2 * P], s[8 + 2 * P:8 + 3 * P]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = sa / nf
+        sd = np.sqrt(np.maximum(saa / nf - mean * mean, 0.0))
+        wf = wsum / wcnt
+        wsd = np.sqrt(np.maximum(wsq / wcnt - wf * wf, 0.0))
+        return UnitQuality(int(n), int(nf), float(mean), float(sd), float(sigma / np.sqrt(smm)),
+                           float(srss / (sigma * sigma * P * nf)), float(smm / (sigma * sigma)), wf, wsd)
+
+
+def unit_quality(model, track=None):
+    """unit_quality(model[, track]) -> one UnitQuality per template, from spike_fit's summary and the model's sigma:
+    do these templates fit this recording (chi2 near 1, mean_amp near 1, sd_amp near sd_expected), and what do the
+    spikes the path found look like (waveform)?  Figures without events are NaN."""
+    tm = model.template_model
+    return [quality_from_summary(f.summary, tm.state_matrix.K, tm.sigma) for f in spike_fit(model, track)]
+
+
+def get_energy(waveforms, cinv):
+    """get_energy(waveforms::Array{Float64,2}, cinv::Float64) -> ee   utils.jl:112-124: per template (column) the sum
+    over rows j ascending of w*cinv*w, folded from 0.0 in the reference's operation order.  Host code."""
+    W = np.asarray(waveforms, dtype=np.float64)
+    if W.ndim != 2:
+        raise ValueError("get_energy: waveforms must be nstates x N")
+    cinv = np.float64(cinv)
+    ee = np.zeros(W.shape[1])
+    for j in range(W.shape[0]):
+        ee += (W[j] * cinv) * W[j]
+    return ee
 
 
 @dataclass

@@ -541,8 +541,12 @@ int hmmsort_unroll_mlseq(const int16_t *mlseq, int64_t T, const int16_t *states,
 // extract_spiketimes on a path that already lives in device memory
 static int extract_from_device(const int16_t *d_x, int64_t T, const int16_t *states, int64_t N,
                                int64_t S, const double *mu, int64_t K, int64_t *times_out,
-                               int64_t cap, int64_t *counts_out, hipStream_t st, DevBuf *dt_keep = nullptr)
+                               int64_t cap, int64_t *counts_out, hipStream_t st, DevBuf *dt_keep = nullptr,
+                               int64_t *dcap_all = nullptr)
 {
+    // dcap_all (with dt_keep): the device keeps EVERY event, rows of *dcap_all = max(1, largest count) entries,
+    // whatever cap says; the host still receives the first min(count, cap) of each row
+    const bool all = dt_keep && dcap_all;
     // match table per state: the states in which a template is at its trough
     std::vector<uint32_t> match(S, 0u);
     for (int64_t i = 0; i < N; i++) {
@@ -556,7 +560,7 @@ static int extract_from_device(const int16_t *d_x, int64_t T, const int16_t *sta
     int rc;
     if ((rc = dm.alloc(S * sizeof(uint32_t))) || (rc = dcnt.alloc(nb * N * sizeof(int64_t))) ||
         (rc = doff.alloc(nb * N * sizeof(int64_t))) ||
-        (rc = dt.alloc(std::max<int64_t>(1, N * cap) * sizeof(int64_t))))
+        (!all && (rc = dt.alloc(std::max<int64_t>(1, N * cap) * sizeof(int64_t)))))
         return rc;
     HS_HIP(hipMemcpyAsync(dm.p, match.data(), S * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     if ((rc = dev_spike_compact(d_x, T, dm.as<uint32_t>(), (int)N, (int)S, 0, dcnt.as<int64_t>(), nullptr,
@@ -569,6 +573,24 @@ static int extract_from_device(const int16_t *d_x, int64_t T, const int16_t *sta
         int64_t acc = 0;
         for (int64_t b = 0; b < nb; b++) { off[b * N + i] = acc; acc += cnt[b * N + i]; }
         counts_out[i] = acc;
+    }
+    if (all) {
+        int64_t dcap = 1;
+        for (int64_t i = 0; i < N; i++) dcap = std::max(dcap, counts_out[i]);
+        *dcap_all = dcap;
+        if ((rc = dt.alloc((size_t)N * dcap * sizeof(int64_t)))) return rc;
+        HS_HIP(hipMemcpyAsync(doff.p, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        if ((rc = dev_spike_compact(d_x, T, dm.as<uint32_t>(), (int)N, (int)S, 1, dcnt.as<int64_t>(),
+                                    doff.as<int64_t>(), dt.as<int64_t>(), dcap, st)))
+            return rc;
+        for (int64_t i = 0; i < N && times_out; i++) {
+            const int64_t n = std::min(counts_out[i], cap);
+            if (n > 0)
+                HS_HIP(hipMemcpyAsync(times_out + i * cap, dt.as<int64_t>() + i * dcap, n * sizeof(int64_t),
+                                      hipMemcpyDeviceToHost, st));
+        }
+        HS_HIP(hipStreamSynchronize(st));   // off and the compaction tables die with this frame
+        return HMMSORT_OK;
     }
     if (cap == 0) return HMMSORT_OK;
     HS_HIP(hipMemcpyAsync(doff.p, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
@@ -699,6 +721,160 @@ int hmmsort_plan_expected_counts(hmmsort_plan *p, double *counts_out, void *stre
 {
     HS_CHECK(p && counts_out, HMMSORT_EINVAL, "plan_expected_counts: null argument");
     return p->eng->expected_counts(counts_out, (hipStream_t)stream);
+}
+
+// ---- per-spike fit (spike_fit.hip) -------------------------------------------------
+
+// what both entry points refuse before any GPU work; qv receives the N trough values of the base templates
+static int spike_fit_check(const char *who, int64_t N, int64_t S, const double *mu, int64_t K, int64_t nchunks,
+                           const int64_t *first, const double *mu_track, const hmmsort_spike_fit_out *out, int32_t *qv)
+{
+    HS_CHECK(N >= 1 && N <= 32, HMMSORT_EINVAL, "%s: N = %lld templates (1..32)", who, (long long)N);
+    HS_CHECK(K >= 2, HMMSORT_EINVAL, "%s: K = %lld (a template needs at least one phase besides the silent row)", who,
+             (long long)K);
+    HS_CHECK(S >= 1 && out->cap >= 0, HMMSORT_EINVAL, "%s: bad sizes (S = %lld, cap = %lld)", who, (long long)S,
+             (long long)out->cap);
+    HS_CHECK(nchunks >= 0, HMMSORT_EINVAL, "%s: nchunks = %lld", who, (long long)nchunks);
+    HS_CHECK(nchunks <= kTrackChunks, HMMSORT_EUNSUP, "%s: %lld chunks (at most %lld)", who, (long long)nchunks,
+             (long long)kTrackChunks);
+    if (nchunks > 0) {
+        HS_CHECK(first && mu_track, HMMSORT_EINVAL, "%s: a track needs first and mu_track", who);
+        HS_CHECK(first[0] >= 1, HMMSORT_EINVAL, "%s: first[0] = %lld is no 1-based sample number", who,
+                 (long long)first[0]);
+        for (int64_t c = 1; c < nchunks; c++)
+            HS_CHECK(first[c] > first[c - 1], HMMSORT_EINVAL, "%s: chunk starts must ascend (first[%lld] = %lld after "
+                     "%lld)", who, (long long)c, (long long)first[c], (long long)first[c - 1]);
+    }
+    for (int64_t a = 0; a < N; a++) {
+        qv[a] = trough_value(mu, K, a);
+        HS_CHECK(qv[a] != 1, HMMSORT_EINVAL, "%s: template %lld has its minimum in the silent row (trough value 1): "
+                 "no state marks its spikes", who, (long long)a);
+    }
+    return HMMSORT_OK;
+}
+
+// one channel: resident signal and path in, host arrays out (rows of `cap` entries; any of them may be null)
+static int spike_fit_channel(const double *d_y, const int16_t *d_x, int64_t T, const int16_t *states, int64_t N,
+                             int64_t S, const double *mu, int64_t K, const int32_t *qv, int64_t nchunks,
+                             const int64_t *first, const double *mu_track, int64_t *times, double *amp, double *rss,
+                             double *energy, int32_t *nused, int64_t cap, int64_t *counts, double *summary,
+                             hipStream_t st)
+{
+    const int64_t L = spike_fit_len(K);
+    for (int64_t a = 0; a < N; a++) counts[a] = 0;
+    if (summary) {
+        std::fill(summary, summary + N * L, 0.0);
+        for (int64_t a = 0; a < N; a++) {   // smm of the whole base template, k = 2..K ascending
+            double s = 0.0;
+            for (int64_t k = 1; k < K; k++) {
+                const double q = mu[k + K * a] * mu[k + K * a];
+                s += q;
+            }
+            summary[a * L + 7] = s;
+        }
+    }
+    if (T == 0) return HMMSORT_OK;
+    int rc = need_device();
+    if (rc) return rc;
+    DevBuf dt;
+    int64_t dcap = 1;
+    if ((rc = extract_from_device(d_x, T, states, N, S, mu, K, times, cap, counts, st, &dt, &dcap))) return rc;
+    int64_t maxn = 0;
+    for (int64_t a = 0; a < N; a++) maxn = std::max(maxn, counts[a]);
+    if (maxn == 0) return HMMSORT_OK;
+    const int64_t nblk = spike_fit_blocks(maxn), nM = (nchunks > 0 ? nchunks : 1) * K * N;
+    DevBuf dst, dM, dfirst, damp, drss, den, dnu, dch, dpart, dsum;
+    if ((rc = dst.alloc(N * S * sizeof(int16_t))) || (rc = dM.alloc(nM * sizeof(double))) ||
+        (rc = dfirst.alloc(std::max<int64_t>(1, nchunks) * sizeof(int64_t))) ||
+        (rc = damp.alloc(N * dcap * sizeof(double))) || (rc = drss.alloc(N * dcap * sizeof(double))) ||
+        (rc = den.alloc(N * dcap * sizeof(double))) || (rc = dnu.alloc(N * dcap * sizeof(int32_t))) ||
+        (rc = dch.alloc(N * dcap * sizeof(int32_t))) || (rc = dpart.alloc(N * nblk * L * sizeof(double))) ||
+        (rc = dsum.alloc(N * L * sizeof(double))))
+        return rc;
+    HS_HIP(hipMemcpyAsync(dst.p, states, N * S * sizeof(int16_t), hipMemcpyHostToDevice, st));
+    HS_HIP(hipMemcpyAsync(dM.p, nchunks > 0 ? mu_track : mu, nM * sizeof(double), hipMemcpyHostToDevice, st));
+    if (nchunks > 0)
+        HS_HIP(hipMemcpyAsync(dfirst.p, first, nchunks * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    if ((rc = dev_spike_fit(d_y, d_x, T, dst.as<int16_t>(), N, S, K, dM.as<double>(), nchunks, dfirst.as<int64_t>(),
+                            dt.as<int64_t>(), dcap, counts, qv, damp.as<double>(), drss.as<double>(),
+                            den.as<double>(), dnu.as<int32_t>(), dch.as<int32_t>(), dpart.as<double>(),
+                            dsum.as<double>(), st)))
+        return rc;
+    for (int64_t a = 0; a < N; a++) {
+        const size_t n = (size_t)std::min(counts[a], cap);
+        if (n == 0) continue;
+        if (amp) HS_HIP(hipMemcpyAsync(amp + a * cap, damp.as<double>() + a * dcap, n * 8, hipMemcpyDeviceToHost, st));
+        if (rss) HS_HIP(hipMemcpyAsync(rss + a * cap, drss.as<double>() + a * dcap, n * 8, hipMemcpyDeviceToHost, st));
+        if (energy)
+            HS_HIP(hipMemcpyAsync(energy + a * cap, den.as<double>() + a * dcap, n * 8, hipMemcpyDeviceToHost, st));
+        if (nused)
+            HS_HIP(hipMemcpyAsync(nused + a * cap, dnu.as<int32_t>() + a * dcap, n * 4, hipMemcpyDeviceToHost, st));
+    }
+    std::vector<double> sum(summary ? N * L : 0);
+    if (summary) HS_HIP(hipMemcpyAsync(sum.data(), dsum.p, N * L * sizeof(double), hipMemcpyDeviceToHost, st));
+    HS_HIP(hipStreamSynchronize(st));
+    for (int64_t i = 0; summary && i < N * L; i++)
+        if (i % L != 7) summary[i] = sum[i];
+    return HMMSORT_OK;
+}
+
+int hmmsort_spike_fit(const void *y, int sample_type, int64_t T, const int16_t *x, const int16_t *states, int64_t N,
+                      int64_t S, const double *mu, int64_t K, int64_t nchunks, const int64_t *first,
+                      const double *mu_track, hmmsort_spike_fit_out *out)
+{
+    HS_CHECK(states && mu && out && out->counts && (T == 0 || (y && x)), HMMSORT_EINVAL, "spike_fit: null argument");
+    HS_CHECK(sample_type == HMMSORT_SAMPLES_F64 || sample_type == HMMSORT_SAMPLES_I16, HMMSORT_EINVAL,
+             "spike_fit: samples must be HMMSORT_SAMPLES_F64 or HMMSORT_SAMPLES_I16");
+    HS_CHECK(T >= 0, HMMSORT_EINVAL, "spike_fit: T = %lld", (long long)T);
+    int32_t qv[32];
+    int rc = spike_fit_check("spike_fit", N, S, mu, K, nchunks, first, mu_track, out, qv);
+    if (rc) return rc;
+    // every phase the table names must be a row of the templates: the device code indexes with it
+    for (int64_t i = 0; i < N * S; i++)
+        HS_CHECK(states[i] >= 1 && states[i] <= K, HMMSORT_EINVAL, "spike_fit: states[%lld] = %d outside 1..K",
+                 (long long)i, (int)states[i]);
+    DevBuf draw, dy, dx;
+    if (T > 0) {
+        if ((rc = need_device())) return rc;
+        if ((rc = dy.alloc((size_t)T * sizeof(double))) || (rc = dx.alloc((size_t)T * sizeof(int16_t)))) return rc;
+        HS_HIP(hipMemcpy(dx.p, x, (size_t)T * sizeof(int16_t), hipMemcpyHostToDevice));
+        if (sample_type == HMMSORT_SAMPLES_I16) {
+            if ((rc = draw.alloc((size_t)T * sizeof(int16_t)))) return rc;
+            HS_HIP(hipMemcpy(draw.p, y, (size_t)T * sizeof(int16_t), hipMemcpyHostToDevice));
+            if ((rc = dev_widen(draw.p, sample_type, T, 1, dy.as<double>(), nullptr))) return rc;
+        } else {
+            HS_HIP(hipMemcpy(dy.p, y, (size_t)T * sizeof(double), hipMemcpyHostToDevice));
+        }
+    }
+    return spike_fit_channel(dy.as<double>(), dx.as<int16_t>(), T, states, N, S, mu, K, qv, nchunks, first, mu_track,
+                             out->times, out->amp, out->rss, out->energy, out->nused, out->cap, out->counts,
+                             out->summary, nullptr);
+}
+
+int hmmsort_plan_spike_fit(hmmsort_plan *p, const double *d_y, const int16_t *d_x, int64_t nchunks,
+                           const int64_t *first, const double *mu_track, hmmsort_spike_fit_out *out, void *stream)
+{
+    HS_CHECK(p && d_y && d_x && out && out->counts, HMMSORT_EINVAL, "plan_spike_fit: null argument");
+    HS_CHECK(p->C == 1 || nchunks == 0, HMMSORT_EINVAL, "plan_spike_fit: a batched plan takes no model track");
+    const int64_t N = p->model.N, K = p->model.K, S = p->model.S, T = p->T, cap = out->cap, L = spike_fit_len(K);
+    std::vector<int32_t> qv((size_t)p->C * 32);
+    for (int64_t ch = 0; ch < p->C; ch++) {
+        const HostModel &m = p->C > 1 ? p->models[ch] : p->model;
+        int rc = spike_fit_check("plan_spike_fit", N, S, m.mu.data(), K, nchunks, first, mu_track, out, &qv[ch * 32]);
+        if (rc) return rc;
+    }
+    for (int64_t ch = 0; ch < p->C; ch++) {
+        const HostModel &m = p->C > 1 ? p->models[ch] : p->model;
+        const int64_t o = ch * N * cap;
+        int rc = spike_fit_channel(d_y + ch * T, d_x + ch * T, T, m.states.data(), N, S, m.mu.data(), K, &qv[ch * 32],
+                                   nchunks, first, mu_track, out->times ? out->times + o : nullptr,
+                                   out->amp ? out->amp + o : nullptr, out->rss ? out->rss + o : nullptr,
+                                   out->energy ? out->energy + o : nullptr, out->nused ? out->nused + o : nullptr, cap,
+                                   out->counts + ch * N, out->summary ? out->summary + ch * N * L : nullptr,
+                                   (hipStream_t)stream);
+        if (rc) return rc;
+    }
+    return HMMSORT_OK;
 }
 
 }  // extern "C"

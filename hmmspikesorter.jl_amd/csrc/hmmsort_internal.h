@@ -325,6 +325,18 @@ constexpr int kPostParts = 256;
 int dev_spike_conf(const double *d_src, const double *d_head, int64_t T, int64_t shift, int64_t jitter,
                    const int64_t *d_times, int64_t n, double *d_conf, hipStream_t st);
 int dev_row_sums(const double *d_rows, int64_t nrows, int64_t T, double *d_part, double *out_host, hipStream_t st);
+// per-spike fit (spike_fit.hip; rules in its header and include/hmmsort.h): the events d_times [N][dcap] (1-based,
+// ascending, counts[a] <= dcap of them per template, trough values qv) of the path d_x of d_y under the templates d_M
+// ([K*N], or with nchunks > 0 the track [nchunks][K*N] with chunk starts d_first) into the per-event arrays
+// [N][dcap] and d_summary [N][spike_fit_len(K)] (slot 7 left 0.0 for the caller).  d_part: N x spike_fit_blocks(max
+// count) x spike_fit_len(K) doubles of scratch.  Nothing is launched when no template has an event.
+inline int64_t spike_fit_len(int64_t K) { return 8 + 3 * (K - 1); }
+inline int64_t spike_fit_blocks(int64_t n) { return (n + 255) / 256; }
+int dev_spike_fit(const double *d_y, const int16_t *d_x, int64_t T, const int16_t *d_states, int64_t N, int64_t S,
+                  int64_t K, const double *d_M, int64_t nchunks, const int64_t *d_first, const int64_t *d_times,
+                  int64_t dcap, const int64_t *counts, const int32_t *qv, double *d_amp, double *d_rss,
+                  double *d_energy, int32_t *d_nused, int32_t *d_chunk, double *d_part, double *d_summary,
+                  hipStream_t st);
 
 }  // namespace hmmsort
 

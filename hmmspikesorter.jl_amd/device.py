@@ -248,6 +248,19 @@ class Plan:
                for c in range(nC)]
         return out if hasattr(self, "C") else out[0]
 
+    def spike_fit(self, d_y, d_x, track=None, stream=0):
+        """per template an api.SpikeFit of the events extract_spiketimes reports on the path d_x of the resident
+        signal d_y, under the plan's current model (hmmsort_plan_spike_fit): amplitude, residual at unit amplitude,
+        energy and used phases per spike, and the per-template summary.  `track`: fit_adaptive's ModelTrack
+        (single-channel plans only).  A batched plan returns one such list per channel."""
+        from .api import _spike_fit_run, _track_args
+        nC = getattr(self, "C", 1)
+        nch, first, mut = _track_args(self.lA, track)
+        out = _spike_fit_run(lambda o: lib().hmmsort_plan_spike_fit(self._h, _dptr(d_y), _dptr(d_x), nch, ptr(first),
+                                                                    ptr(mut), o, C.c_void_p(stream)),
+                             nC, self.N, self.K, max(1, self.T // 8))
+        return out if hasattr(self, "C") else out[0]
+
     def expected_counts(self, stream=0):
         """expected number of spikes per template, sum_t onset[a, t] ([C][N]; [N] for a single-channel plan)"""
         nC = getattr(self, "C", 1)

@@ -71,7 +71,7 @@ def _chunk_confidence(templates, dataf, ml_seq, chunksize, jitter):
 
 
 def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_templates=4,
-              chunksize=100_000, confidence=False, jitter=2, refine_steps=0, adapt_halflife=None):
+              chunksize=100_000, confidence=False, jitter=2, refine_steps=0, adapt_halflife=None, quality=False):
     """sort_data(inputfile, datafile, outputfile; dosave, max_templates)   hmmsort.jl:36-104.
 
     Returns the reference's output dictionary; {} when there are more templates than
@@ -97,7 +97,12 @@ def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_temp
     (api.fit_adaptive: the templates and sigma are re-estimated after every chunk from statistics that lose half
     their weight every h samples) and adds "waveforms_track" (chunks x nstates x ntemplates, the templates each chunk
     was decoded with), "sigma_track" and "chunk_first" (1-based first sample of each chunk).  "waveforms" and
-    "sigma" stay the model the decode started from."""
+    "sigma" stay the model the decode started from.
+
+    `quality=True` (an extension; default off, output unchanged) adds "spiketimes" (when `confidence` has not already),
+    "amplitude" and "residual" (per template and spike: api.spike_fit's amp and rss on the whole recording and the
+    stitched path) and "unit_quality" (per-template arrays of api.unit_quality's figures).  With `adapt_halflife`
+    every spike is measured against the templates its chunk was decoded with."""
     spike_forms = np.asarray(spike_forms, dtype=np.float64)
     nstates, _nchannels, ntemplates = spike_forms.shape
     pp = np.atleast_1d(np.asarray(p, dtype=np.float64))
@@ -139,9 +144,21 @@ def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_temp
         out["spiketimes"], out["confidence"] = np.empty(len(st), dtype=object), np.empty(len(cf), dtype=object)
         for a in range(len(st)):
             out["spiketimes"][a], out["confidence"][a] = st[a], cf[a]
+    if quality:
+        fits = api.spike_fit(modelf, track)
+        names = (("spiketimes", "times"), ("amplitude", "amp"), ("residual", "rss"))
+        for key, field in names[("spiketimes" in out):]:
+            out[key] = np.empty(len(fits), dtype=object)                       # a cell per template
+            for a, f in enumerate(fits):
+                out[key][a] = getattr(f, field)
+        uq = [api.quality_from_summary(f.summary, sm.K, sigma) for f in fits]
+        out["unit_quality"] = {k: np.array([getattr(q, k) for q in uq])
+                               for k in ("n", "n_full", "mean_amp", "sd_amp", "sd_expected", "chi2", "energy")}
+        out["unit_quality"]["waveform"] = np.stack([q.waveform for q in uq], axis=1)
+        out["unit_quality"]["waveform_sd"] = np.stack([q.waveform_sd for q in uq], axis=1)
     if dosave and outputfile is not None:
         from scipy.io import savemat
-        savemat(outputfile, out)                                               # MAT.matwrite :100
+        savemat(outputfile, out)                                              # MAT.matwrite :100
     return out
 
 

@@ -566,6 +566,60 @@ int hmmsort_posteriors(const double *y, int64_t T, const int16_t *states, int64_
                        const hmm_trans *tr, int64_t R, const double *mu, double sigma, double *onset,
                        double *occ, double *silent, int16_t *xm, double *logz);
 
+/* Per-spike amplitude and residual, and a per-template quality summary (an extension): how well the
+ * spike the path placed fits the samples under it, once the other templates the path says are active are taken out.
+ * Inputs: y[T] (fp64, or int16 widened exactly), x[T] an Int16 path, 1-based (normally a decode; any array is
+ * accepted), states N x S, mu K x N, and optionally a model track (nchunks, first, mu_track) as
+ * hmmsort_reconstruct_tracked takes it; nchunks == 0: no track.
+ *   events    exactly those of hmmsort_extract_spiketimes, in its ascending order: template a has an event at 0-based
+ *             sample t when x[t] is in 1..S and states[a, x[t]] == qv_a, the trough value of the BASE mu (also under a
+ *             track).  A template whose minimum is in the silent row (qv_a == 1): HMMSORT_EINVAL naming it.
+ *   model     M = mu; under a track M = mu_track[c] for the last chunk c with first[c] <= t + 1 (the trough's chunk
+ *             serves the whole window).  An event before first[0]: amp = rss = energy = NaN, nused = 0; it is counted
+ *             in n only.
+ *   window    for phases k = 2..K ascending, u = t + (k - qv_a); phase k is used iff 0 <= u < T, x[u] is in 1..S and
+ *             states[a, x[u]] == k (a path that jumps, starts or ends mid-spike gives a partial event).  nused = number
+ *             of used phases; the event is full iff nused == K - 1.
+ *   phase     oth = 0.0; for b ascending, b != a: oth += M[states[b, x[u]] - 1, b] (reconstruct_signal's row lookup,
+ *             silent row included);  r = y[u] - oth;  m = M[k - 1, a].
+ *   event     four serial folds from 0.0 in ascending k, product and sum rounded separately (never a fused
+ *             multiply-add): srm += r*m, smm += m*m, energy += r*r, rss += d*d with d = r - m.  amp = srm / smm, the
+ *             IEEE quotient whatever it is.  rss is the residual at unit amplitude; the residual at the fitted
+ *             amplitude is energy - amp * srm = energy - amp * amp * smm and is left to the caller.
+ *   summary   per template 8 + 3 (K-1) doubles: [0] n (all events), [1] n_full, [2] sum amp, [3] sum amp*amp,
+ *             [4] sum rss, [5] sum energy (2..5 over full events), [6] sum nused (all events), [7] smm of the whole base
+ *             template (k = 2..K ascending); then wsum, wsq, wcnt of K-1 entries each: sum of r, sum of r*r and count
+ *             per phase over every used phase of every event -- the overlap-cleaned spike-triggered mean and spread, what
+ *             one compares a template loaded from a file against.  Fixed order, no floating-point atomics: events in
+ *             ascending order are cut into blocks of 256, each slot's block partial is a serial fold from 0.0 in event
+ *             order, the partials are folded serially from 0.0 in block order; counts are doubles.  The summary covers
+ *             all n events, also when cap < n.
+ * Outputs are host arrays: times (1-based), amp, rss, energy, nused as N rows of `cap` entries, any of them NULL;
+ * counts [N] is required; protocol of hmmsort_extract_spiketimes (entries beyond cap are dropped, entries beyond counts
+ * untouched; cap = 0: counts and summary only).
+ * Refused before any GPU work: a null required argument, N outside 1..32, K < 2, a sample type other than F64 / I16,
+ * first not strictly ascending or first[0] < 1 (HMMSORT_EINVAL); nchunks > 8192 (HMMSORT_EUNSUP).  T == 0: zero counts,
+ * zero summary except [7].
+ * hmmsort_spike_fit: host buffers, no plan; uploads once, int16 samples as they are (widened on the device).
+ * hmmsort_plan_spike_fit: resident d_y / d_x of the plan's length under the plan's current model; a batched plan takes
+ * channel-major buffers and writes [C][N][cap], [C][N] and [C][N][8 + 3 (K-1)] as hmmsort_plan_spike_confidence lays
+ * them out, and takes no track (HMMSORT_EINVAL).  Synchronises the stream. */
+typedef struct hmmsort_spike_fit_out {
+    int64_t *times;     /* [N][cap], may be NULL */
+    double *amp;        /* [N][cap], may be NULL */
+    double *rss;        /* [N][cap], may be NULL */
+    double *energy;     /* [N][cap], may be NULL */
+    int32_t *nused;     /* [N][cap], may be NULL */
+    int64_t cap;
+    int64_t *counts;    /* [N], required */
+    double *summary;    /* [N][8 + 3 (K-1)], may be NULL */
+} hmmsort_spike_fit_out;
+int hmmsort_spike_fit(const void *y, int sample_type, int64_t T, const int16_t *x, const int16_t *states, int64_t N,
+                      int64_t S, const double *mu, int64_t K, int64_t nchunks, const int64_t *first,
+                      const double *mu_track, hmmsort_spike_fit_out *out);
+int hmmsort_plan_spike_fit(hmmsort_plan *plan, const double *d_y, const int16_t *d_x, int64_t nchunks,
+                           const int64_t *first, const double *mu_track, hmmsort_spike_fit_out *out, void *stream);
+
 /* Widening of raw samples already in device memory into the fp64 signal the plan calls take
  * (src/hmmsort.jl:79-88: `view(data, :, 1)` of the acquisition array, converted to Float64): element i
  * of the output is d_in[i * stride] (stride in elements: 1 for a channel stored contiguously, the

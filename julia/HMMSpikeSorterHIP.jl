@@ -337,6 +337,66 @@ function seed_templates_device(d_y::Ptr{Float64}, n::Integer, N::Integer=3, K::I
     _seed_finish(N, K, resolve_overlaps, μ, σ, lp, counts, ne, iters, times, labels)
 end
 
+# struct hmmsort_spike_fit_out (include/hmmsort.h)
+struct CSpikeFitOut
+    times::Ptr{Int64}; amp::Ptr{Float64}; rss::Ptr{Float64}; energy::Ptr{Float64}; nused::Ptr{Int32}; cap::Int64
+    counts::Ptr{Int64}; summary::Ptr{Float64}
+end
+
+# call(out::Ref{CSpikeFitOut}) -> code, repeated with a larger cap until every event fits
+function _spike_fit_run(call, N, K, cap)
+    while true
+        times = zeros(Int64, cap, N); amp = zeros(Float64, cap, N); rss = zeros(Float64, cap, N)
+        energy = zeros(Float64, cap, N); nused = zeros(Int32, cap, N); counts = zeros(Int64, N)
+        summary = zeros(Float64, 8 + 3 * (K - 1), N)
+        GC.@preserve times amp rss energy nused counts summary begin
+            check(call(Ref(CSpikeFitOut(pointer(times), pointer(amp), pointer(rss), pointer(energy), pointer(nused), cap,
+                                        pointer(counts), pointer(summary)))))
+        end
+        if maximum(counts) <= cap
+            return [(times=times[1:counts[a], a], amp=amp[1:counts[a], a], rss=rss[1:counts[a], a],
+                     energy=energy[1:counts[a], a], nused=nused[1:counts[a], a], summary=summary[:, a]) for a in 1:N]
+        end
+        cap = maximum(counts)
+    end
+end
+
+"""
+    spike_fit(y, x, lA, μ[, first, μtrack]) -> one (times, amp, rss, energy, nused, summary) per template
+
+Per-spike amplitude and residual of the path `x` of `y` (`hmmsort_spike_fit`; an extension, INTEGRATION.md "Spike fit"):
+for every spike `extract_spiketimes` reports, the least-squares amplitude of its template on the samples under it once
+the other templates the path says are active are taken out, the residual at unit amplitude and the window's energy;
+`summary` holds the per-template sums (include/hmmsort.h).  `first`, `μtrack`: the model track of `fit_adaptive`.
+`spike_fit_device` takes a plan and resident buffers of the plan's length.
+"""
+function spike_fit(y::Vector{T}, x::Vector{Int16}, lA::StateMatrix, μ::Array{Float64,2},
+                   first::Vector{Int64}=Int64[], μtrack::Array{Float64,3}=zeros(Float64, 0, 0, 0)) where T <: Union{Float64,Int16}
+    K = size(μ, 1)
+    GC.@preserve y x μ first μtrack begin
+        _spike_fit_run(lA.N, K, max(1, length(x) ÷ 8)) do out
+            ccall((:hmmsort_spike_fit, lib), Cint,
+                (Ptr{Cvoid}, Cint, Int64, Ptr{Int16}, Ptr{Int16}, Int64, Int64, Ptr{Float64}, Int64, Int64, Ptr{Int64},
+                 Ptr{Float64}, Ref{CSpikeFitOut}),
+                y, T === Int16 ? HMMSORT_SAMPLES_I16 : HMMSORT_SAMPLES_F64, length(y), x, lA.states, lA.N, lA.nstates, μ, K,
+                length(first), first, μtrack, out)
+        end
+    end
+end
+
+"`spike_fit` of a signal and path in device memory under the plan's current model (`hmmsort_plan_spike_fit`); synchronises `stream`"
+function spike_fit_device(plan::Ptr{Cvoid}, d_y::Ptr{Float64}, d_x::Ptr{Int16}, n::Integer, N::Integer, K::Integer,
+                          first::Vector{Int64}=Int64[], μtrack::Array{Float64,3}=zeros(Float64, 0, 0, 0);
+                          stream::Ptr{Cvoid}=C_NULL)
+    GC.@preserve first μtrack begin
+        _spike_fit_run(N, K, max(1, n ÷ 8)) do out
+            ccall((:hmmsort_plan_spike_fit, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Int16}, Int64, Ptr{Int64}, Ptr{Float64}, Ref{CSpikeFitOut}, Ptr{Cvoid}),
+                plan, d_y, d_x, length(first), first, μtrack, out, stream)
+        end
+    end
+end
+
 function reconstruct_signal(x::Array{T,1}, lA::StateMatrix, μ::Array{Float64,2}, σ::Float64) where T <: Integer
     xs = T === Int16 ? x : Int16.(x)
     Y2 = zeros(Float64, length(xs))
