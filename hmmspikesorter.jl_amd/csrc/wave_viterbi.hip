@@ -478,10 +478,20 @@ __device__ __forceinline__ int vit_final_state(const WaveGeom &g, const WaveCons
 // the exact resolver, wave_ties.hip).
 // Two kernels.  kw_backtrace (register rows): a lane holds its whole tile row (one or two words per sample) in
 // registers through the tile's unrolled walk -- 300 registers per lane, one wave per SIMD, the fastest when nothing
-// else runs.  kw_backtrace_light: tiles of 64 / 32 / 16 samples, and a lane reads its row from LDS in chunks of 8 / 4
-// samples (all words of a chunk's samples, so the reads do not depend on the walk) and puts the decoded ids into
-// the output tile chunk by chunk: at most 80 registers and 32 KB of LDS, so that it fits on a SIMD beside two
-// waves of the backward sweep (decode + E-step in one call).  Same integer logic, same x, bstate and tie counters.
+// else runs.  kw_backtrace_light: tiles of 64 / 32 / 16 samples in LDS, at most 80 registers and 32 KB of LDS, so
+// that it fits on a SIMD beside two waves of the backward sweep (decode + E-step in one call), where a wave gets
+// one issue slot in three and the length of the walk's dependent chain is what it costs.  Its walk therefore visits
+// DECISIONS, not samples (HS_BT_EVENTS): the path only changes at junctions, so
+//   * inside a ring (rem > 0) nothing is read: the next rem samples are id-1, id-2, ..., one jump;
+//   * in the silent state every sample reads entry 0 and almost always finds "silent" again: the walk needs the
+//     nearest earlier sample whose entry 0 names a ring, the highest set bit of a row mask (one ballot per row of
+//     the tile, all lanes), and the flagged decisions it skips are a popcount of a second mask;
+//   * only a ring's first state and the silent sample that leaves into a ring read their entry from the tile.
+// A lane's walk through a tile is then a handful of passes (a 704-sample walk at the headline rates meets about
+// five spikes) and leaves the ids as ramps, which all lanes expand while x is stored.  HS_BT_EVENTS = 0 is the
+// per-sample walk: a lane reads its row from LDS in chunks of 8 / 4 samples and puts the decoded ids into an output
+// tile.  Same integer decisions in all three: same x, bstate and tie counters (tests/backtrace_model.py states the
+// two light walks; tests/test_gpu_backtrace_events.py compares them with the register rows).
 // Start of the walks that begin at a channel's last sample.  The workgroups that hold such a walk find the final
 // state themselves (vit_final_state: vend is final by now); the one that owns the last segment records it and its
 // near-tie flag.  (wave-uniform branch)
@@ -517,10 +527,21 @@ template <int N> constexpr int bt_tile()
 // dynamic LDS of a light backtrace workgroup: the psi tile (rows padded by four words: a row starts on 16 bytes,
 // and both the 128-bit staging writes and the 128-bit chunk reads of the walk are conflict-free per quarter wave)
 // and the output tile (rows padded by one word)
+#ifndef HS_BT_EVENTS
+#define HS_BT_EVENTS 1    // the light backtrace walks junction decisions (0: one step per sample, the output tile in LDS)
+#endif
+// ramps a segment row can hold in one tile: a ring cut by the tile's newest sample, whole rings, a ring cut by its
+// oldest sample; rings have at least 8 states (wave_supported)
+template <int N> constexpr int bt_ramps() { return bt_tile<N>() / 8 + 2; }
 template <int N, int SPW> constexpr size_t bt_lds_bytes()
 {
     constexpr int PW = wpsi_words_c(N), TS = bt_tile<N>();
+#if HS_BT_EVENTS
+    // the output tile is not kept: the ramps of a row (a count and bt_ramps words) are expanded as x is stored
+    return sizeof(uint32_t) * (size_t)(PW * SPW * (TS + 4) + SPW * (bt_ramps<N>() + 1));
+#else
     return sizeof(uint32_t) * (size_t)(PW * SPW * (TS + 4) + SPW * (TS / 2 + 1));
+#endif
 }
 
 // SPW: segments (tile rows) per workgroup, 64, 32 or 16.  With SPW < 64 the lanes < SPW walk, all 64 lanes stage
@@ -540,21 +561,28 @@ __device__ __forceinline__ void backtrace_light_body(const WaveGeom &g, const Wa
     constexpr int XW = TS / 2;              // decoded ids leave as pairs (two int16 per word)
     constexpr int XRI = 64 / XW;            // rows per store instruction
     constexpr int CH = PW == 1 ? 8 : 4;     // samples per register chunk
-    constexpr int NCH = TS / CH;
+    [[maybe_unused]] constexpr int NCH = TS / CH;
     constexpr int TSP = TS + 4;             // tile row stride in words
     constexpr int LPR = TS / 4;             // lanes per row of a 16-byte load instruction
     constexpr int RPW = 64 / LPR;           // segment rows per 16-byte load instruction (TS / 4 instructions per plane)
     constexpr int WU = SPW / RPW < 4 ? SPW / RPW : 4;   // 16-byte loads in flight while a tile is staged (up to 16 registers, dead in the walk)
     constexpr int SU = 2;                   // row loads in flight on the dword path (planes off 16 bytes)
-    constexpr int XU = PW == 4 ? 2 : 4;     // row stores in flight while the output tile leaves (four spill at PW = 4)
+    [[maybe_unused]] constexpr int XU = PW == 4 ? 2 : 4;     // row stores in flight while the output tile leaves (four spill at PW = 4)
     static_assert(CH % 4 == 0 && TS % CH == 0, "chunks are whole 16-byte groups");
     static_assert(SPW == 64 || SPW == 32 || SPW == 16, "segments per workgroup");
     static_assert(WU >= 1 && SPW % (RPW * WU) == 0, "whole batches of wide loads");
     static_assert(SPW % RPI == 0 && SPW % XRI == 0, "whole row instructions");
     static_assert(bt_lds_bytes<N, SPW>() <= 32 * 1024, "LDS budget");
-    extern __shared__ __align__(16) uint32_t lds_bt[];    // tile[PW][SPW][TS + 4] | xt[SPW][XW + 1]
+    extern __shared__ __align__(16) uint32_t lds_bt[];    // tile[PW][SPW][TS + 4] | xt[SPW][XW + 1] (events: ramp[SPW][ND + 1])
     uint32_t (*tile)[SPW][TSP] = reinterpret_cast<uint32_t (*)[SPW][TSP]>(lds_bt);
+#if HS_BT_EVENTS
+    constexpr int ND = bt_ramps<N>();       // ramps per row and tile (odd row stride: conflict-free)
+    static_assert(TS <= 64 && ND * 8 >= TS + 16 && (ND + 1) % 2 == 1, "ramp capacity");
+    uint32_t (*ramp)[ND + 1] = reinterpret_cast<uint32_t (*)[ND + 1]>(lds_bt + PW * SPW * TSP);
+    using Mask = std::conditional_t<TS == 64, uint64_t, uint32_t>;   // one bit per sample of a tile row
+#else
     uint32_t (*xt)[XW + 1] = reinterpret_cast<uint32_t (*)[XW + 1]>(lds_bt + PW * SPW * TSP);
+#endif
     const int lane = threadIdx.x, ch = blockIdx.y;
     const int L = g.L, Bb = g.Bb, Hb = g.Hb;
     const int64_t T = g.T;
@@ -578,6 +606,80 @@ __device__ __forceinline__ void backtrace_light_body(const WaveGeom &g, const Wa
     bt_start<N>(g, cst, ysum, vend, final_state, tie_cnt, ch, lane, active && te == T, id, rem, wi, sh);
     int nflag = 0, bs = 0;
     const int lr = lane / TS, lc = lane % TS;
+#if HS_BT_EVENTS
+    // One tile of the walk, newest sample first, by EVENTS: u is the next sample the lane decides (relative to
+    // its segment; te_rel - 1 before the walk has begun, so a lane enters the loop in the tile that holds its
+    // start), and every pass of the loop takes it past one stretch of the path:
+    //   silent state -- down to the nearest sample whose entry 0 names a ring (pm: one bit per sample of the
+    //     tile row, set where entry 0 has a predecessor != 0), or out of the tile; the flagged decisions of the
+    //     stretch are a popcount of fm (entry 0's flag bits) over it;
+    //   inside a ring -- the rem samples that need no decision and, when it is still in the tile, the ring's
+    //     first state, whose entry (wi, sh) is read from the tile and decides the junction.  Such a stretch is
+    //     one RAMP of ids: (first sample, last sample, id at the last sample), 6 + 6 + 20 bits, left in LDS for
+    //     the store phase when `emit` (the tile is inside the owned segments).  Silence leaves nothing.
+    // A pass lowers u by at least 1.  FAST: every lane of the wave is inside its walk for the whole tile and
+    // (OWN) inside / (not OWN) behind its own segment, so no per-lane time marks: the others apply the rules of
+    // the per-sample walk (no step at u < t1, flags counted in [t2, hi_rel), bs = the id at hi_rel).
+    constexpr uint32_t PJM = (1u << (EB - 1)) - 1u;
+    int u = te_rel - 1;
+    auto low = [](int p) -> Mask { return (Mask)(((Mask)2 << p) - 1); };   // bits 0..p (p < TS)
+    auto msb = [](Mask m) -> int { return TS == 64 ? 63 - __clzll((long long)m) : 31 - __clz((int)m); };
+    auto popc = [](Mask m) -> int { return TS == 64 ? __popcll((unsigned long long)m) : __popc((unsigned)m); };
+    auto walk = [&](int u0, auto fast_tag, auto own_tag, bool emit, Mask pm, Mask fm) {
+        constexpr bool FAST = decltype(fast_tag)::value, OWN = decltype(own_tag)::value;
+        const uint32_t *row0 = &tile[0][lane][0];
+        int nd = 0;
+        while (u >= u0) {
+            const int p = u - u0;
+            if (id == 1) {   // silent (rem = 0, entry 0)
+                const Mask below = pm & low(p);
+                int j = below ? msb(below) : -1;
+                if (!FAST && u0 + j < t1) j = -1;        // the step at t = 0 has no predecessor
+                const int lo = j < 0 ? 0 : j;            // the stretch lo..p is silent; its decisions read entry 0
+                if (FAST ? OWN : true) {
+                    int a = lo, b = p;
+                    if (!FAST) {
+                        a = a > t2 - u0 ? a : t2 - u0;
+                        b = b < hi_rel - 1 - u0 ? b : hi_rel - 1 - u0;
+                    }
+                    if (a <= b) nflag += popc(fm & low(b) & (Mask)(~(Mask)0 << a));
+                }
+                if (!FAST) {
+                    const int h = hi_rel - u0;
+                    bs = (h >= lo && h <= p) ? 1 : bs;
+                }
+                if (j < 0) { u = u0 - 1; break; }
+                const int pj = (int)(row0[j] & PJM);     // != 0: the last state of ring pj - 1
+                id = 1 + pj * L; rem = L - 1;
+                wi = pj / EPW; sh = (pj % EPW) * EB;
+                u = u0 + j - 1;
+            } else {
+                const int s = rem < p + 1 ? rem : p + 1;     // samples without a decision
+                const bool junc = s <= p;                     // the ring's first state is in the tile
+                const int n = s + (junc ? 1 : 0);
+                if (emit) ramp[lane][1 + nd++] = (uint32_t)(p - n + 1) | ((uint32_t)p << 6) | ((uint32_t)id << 12);
+                if (!FAST) {
+                    const int d = u - hi_rel;
+                    bs = (d >= 0 && d < n) ? id - d : bs;
+                }
+                if (junc) {
+                    const int uj = u - s;
+                    if (FAST || uj >= t1) {
+                        const uint32_t ent = row0[wi * (SPW * TSP) + (uj - u0)] >> sh;
+                        const int pj = (int)(ent & PJM);
+                        if (FAST ? OWN : (uj < hi_rel && uj >= t2)) nflag += (int)((ent >> (EB - 1)) & 1u);
+                        id = 1 + pj * L; rem = pj ? L - 1 : 0;
+                        wi = pj / EPW; sh = (pj % EPW) * EB;
+                    }
+                } else {
+                    id -= s; rem -= s;
+                }
+                u -= n;
+            }
+        }
+        if (emit) ramp[lane][0] = (uint32_t)nd;
+    };
+#else
     // one tile of the walk, newest sample first.  FAST: every lane of the wave is inside its walk for the
     // whole tile and (OWN) inside / (not OWN) behind its own segment, so no per-lane time predicates.
     // The decoded ids of a chunk go to the output tile when `emit` (the tile is inside the owned segments).
@@ -636,6 +738,7 @@ __device__ __forceinline__ void backtrace_light_body(const WaveGeom &g, const Wa
             }
         }
     };
+#endif
     const int nq = (Bb + Hb) / TS;
     for (int q = nq - 1; q >= 0; q--) {
         // stage psi rows: row r = segment sg0 + r, samples s_lo(r) + TS q + (0..TS-1).  Wave-uniform tile origin +
@@ -698,20 +801,68 @@ __device__ __forceinline__ void backtrace_light_body(const WaveGeom &g, const Wa
         const bool lane_fast = u0 >= t1 && u1 <= te_rel &&
                                (own_tile ? (u1 <= hi_rel && u0 >= t2) : (u0 > hi_rel));
         const bool fast = __all(lane_fast || !walker);
+#if HS_BT_EVENTS
+        // the masks of the tile's rows, all lanes: lanes = samples of RPI rows, one LDS read and one compare per
+        // ballot; the lane that walks a row keeps that row's bits (registers).  Rows that do not exist and samples
+        // past T are staged as zeros: silent -> silent, not flagged.  Flags are counted in owned tiles only.
+        Mask pm, fm;
+        {
+            unsigned long long mp = 0, mf = 0;
+#pragma unroll 4
+            for (int it = 0; it < SPW / RPI; it++) {
+                const uint32_t w0 = tile[0][it * RPI + lr][lc];
+                const bool mine = lane / RPI == it;
+                const unsigned long long bp = __ballot((w0 & PJM) != 0u);
+                mp = mine ? bp : mp;
+                if (own_tile) {
+                    const unsigned long long bf = __ballot(((w0 >> (EB - 1)) & 1u) != 0u);
+                    mf = mine ? bf : mf;
+                }
+            }
+            constexpr Mask row_bits = (Mask)(~(Mask)0 >> (8 * sizeof(Mask) - TS));
+            const int shf = (lane % RPI) * TS;
+            pm = (Mask)(mp >> shf) & row_bits;
+            fm = (Mask)(mf >> shf) & row_bits;
+        }
+        if (walker) {   // (divergent: no barrier and no cross-lane move inside a walk)
+            if (fast && own_tile) walk(u0, std::true_type(), std::true_type(), true, pm, fm);
+            else if (fast) walk(u0, std::true_type(), std::false_type(), false, pm, fm);
+            else walk(u0, std::false_type(), std::false_type(), own_tile, pm, fm);
+        }
+#else
         if (walker) {   // (no barrier and no cross-lane move inside a walk)
             if (fast && own_tile) walk(q, std::true_type(), std::true_type(), true);
             else if (fast) walk(q, std::true_type(), std::false_type(), false);
             else walk(q, std::false_type(), std::false_type(), own_tile);
         }
+#endif
         if (own_tile) {  // owned rows: write x out, coalesced
             __syncthreads();
             const int xrw = lane / XW, xcw = lane % XW;
             int16_t *xb = xc + (lim > 0 ? tb : 0);   // wave-uniform tile origin + 32-bit lane offsets, as the loads
+#if HS_BT_EVENTS
+#pragma unroll 2
+#else
 #pragma unroll XU
+#endif
             for (int rr = 0; rr < SPW; rr += XRI) {
                 const int r = rr + xrw, o = r * Bb + 2 * xcw;
                 if (r < nrow && o < lim) {
+#if HS_BT_EVENTS
+                    // the pair of samples 2 xcw, 2 xcw + 1 of row r: silent unless one of the row's ramps covers it
+                    const uint32_t *rp = ramp[r];
+                    const int nr = (int)rp[0], c0 = 2 * xcw;
+                    uint32_t v = 0x00010001u;
+                    for (int k = 1; k <= nr; k++) {
+                        const uint32_t d = rp[k];
+                        const int f = (int)(d & 63u), l = (int)((d >> 6) & 63u);
+                        const uint32_t top = (d >> 12) - (uint32_t)l;      // id(c) = top + c for f <= c <= l
+                        if (c0 >= f && c0 <= l) v = (v & 0xffff0000u) | (top + (uint32_t)c0);
+                        if (c0 + 1 >= f && c0 + 1 <= l) v = (v & 0x0000ffffu) | ((top + (uint32_t)c0 + 1u) << 16);
+                    }
+#else
                     const uint32_t v = xt[r][xcw];
+#endif
                     if (o + 1 < lim && xal) *reinterpret_cast<uint32_t *>(xb + o) = v;
                     else {
                         xb[o] = (int16_t)(v & 0xffffu);
