@@ -78,7 +78,19 @@ class SpikeFitOut(C.Structure):
                 ("counts", _vp), ("summary", _vp)]
 
 
+class CcgOpt(C.Structure):
+    """struct hmmsort_ccg_opt: bin width, bins on each side of lag 0, refractory period, coincidence window (samples)"""
+    _fields_ = [("bin", _i64), ("half_bins", _i64), ("refractory", _i64), ("coincidence", _i64)]
+
+
+class CcgOut(C.Structure):
+    """struct hmmsort_ccg_out: host int64 arrays hmmsort_correlograms fills ([U][U][2H], [U], [U][U], [U]; n is
+    required)"""
+    _fields_ = [("ccg", _vp), ("viol", _vp), ("coinc", _vp), ("n", _vp)]
+
+
 SEED_MAX_K, SEED_MAX_N, SEED_MAX_R = 1025, 16, 1024
+CCG_MAX_UNITS, CCG_MAX_HALF_BINS = 4096, 2048
 
 # name -> (restype, argtypes); every symbol include/hmmsort.h declares
 SIGNATURES = {
@@ -156,6 +168,8 @@ SIGNATURES = {
     "hmmsort_spike_fit": (_int, [_vp, _int, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp,
                                  C.POINTER(SpikeFitOut)]),
     "hmmsort_plan_spike_fit": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, C.POINTER(SpikeFitOut), _vp]),
+    "hmmsort_correlograms": (_int, [_i64, C.POINTER(_vp), _vp, C.POINTER(CcgOpt), C.POINTER(CcgOut)]),
+    "hmmsort_plan_correlograms": (_int, [_vp, _vp, C.POINTER(CcgOpt), C.POINTER(CcgOut), _vp]),
     "hmmsort_plan_profile": (_int, [_vp, _int]),
     "hmmsort_plan_profile_read": (_int, [_vp, _vp, C.c_char_p, _i64, C.POINTER(_f64), _pi64, _i64,
                                          _pi64]),

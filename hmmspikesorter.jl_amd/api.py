@@ -889,6 +889,63 @@ def unit_quality(model, track=None):
     return [quality_from_summary(f.summary, tm.state_matrix.K, tm.sigma) for f in spike_fit(model, track)]
 
 
+@dataclass
+class Correlograms:
+    """What hmmsort_correlograms counts for U units (definitions in include/hmmsort.h); all integers."""
+    counts: np.ndarray          # [U, U, 2H]: counts[u, v, k] pairs with lag t_v - t_u in [lags[k], lags[k] + bin)
+    lags: np.ndarray            # [2H]: left bin edges in samples, (k - H) * bin
+    isi_violations: np.ndarray  # [U]: consecutive intervals shorter than `refractory`
+    coincidence: np.ndarray     # [U, U]: spikes of u with a spike of v within +-`coincidence` samples
+    n: np.ndarray               # [U]: spikes per unit
+
+
+def _ccg_run(call, U, bin, half_bins, refractory, coincidence):
+    """call(byref(hmmsort_ccg_opt), byref(hmmsort_ccg_out)) -> rc into a Correlograms of U units"""
+    b, H = int(bin), int(half_bins)
+    # sizes the library refuses get token arrays: it checks before it writes, and its message says what is wrong
+    ok = 1 <= U <= _lib.CCG_MAX_UNITS and 1 <= H <= _lib.CCG_MAX_HALF_BINS and U * U * 2 * H <= 1 << 28
+    Ua, Ha = (U, H) if ok else (1, 1)
+    ccg, coinc = np.zeros((Ua, Ua, 2 * Ha), dtype=np.int64), np.zeros((Ua, Ua), dtype=np.int64)
+    viol, n = np.zeros(Ua, dtype=np.int64), np.zeros(Ua, dtype=np.int64)
+    opt = _lib.CcgOpt(b, H, int(refractory), int(coincidence))
+    out = _lib.CcgOut(ccg.ctypes.data, viol.ctypes.data, coinc.ctypes.data, n.ctypes.data)
+    check(call(C.byref(opt), C.byref(out)))
+    return Correlograms(ccg, (np.arange(2 * H, dtype=np.int64) - H) * b, viol, coinc, n)
+
+
+def correlograms(models_or_time_lists, bin=30, half_bins=50, refractory=30, coincidence=2):
+    """correlograms(units; bin, half_bins, refractory, coincidence) -> Correlograms (an extension, INTEGRATION.md
+    "Correlograms"): auto- and cross-correlograms of the spike trains, refractory violations per unit and, per ordered
+    pair, how many spikes of one unit the other also has.  `units` is a list whose entries are spike-time arrays
+    (1-based samples, strictly ascending) or HMMSpikingModels; a model contributes its extract_spiketimes lists in
+    order, so a list of per-channel models (fit_channels) gives units channel by channel.  All options in samples."""
+    lists = []
+    for item in models_or_time_lists:
+        if isinstance(item, HMMSpikingModel):
+            lists.extend(extract_spiketimes(item))
+        else:
+            lists.append(item)
+    lists = [np.ascontiguousarray(t, dtype=np.int64).ravel() for t in lists]
+    U = len(lists)
+    ptrs = (C.c_void_p * max(U, 1))(*[t.ctypes.data if len(t) else None for t in lists])
+    cnt = np.array([len(t) for t in lists] + [0] * (U == 0), dtype=np.int64)
+    return _ccg_run(lambda opt, out: lib().hmmsort_correlograms(U, ptrs, ptr(cnt), opt, out), U, bin, half_bins,
+                    refractory, coincidence)
+
+
+def duplicate_units(cg, min_fraction=0.5):
+    """duplicate_units(cg::Correlograms; min_fraction) -> [(u, v, fraction)] for u != v with fraction =
+    coincidence[u, v] / n[u] >= min_fraction, in ascending (u, v): v has that share of u's spikes too.  A neuron sorted
+    twice shows up in both directions; a unit without spikes is in no pair.  Host code."""
+    out = []
+    n = np.asarray(cg.n)
+    for u in range(len(n)):
+        for v in range(len(n)):
+            if u != v and n[u] > 0 and cg.coincidence[u, v] >= min_fraction * n[u]:
+                out.append((u, v, float(cg.coincidence[u, v]) / float(n[u])))
+    return out
+
+
 def get_energy(waveforms, cinv):
     """get_energy(waveforms::Array{Float64,2}, cinv::Float64) -> ee   utils.jl:112-124: per template (column) the sum
     over rows j ascending of w*cinv*w, folded from 0.0 in the reference's operation order.  Host code."""

@@ -337,6 +337,13 @@ int dev_spike_fit(const double *d_y, const int16_t *d_x, int64_t T, const int16_
                   int64_t dcap, const int64_t *counts, const int32_t *qv, double *d_amp, double *d_rss,
                   double *d_energy, int32_t *d_nused, int32_t *d_chunk, double *d_part, double *d_summary,
                   hipStream_t st);
+// correlograms (correlogram.hip; rules in include/hmmsort.h): ccg_check is what both entry points refuse about U, the
+// options and the output record before any GPU work.  dev_correlograms takes the U lists concatenated in device memory
+// (d_times, offs[u] .. offs[u + 1] with offs a host array of U + 1 ascending entries; every list strictly ascending),
+// fills the caller's host arrays and synchronises st.  Nothing beyond offs[U] entries of d_times is read.
+int ccg_check(const char *who, int64_t U, const hmmsort_ccg_opt *opt, const hmmsort_ccg_out *out);
+int dev_correlograms(int64_t U, const int64_t *d_times, const int64_t *offs, const hmmsort_ccg_opt *opt,
+                     const hmmsort_ccg_out *out, hipStream_t st);
 
 }  // namespace hmmsort
 

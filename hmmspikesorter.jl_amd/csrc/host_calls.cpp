@@ -1270,4 +1270,37 @@ int hmmsort_seed_templates(const void *y, int sample_type, int64_t T, int64_t N,
     return dev_seed_templates(dy.as<double>(), T, N, K, p, out, nullptr);
 }
 
+// Correlograms of host lists (correlogram.hip).  No plan and no cached slot: the lists go up once, concatenated.
+int hmmsort_correlograms(int64_t U, const int64_t *const *times, const int64_t *counts, const hmmsort_ccg_opt *opt,
+                         hmmsort_ccg_out *out)
+{
+    HS_CHECK(times && counts, HMMSORT_EINVAL, "correlograms: null argument (times and counts are required)");
+    int rc = ccg_check("correlograms", U, opt, out);
+    if (rc) return rc;
+    std::vector<int64_t> offs((size_t)U + 1, 0);
+    for (int64_t u = 0; u < U; u++) {
+        HS_CHECK(counts[u] >= 0, HMMSORT_EINVAL, "correlograms: unit %lld has a count of %lld", (long long)u,
+                 (long long)counts[u]);
+        HS_CHECK(counts[u] == 0 || times[u], HMMSORT_EINVAL, "correlograms: unit %lld has a null list of %lld times",
+                 (long long)u, (long long)counts[u]);
+        for (int64_t i = 0; i < counts[u]; i++) {
+            const int64_t t = times[u][i];
+            HS_CHECK(t >= 1 && t <= (1ll << 40), HMMSORT_EINVAL, "correlograms: unit %lld, position %lld: time %lld "
+                     "outside 1..2^40", (long long)u, (long long)i, (long long)t);
+            HS_CHECK(i == 0 || t > times[u][i - 1], HMMSORT_EINVAL, "correlograms: unit %lld, position %lld: time %lld "
+                     "after %lld (a list must be strictly ascending)", (long long)u, (long long)i, (long long)t,
+                     (long long)times[u][i - 1]);
+        }
+        offs[u + 1] = offs[u] + counts[u];
+    }
+    if ((rc = need_device())) return rc;
+    DevBuf dt;
+    if ((rc = dt.alloc((size_t)offs[U] * sizeof(int64_t)))) return rc;
+    for (int64_t u = 0; u < U; u++)
+        if (counts[u] > 0)
+            HS_HIP(hipMemcpy(dt.as<int64_t>() + offs[u], times[u], (size_t)counts[u] * sizeof(int64_t),
+                             hipMemcpyHostToDevice));
+    return dev_correlograms(U, dt.as<int64_t>(), offs.data(), opt, out, nullptr);
+}
+
 }  // extern "C"

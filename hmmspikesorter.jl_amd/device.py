@@ -261,6 +261,16 @@ class Plan:
                              nC, self.N, self.K, max(1, self.T // 8))
         return out if hasattr(self, "C") else out[0]
 
+    def correlograms(self, d_x, bin=30, half_bins=50, refractory=30, coincidence=2, stream=0):
+        """api.Correlograms of the events extract_spiketimes reports on the resident path(s) d_x under the plan's
+        current model (hmmsort_plan_correlograms): units are u = channel * N + template, pairs across the channels
+        of a batched plan included.  The events are compacted on the device and stay there; only the counts cross."""
+        from .api import _ccg_run
+        U = getattr(self, "C", 1) * self.N
+        return _ccg_run(lambda opt, out: lib().hmmsort_plan_correlograms(self._h, _dptr(d_x), opt, out,
+                                                                         C.c_void_p(stream)),
+                        U, bin, half_bins, refractory, coincidence)
+
     def expected_counts(self, stream=0):
         """expected number of spikes per template, sum_t onset[a, t] ([C][N]; [N] for a single-channel plan)"""
         nC = getattr(self, "C", 1)

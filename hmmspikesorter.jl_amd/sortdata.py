@@ -71,7 +71,8 @@ def _chunk_confidence(templates, dataf, ml_seq, chunksize, jitter):
 
 
 def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_templates=4,
-              chunksize=100_000, confidence=False, jitter=2, refine_steps=0, adapt_halflife=None, quality=False):
+              chunksize=100_000, confidence=False, jitter=2, refine_steps=0, adapt_halflife=None, quality=False,
+              correlograms=None):
     """sort_data(inputfile, datafile, outputfile; dosave, max_templates)   hmmsort.jl:36-104.
 
     Returns the reference's output dictionary; {} when there are more templates than
@@ -102,7 +103,11 @@ def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_temp
     `quality=True` (an extension; default off, output unchanged) adds "spiketimes" (when `confidence` has not already),
     "amplitude" and "residual" (per template and spike: api.spike_fit's amp and rss on the whole recording and the
     stitched path) and "unit_quality" (per-template arrays of api.unit_quality's figures).  With `adapt_halflife`
-    every spike is measured against the templates its chunk was decoded with."""
+    every spike is measured against the templates its chunk was decoded with.
+
+    `correlograms=True` or a dict of api.correlograms' options (an extension; default None, output unchanged) adds
+    "ccg" (templates x templates x 2 half_bins counts of the channel's templates on the stitched path), "ccg_lags"
+    (left bin edges in samples) and "isi_violations" (per template)."""
     spike_forms = np.asarray(spike_forms, dtype=np.float64)
     nstates, _nchannels, ntemplates = spike_forms.shape
     pp = np.atleast_1d(np.asarray(p, dtype=np.float64))
@@ -156,6 +161,9 @@ def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_temp
                                for k in ("n", "n_full", "mean_amp", "sd_amp", "sd_expected", "chi2", "energy")}
         out["unit_quality"]["waveform"] = np.stack([q.waveform for q in uq], axis=1)
         out["unit_quality"]["waveform_sd"] = np.stack([q.waveform_sd for q in uq], axis=1)
+    if correlograms is not None and correlograms is not False:
+        cg = api.correlograms([modelf], **({} if correlograms is True else dict(correlograms)))
+        out["ccg"], out["ccg_lags"], out["isi_violations"] = cg.counts, cg.lags, cg.isi_violations
     if dosave and outputfile is not None:
         from scipy.io import savemat
         savemat(outputfile, out)                                              # MAT.matwrite :100

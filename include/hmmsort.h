@@ -689,6 +689,48 @@ int hmmsort_seed_templates(const void *y, int sample_type, int64_t T, int64_t N,
 int hmmsort_seed_templates_device(const double *d_y, int64_t T, int64_t N, int64_t K, const hmmsort_seed_opt *opt,
                                   hmmsort_seed_out *out, void *stream);
 
+/* Correlograms, refractory violations and coincident spikes of sorted units (an extension): what the
+ * spike trains themselves say, beside the per-spike fit above -- the auto-correlogram and ISI violations of a unit, the
+ * cross-correlogram of two units, and the share of a unit's spikes another unit also has (a neuron seen on two
+ * electrodes comes out of a per-channel sort as two units).  Integers only: the result is a fixed function of the input.
+ *   units     u = 0..U-1; unit u has n_u >= 0 spike times t_u[0..n_u), 1-based samples, strictly ascending, each in
+ *             1..2^40.
+ *   options   (b, H, r, c) = (bin, half_bins, refractory, coincidence), all in samples.
+ *   ccg       [U][U][2H] int64: ccg[u][v][k] counts the pairs (i, j) with (u, i) != (v, j), d = t_v[j] - t_u[i],
+ *             -H b <= d < H b and k = floor(d / b) + H.  Bin edges are at multiples of b and every bin is half open;
+ *             d = 0 between different units lands in bin H; u == v gives the auto-correlogram without the self pair.
+ *   viol      [U]: viol[u] = #{ i >= 1 : t_u[i] - t_u[i-1] < r }, consecutive intervals; r = 0 gives 0.
+ *   coinc     [U][U]: coinc[u][v] = #{ i : there is j with (v, j) != (u, i) and |t_v[j] - t_u[i]| <= c }; each spike of
+ *             u is counted once however many partners it has, so coinc[u][v] / n_u is the share of u's spikes that v
+ *             also has.
+ *   n         [U]: n[u] = n_u.
+ * Outputs are host arrays; any of them except n may be NULL.
+ * Refused before any GPU work, HMMSORT_EINVAL (the message names unit and position where one applies): a null required
+ * argument, U outside 1..4096, b < 1, H outside 1..2048, H b >= 2^31, r < 0 or c < 0, a negative count, a time outside
+ * 1..2^40, a list that is not strictly ascending.  HMMSORT_EUNSUP, naming the number of entries: U U 2H > 2^28.
+ * hmmsort_correlograms: host lists, times[u] a host pointer (may be NULL when counts[u] == 0) and counts[u] its
+ * length; uploads once, no plan is involved.
+ * hmmsort_plan_correlograms: the resident path(s) d_x of a plan ([C][T] for a batched plan).  Units are u = ch N + a;
+ * the events are exactly those of hmmsort_plan_extract_spiketimes under the plan's current model, compacted on the
+ * device, and never come to the host -- only the counts do.  Pairs across channels are included.  Any engine.
+ * Synchronises the stream.  Channels with different models, lengths or devices go through the host form. */
+typedef struct hmmsort_ccg_opt {
+    int64_t bin;          /* b: bin width */
+    int64_t half_bins;    /* H: bins on each side of lag 0 */
+    int64_t refractory;   /* r */
+    int64_t coincidence;  /* c */
+} hmmsort_ccg_opt;
+typedef struct hmmsort_ccg_out {
+    int64_t *ccg;     /* [U][U][2H], may be NULL */
+    int64_t *viol;    /* [U], may be NULL */
+    int64_t *coinc;   /* [U][U], may be NULL */
+    int64_t *n;       /* [U], required */
+} hmmsort_ccg_out;
+int hmmsort_correlograms(int64_t U, const int64_t *const *times, const int64_t *counts, const hmmsort_ccg_opt *opt,
+                         hmmsort_ccg_out *out);
+int hmmsort_plan_correlograms(hmmsort_plan *plan, const int16_t *d_x, const hmmsort_ccg_opt *opt, hmmsort_ccg_out *out,
+                              void *stream);
+
 /* Per-kernel timing of the ring engine with HIP events recorded on the caller's stream (used by
  * bench.py for the roofline line).  hmmsort_plan_profile(plan, 1) switches bracketing on;
  * hmmsort_plan_profile_read synchronises the stream and returns, per kernel name, the total
