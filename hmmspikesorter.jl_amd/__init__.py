@@ -10,7 +10,7 @@ from ._lib import (ENGINE_AUTO, ENGINE_BLOCKED, ENGINE_RING, ENGINE_STRICT, ENGI
 from .api import (Correlograms, HMMSpikeTemplateModel, HMMSpikingModel, ModelTrack, Posteriors, SpikeFit, StateMatrix, UnitQuality,
                   backward, extract_spiketimes, fit, fit_adaptive, fit_channels, fit_step_channels, forward, get_energy,
                   quality_from_summary, spike_fit, unit_quality, correlograms, duplicate_units,
-                  posterior_decode, posteriors, predict, reconstruct_signal, reconstruct_tracked, seed_templates, spike_confidence, train_model, train_step, unroll_mlseq, update,
+                  posterior_decode, posteriors, predict, design_fir, preprocess, reconstruct_signal, reconstruct_tracked, seed_templates, spike_confidence, train_model, train_step, unroll_mlseq, update,
                   viterbi, viterbi_step)
 from .device import Plan, stats_blend, stats_sum
 from .postprocess import (condense_candidates, condense_templates, find_best_overlap, match_templates,
@@ -27,4 +27,4 @@ __all__ = ["StateMatrix", "HMMSpikeTemplateModel", "HMMSpikingModel", "forward",
            "match_templates", "Posteriors", "posteriors", "posterior_decode", "spike_confidence",
            "viterbi_step", "fit_adaptive", "reconstruct_tracked", "ModelTrack", "stats_blend", "seed_templates",
            "learn_templates", "SpikeFit", "UnitQuality", "spike_fit", "unit_quality", "quality_from_summary",
-           "get_energy", "Correlograms", "correlograms", "duplicate_units"]
+           "get_energy", "Correlograms", "correlograms", "duplicate_units", "design_fir", "preprocess"]

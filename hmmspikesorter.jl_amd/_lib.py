@@ -89,7 +89,16 @@ class CcgOut(C.Structure):
     _fields_ = [("ccg", _vp), ("viol", _vp), ("coinc", _vp), ("n", _vp)]
 
 
+class PreOpt(C.Structure):
+    """struct hmmsort_pre_opt: half filter (taps NULL: none), reference mode, group id per channel (NULL: one group)
+    and, in the host form, the rows to return (NULL: all)"""
+    _fields_ = [("taps", _vp), ("half", _i64), ("reference", _int), ("group", _vp), ("keep", _vp), ("nkeep", _i64)]
+
+
 SEED_MAX_K, SEED_MAX_N, SEED_MAX_R = 1025, 16, 1024
+LAYOUT_CHANNEL_MAJOR, LAYOUT_SAMPLE_MAJOR = 0, 1
+REF_NONE, REF_MEDIAN, REF_MEAN = 0, 1, 2
+PRE_MAX_HALF, PRE_MAX_CHANNELS, PRE_MAX_GROUP = 4096, 1024, 64
 CCG_MAX_UNITS, CCG_MAX_HALF_BINS = 4096, 2048
 
 # name -> (restype, argtypes); every symbol include/hmmsort.h declares
@@ -117,6 +126,8 @@ SIGNATURES = {
     "hmmsort_reconstruct_tracked": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
     "hmmsort_chunk_stitch": (_int, [_vp, _i64, _int, _int, _vp, _vp, _vp]),
     "hmmsort_samples_to_f64": (_int, [_vp, C.c_int, _i64, _i64, _vp, _vp]),
+    "hmmsort_preprocess": (_int, [_vp, _int, _int, _i64, _i64, C.POINTER(PreOpt), _vp]),
+    "hmmsort_preprocess_device": (_int, [_vp, _int, _int, _i64, _i64, C.POINTER(PreOpt), _vp, _vp]),
     "hmmsort_seed_templates": (_int, [_vp, _int, _i64, _i64, _i64, C.POINTER(SeedOpt), C.POINTER(SeedOut)]),
     "hmmsort_seed_templates_device": (_int, [_vp, _i64, _i64, _i64, C.POINTER(SeedOpt), C.POINTER(SeedOut), _vp]),
     "hmmsort_forward": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _f64, _vp]),

@@ -381,6 +381,92 @@ def seed_templates(X, N=3, K=60, resolve_overlaps=False, **opts):
                      len(X), N, K, resolve_overlaps, opts)
 
 
+def design_fir(fs, low=None, high=None, ntaps=257):
+    """Linear-phase FIR filter for api.preprocess: the full, odd-length tap vector of a Hamming-windowed sinc scaled
+    to unit gain, scipy.signal.firwin(ntaps, cutoffs, window="hamming", pass_zero=..., fs=fs) restated in numpy.
+    `low` alone: high-pass above `low` Hz (unit gain at the Nyquist frequency); `high` alone: low-pass below `high` Hz
+    (unit gain at 0 Hz); both: band-pass low..high (unit gain at the band centre)."""
+    fs, ntaps = float(fs), int(ntaps)
+    if low is None and high is None:
+        raise ValueError("design_fir: give low (high-pass), high (low-pass) or both (band-pass)")
+    if ntaps < 3 or ntaps % 2 == 0:
+        raise ValueError("design_fir: ntaps = %d must be odd and at least 3" % ntaps)
+    edges = np.array([f for f in (low, high) if f is not None], dtype=np.float64) / (0.5 * fs)
+    if np.any(edges <= 0.0) or np.any(edges >= 1.0) or np.any(np.diff(edges) <= 0.0):
+        raise ValueError("design_fir: cutoffs must lie strictly between 0 and fs / 2 = %g Hz, low below high"
+                         % (0.5 * fs))
+    if low is None:
+        bands = [(0.0, edges[0])]
+    elif high is None:
+        bands = [(edges[0], 1.0)]
+    else:
+        bands = [(edges[0], edges[1])]
+    m = np.arange(ntaps) - 0.5 * (ntaps - 1)
+    h = np.zeros(ntaps)
+    for left, right in bands:
+        h += right * np.sinc(right * m)
+        h -= left * np.sinc(left * m)
+    h *= 0.54 + 0.46 * np.cos(np.linspace(-np.pi, np.pi, ntaps))           # symmetric Hamming window
+    left, right = bands[0]
+    gain_at = 0.0 if left == 0.0 else (1.0 if right == 1.0 else 0.5 * (left + right))
+    return h / np.sum(h * np.cos(np.pi * m * gain_at))
+
+
+_PRE_TYPES = {np.dtype(np.int16): _lib.SAMPLES_I16, np.dtype(np.int32): _lib.SAMPLES_I32,
+              np.dtype(np.float32): _lib.SAMPLES_F32, np.dtype(np.float64): _lib.SAMPLES_F64}
+_PRE_REFS = {None: _lib.REF_NONE, "none": _lib.REF_NONE, "median": _lib.REF_MEDIAN, "mean": _lib.REF_MEAN}
+
+
+def _pre_opt(taps, reference, groups, keep):
+    """struct hmmsort_pre_opt of api.preprocess / device.preprocess and the arrays it points into (keep them alive).
+    `taps` is the full odd-length vector; its second half, centre first, is what goes over."""
+    if reference not in _PRE_REFS:
+        raise ValueError("preprocess: reference must be None, 'median' or 'mean' (got %r)" % (reference,))
+    half = grp = kp = None
+    if taps is not None:
+        h = np.asarray(taps, dtype=np.float64).ravel()
+        if len(h) % 2 == 0:
+            raise ValueError("preprocess: taps must be the full filter of odd length (got %d)" % len(h))
+        half = np.ascontiguousarray(h[len(h) // 2:])
+    if groups is not None:
+        grp = np.ascontiguousarray(groups, dtype=np.int32).ravel()
+    if keep is not None:
+        kp = np.ascontiguousarray(keep, dtype=np.int32).ravel()
+    opt = _lib.PreOpt(None if half is None else half.ctypes.data, 0 if half is None else len(half) - 1,
+                      _PRE_REFS[reference], None if grp is None else grp.ctypes.data,
+                      None if kp is None else kp.ctypes.data, 0 if kp is None else len(kp))
+    return opt, (half, grp, kp)
+
+
+def preprocess(raw, taps=None, reference=None, groups=None, keep=None):
+    """Front end for a raw recording block (hmmsort_preprocess; an extension, INTEGRATION.md "Front end"): a zero-phase
+    FIR filter per channel (`taps`: the full odd-length symmetric vector, e.g. design_fir's; None: no filter), then a
+    common reference per sample (`reference`: None, "median" or "mean") across the channels that share an id in
+    `groups` (one int per channel; negative: filtered only; None: all channels in one group).  Deterministic, and
+    equal bit for bit to tests/preprocess_model.py.
+
+    raw: 1-D, or 2-D of shape (T, C) as the reference's data arrays are; int16, int32, float32 or float64 samples go
+    over as they are (anything else as float64).  A C-contiguous array goes over as sample-major, a Fortran-contiguous
+    one as channel-major; neither is copied.  Returns (C or len(keep), T) float64, row i being channel keep[i]."""
+    raw = np.asarray(raw)
+    if raw.ndim == 1:
+        raw = raw[:, None]
+    if raw.ndim != 2:
+        raise ValueError("preprocess: raw must be 1-D or (T, C), got shape %s" % (raw.shape,))
+    if raw.dtype not in _PRE_TYPES:
+        raw = raw.astype(np.float64)
+    if not (raw.flags.c_contiguous or raw.flags.f_contiguous):
+        raw = np.ascontiguousarray(raw)
+    layout = _lib.LAYOUT_SAMPLE_MAJOR if raw.flags.c_contiguous else _lib.LAYOUT_CHANNEL_MAJOR
+    T, nC = raw.shape
+    opt, alive = _pre_opt(taps, reference, groups, keep)
+    if alive[1] is not None and len(alive[1]) != nC:
+        raise ValueError("preprocess: groups has %d entries for %d channels" % (len(alive[1]), nC))
+    out = np.empty((nC if keep is None else len(alive[2]), T), dtype=np.float64)
+    check(lib().hmmsort_preprocess(ptr(raw), _PRE_TYPES[raw.dtype], layout, nC, T, C.byref(opt), ptr(out)))
+    return out
+
+
 def train_model(X, *args, callback=None, verbose=0, p0=None, rng=None, postprocess="reference",
                 method="baum-welch", init="random", seed_options=None):
     """The three `train_model` methods of baumwelch.jl:

@@ -451,6 +451,44 @@ int hmmsort_samples_to_f64(const void *d_in, int sample_type, int64_t T, int64_t
     return dev_widen(d_in, sample_type, T, stride, d_out, (hipStream_t)stream);
 }
 
+// Front end (preprocess.hip).  No plan and no cached slot.
+int hmmsort_preprocess_device(const void *d_in, int sample_type, int layout, int64_t C, int64_t T,
+                              const hmmsort_pre_opt *opt, double *d_out, void *stream)
+{
+    PrePlan p;
+    int rc = pre_resolve("preprocess_device", d_in, sample_type, layout, C, T, opt, d_out, false, &p);
+    if (rc) return rc;
+    if ((rc = need_device())) return rc;
+    return dev_preprocess(d_in, sample_type, layout, C, T, p, nullptr, d_out, (hipStream_t)stream);
+}
+
+int hmmsort_preprocess(const void *in, int sample_type, int layout, int64_t C, int64_t T, const hmmsort_pre_opt *opt,
+                       double *out)
+{
+    PrePlan p;
+    int rc = pre_resolve("preprocess", in, sample_type, layout, C, T, opt, out, true, &p);
+    if (rc) return rc;
+    if ((rc = need_device())) return rc;
+    const size_t esize = sample_type == HMMSORT_SAMPLES_I16 ? 2 : (sample_type == HMMSORT_SAMPLES_F64 ? 8 : 4);
+    // without a reference only the kept channels are filtered; with one every channel is, and the kept rows return
+    const bool part = !p.keep.empty() && p.reference == HMMSORT_REF_NONE;
+    const int64_t rows = part ? (int64_t)p.keep.size() : C;
+    DevBuf din, dout;
+    if ((rc = din.alloc((size_t)C * T * esize))) return rc;
+    if ((rc = dout.alloc((size_t)rows * T * sizeof(double)))) return rc;
+    HS_HIP(hipMemcpy(din.p, in, (size_t)C * T * esize, hipMemcpyHostToDevice));
+    if ((rc = dev_preprocess(din.p, sample_type, layout, C, T, p, part ? &p.keep : nullptr, dout.as<double>(), nullptr)))
+        return rc;
+    if (p.keep.empty() || part) {
+        HS_HIP(hipMemcpy(out, dout.p, (size_t)rows * T * sizeof(double), hipMemcpyDeviceToHost));
+    } else {
+        for (size_t i = 0; i < p.keep.size(); i++)
+            HS_HIP(hipMemcpy(out + i * T, dout.as<double>() + (int64_t)p.keep[i] * T, (size_t)T * sizeof(double),
+                             hipMemcpyDeviceToHost));
+    }
+    return HMMSORT_OK;
+}
+
 int hmmsort_reconstruct(const int16_t *x, int64_t T, const int16_t *states, int64_t N, int64_t S,
                         const double *mu, int64_t K, double *y_out)
 {

@@ -400,5 +400,20 @@ int seed_resolve(int64_t T, int64_t N, int64_t K, const hmmsort_seed_opt *opt, c
                  SeedParams *p);
 int dev_seed_templates(const double *d_y, int64_t T, int64_t N, int64_t K, const SeedParams &p, hmmsort_seed_out *out,
                        hipStream_t st);
+// front end (preprocess.hip): what both entry points refuse, before any GPU work, and the call resolved: the filter's
+// half (taps null: none), the reference mode, the groups' member channels (ascending; groups in ascending id) and, in
+// the host form, the rows to return.  dev_preprocess filters source channel (*rows)[r] (null: r, all C) into row r of
+// d_out, applies the reference to the groups (members are row numbers) in place and synchronises st.
+struct PrePlan {
+    int64_t half = 0;
+    const double *taps = nullptr;
+    int reference = 0;
+    std::vector<std::vector<int32_t>> groups;
+    std::vector<int32_t> keep;
+};
+int pre_resolve(const char *who, const void *in, int sample_type, int layout, int64_t C, int64_t T,
+                const hmmsort_pre_opt *opt, const double *out, bool host_form, PrePlan *p);
+int dev_preprocess(const void *d_in, int sample_type, int layout, int64_t C, int64_t T, const PrePlan &p,
+                   const std::vector<int32_t> *rows, double *d_out, hipStream_t st);
 void host_slots_trim(size_t keep);   // idle plans of the host-buffer entry points: keep the newest `keep`
 }  // namespace hmmsort

@@ -47,6 +47,39 @@ def seed_templates(d_y, N=3, K=60, resolve_overlaps=False, stream=None, **opts):
                      T, N, K, resolve_overlaps, opts)
 
 
+def preprocess(d_raw, layout, taps=None, reference=None, groups=None, stream=None):
+    """api.preprocess for a raw block that is already resident (hmmsort_preprocess_device): d_raw is a contiguous
+    int16, int32, float32 or float64 device tensor of shape (T, C) with layout LAYOUT_SAMPLE_MAJOR or (C, T) with
+    LAYOUT_CHANNEL_MAJOR (1-D: one channel).  Returns the [C][T] float64 tensor the batched plans take; the taps and
+    groups are host arrays.  `stream`: a raw HIP stream handle, default torch's current one; the call synchronises
+    it."""
+    import torch
+    from ._lib import LAYOUT_CHANNEL_MAJOR, LAYOUT_SAMPLE_MAJOR, SAMPLES_F32, SAMPLES_F64, SAMPLES_I16, SAMPLES_I32
+    from .api import _pre_opt
+    types = {torch.int16: SAMPLES_I16, torch.int32: SAMPLES_I32, torch.float32: SAMPLES_F32,
+             torch.float64: SAMPLES_F64}
+    if d_raw.dtype not in types or not d_raw.is_contiguous() or d_raw.dim() not in (1, 2):
+        raise TypeError("preprocess: d_raw must be a contiguous 1-D or 2-D int16, int32, float32 or float64 device "
+                        "tensor")
+    if layout not in (LAYOUT_CHANNEL_MAJOR, LAYOUT_SAMPLE_MAJOR):
+        raise ValueError("preprocess: unknown layout %r" % (layout,))
+    if d_raw.dim() == 1:
+        nC, T = 1, int(d_raw.numel())
+    elif layout == LAYOUT_SAMPLE_MAJOR:
+        T, nC = (int(n) for n in d_raw.shape)
+    else:
+        nC, T = (int(n) for n in d_raw.shape)
+    if stream is None:
+        stream = torch.cuda.current_stream().cuda_stream
+    opt, alive = _pre_opt(taps, reference, groups, None)
+    if alive[1] is not None and len(alive[1]) != nC:
+        raise ValueError("preprocess: groups has %d entries for %d channels" % (len(alive[1]), nC))
+    d_out = torch.empty((nC, T), dtype=torch.float64, device=d_raw.device)
+    check(lib().hmmsort_preprocess_device(_dptr(d_raw), types[d_raw.dtype], int(layout), nC, T, C.byref(opt),
+                                          _dptr(d_out), C.c_void_p(stream)))
+    return d_out
+
+
 class Plan:
     """One recording channel of length T with a fixed model shape."""
 

@@ -70,9 +70,29 @@ def _chunk_confidence(templates, dataf, ml_seq, chunksize, jitter):
     return cat(times, np.int64), cat(conf, np.float64)
 
 
+_FRONT_END_KEYS = ("fs", "low", "high", "ntaps", "taps", "reference", "groups")
+
+
+def front_end(data, preprocess, channel=0):
+    """Channel `channel` of the raw block `data` ((T, C) or 1-D) through api.preprocess, as sort_data and
+    learn_templates do with their `preprocess` dictionary: either "taps" (the full filter) or "fs" with "low" and / or
+    "high" in Hz and "ntaps" (default 257) for api.design_fir; "reference" ("median" or "mean") and "groups" as
+    api.preprocess takes them.  An empty dictionary selects and widens the channel, nothing else."""
+    opts = dict(preprocess)
+    bad = sorted(set(opts) - set(_FRONT_END_KEYS))
+    if bad:
+        raise TypeError("preprocess: unknown key(s) %s; known: %s" % (", ".join(bad), ", ".join(_FRONT_END_KEYS)))
+    taps = opts.get("taps")
+    if taps is None and (opts.get("low") is not None or opts.get("high") is not None):
+        if opts.get("fs") is None:
+            raise ValueError("preprocess: low / high need the sampling rate fs")
+        taps = api.design_fir(opts["fs"], opts.get("low"), opts.get("high"), opts.get("ntaps") or 257)
+    return api.preprocess(data, taps, opts.get("reference"), opts.get("groups"), keep=[int(channel)])[0]
+
+
 def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_templates=4,
               chunksize=100_000, confidence=False, jitter=2, refine_steps=0, adapt_halflife=None, quality=False,
-              correlograms=None):
+              correlograms=None, preprocess=None, channel=0):
     """sort_data(inputfile, datafile, outputfile; dosave, max_templates)   hmmsort.jl:36-104.
 
     Returns the reference's output dictionary; {} when there are more templates than
@@ -107,7 +127,12 @@ def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_temp
 
     `correlograms=True` or a dict of api.correlograms' options (an extension; default None, output unchanged) adds
     "ccg" (templates x templates x 2 half_bins counts of the channel's templates on the stitched path), "ccg_lags"
-    (left bin edges in samples) and "isi_violations" (per template)."""
+    (left bin edges in samples) and "isi_violations" (per template).
+
+    `preprocess=dict(...)` (an extension; default None, output unchanged) takes `data` as the raw block of all
+    channels: the whole block goes through the front end (front_end: zero-phase FIR filter, common reference) on the
+    device and channel `channel` of the result is what gets sorted.  Without it the first column is sorted as it is,
+    as in the reference, and `channel` must stay 0."""
     spike_forms = np.asarray(spike_forms, dtype=np.float64)
     nstates, _nchannels, ntemplates = spike_forms.shape
     pp = np.atleast_1d(np.asarray(p, dtype=np.float64))
@@ -119,6 +144,10 @@ def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_temp
     templates = api.HMMSpikeTemplateModel(sm, np.asfortranarray(spike_forms[:, 0, :]), sigma)
     lp, _ii = get_lp(sm)                                                       # :61
     data = np.asarray(data)
+    if preprocess is not None:
+        data = front_end(data, preprocess, channel)
+    elif channel != 0:
+        raise ValueError("sort_data: channel = %r needs preprocess (an empty dict selects the channel alone)" % channel)
     if data.ndim == 2:
         data = data[:, 0]                                                      # view(data, :, 1) :80
     # :84-88 converts to Float64 on the host; int16 samples are handed over as they are and widened in HBM
@@ -194,14 +223,19 @@ def merge_and_prune(sm, mu, sigma):
 
 
 def learn_templates(data, N=3, K=60, nsteps=4, method="viterbi", resolve_overlaps=True, postprocess=merge_and_prune,
-                    seed_options=None):
+                    seed_options=None, preprocess=None, channel=0):
     """The learning stage in front of sort_data (an extension: the reference takes its templates from a file an
     earlier stage wrote): seed N templates of K states from the channel's threshold crossings (api.seed_templates)
     and train them with api.train_model(..., init="detect"); `postprocess` is train_model's (default: the reference's
     merge-and-prune stage, see merge_and_prune).  Returns the dictionary sort_data takes: "spikeForms" (K, 1, n),
     "cinv" [1 / sigma^2] and "p" (entry probability per template), n <= N being the templates that are left with a
-    finite entry transition."""
+    finite entry transition.  `preprocess`, `channel`: as in sort_data."""
     data = np.asarray(data)
+    if preprocess is not None:
+        data = front_end(data, preprocess, channel)
+    elif channel != 0:
+        raise ValueError("learn_templates: channel = %r needs preprocess (an empty dict selects the channel alone)"
+                         % channel)
     if data.ndim == 2:
         data = data[:, 0]
     X = np.ascontiguousarray(data, dtype=np.float64)
@@ -225,11 +259,23 @@ def main(argv=None):
     ap.add_argument("--dataname", default="data")
     ap.add_argument("--outfile", default="hmmsort.mat")
     ap.add_argument("--max_templates", type=int, default=4)
+    ap.add_argument("--fs", type=float, help="sampling rate in Hz (with --highpass / --lowpass)")
+    ap.add_argument("--highpass", type=float, metavar="HZ", help="zero-phase FIR filter: pass above HZ")
+    ap.add_argument("--lowpass", type=float, metavar="HZ", help="zero-phase FIR filter: pass below HZ")
+    ap.add_argument("--ntaps", type=int, default=257, help="filter length (odd)")
+    ap.add_argument("--reference", choices=("median", "mean"),
+                    help="subtract the common reference of all channels of the block, per sample")
+    ap.add_argument("--channel", type=int, default=0, help="column of the raw block to sort (0-based)")
     a = ap.parse_args(argv)
+    pre = None
+    if a.highpass is not None or a.lowpass is not None or a.reference is not None or a.channel != 0:
+        if (a.highpass is not None or a.lowpass is not None) and a.fs is None:
+            ap.error("--highpass / --lowpass need --fs")
+        pre = {"fs": a.fs, "low": a.highpass, "high": a.lowpass, "ntaps": a.ntaps, "reference": a.reference}
     data = None
     if a.learn > 0:
         data = load_data(a.datafile, a.dataname)
-        d = learn_templates(data, a.learn, a.nstates)
+        d = learn_templates(data, a.learn, a.nstates, preprocess=pre, channel=a.channel)
         t = (d["spikeForms"], d["cinv"], d["p"]) if len(d["p"]) else None
     elif a.sourcefile is None:
         ap.error("--sourcefile is required without --learn")
@@ -240,7 +286,7 @@ def main(argv=None):
         return 0
     if data is None:
         data = load_data(a.datafile, a.dataname)
-    out = sort_data(*t, data, a.outfile, max_templates=a.max_templates)
+    out = sort_data(*t, data, a.outfile, max_templates=a.max_templates, preprocess=pre, channel=a.channel)
     print("Done! Results saved to %s" % a.outfile if out else "Too many templates. Bailing out...")
     return 0
 

@@ -623,13 +623,64 @@ int hmmsort_plan_spike_fit(hmmsort_plan *plan, const double *d_y, const int16_t 
 /* Widening of raw samples already in device memory into the fp64 signal the plan calls take
  * (src/hmmsort.jl:79-88: `view(data, :, 1)` of the acquisition array, converted to Float64): element i
  * of the output is d_in[i * stride] (stride in elements: 1 for a channel stored contiguously, the
- * channel count for sample-major recordings).  Exact for every source type.  Asynchronous on `stream`. */
+ * channel count for sample-major recordings).  Exact for every source type.  Asynchronous on `stream`.
+ * This is the widening alone, for a channel somebody else has cleaned; a raw multi-channel block (drift, mains hum,
+ * noise common to the electrodes) goes through hmmsort_preprocess below, which filters and re-references it and
+ * widens on the way. */
 #define HMMSORT_SAMPLES_I16 0
 #define HMMSORT_SAMPLES_I32 1
 #define HMMSORT_SAMPLES_F32 2
 #define HMMSORT_SAMPLES_F64 3
 int hmmsort_samples_to_f64(const void *d_in, int sample_type, int64_t T, int64_t stride, double *d_out,
                            void *stream);
+
+/* Front end for raw recordings (an extension; the reference reads a channel an upstream tool has
+ * filtered, src/hmmsort.jl:66-88): a raw block of C channels x T samples, in its own sample type and layout, into
+ * the fp64 channel-major array [C][T] that hmmsort_plan_create_batched, hmmsort_fit_channels and
+ * hmmsort_seed_templates_device take.  Two stages, all indices 0-based:
+ *   1. Zero-phase linear-phase FIR filter per channel.  The filter is given as its half, taps[0..half] with
+ *      h[-j] = h[j] = taps[j]; outside [0, T) the signal is mirrored about its end samples without repeating them
+ *      (x[-i] = x[i], x[T-1+i] = x[T-1-i]; needs T >= half + 1).  Every multiplication and addition is rounded on its
+ *      own (no fused multiply-add), in this order:
+ *          acc = taps[0] * x[t];  for j = 1..half ascending:  acc = acc + taps[j] * (x[t-j] + x[t+j]);  f[c][t] = acc
+ *      taps == NULL: no filter, f = x exactly (the widening and the channel split alone).
+ *   2. Common reference per sample, after the filter.  group[c] >= 0: channels with the same id form a group; < 0:
+ *      the channel is filtered only; group == NULL: all channels are group 0.  For a group of G channels
+ *      c_0 < c_1 < ... at each sample: HMMSORT_REF_MEDIAN: m = the middle order statistic for odd G, (a + b) * 0.5
+ *      for even G with a <= b the two middle ones (exact under ties; a column holding a NaN gives an unspecified m);
+ *      HMMSORT_REF_MEAN: s = 0.0; s = s + f[c][t] for c ascending; m = s / G.  out[c][t] = f[c][t] - m.  A group of
+ *      one channel comes out as zeros.
+ * The result is deterministic to the bit: each output is the work of one thread in a fixed order.
+ * Limits, refused before any GPU work with a message that names the argument: HMMSORT_EINVAL for a null in / out,
+ * C outside 1..HMMSORT_PRE_MAX_CHANNELS, T outside 1..2^36 or T < half + 1, half outside 0..HMMSORT_PRE_MAX_HALF, an
+ * unknown sample type, layout or reference mode, input and output ranges that overlap, a keep entry outside
+ * 0..C-1; HMMSORT_EUNSUP for a median group of more than HMMSORT_PRE_MAX_GROUP channels (the mean takes any size).
+ * opt == NULL: no filter, no reference.
+ * Device form: d_in and d_out are device memory, opt and what it points to host memory (the library uploads the taps
+ * and groups itself); writes all C rows (keep is ignored), the reference in place on d_out; its workspace does not
+ * depend on T and no widened copy of the block is made; synchronises the stream.  Host form: uploads the block once
+ * as it is (2-byte samples stay 2 bytes), runs the device form and downloads the kept rows only; with
+ * HMMSORT_REF_NONE only the kept channels are filtered.  No plan is involved. */
+#define HMMSORT_LAYOUT_CHANNEL_MAJOR 0 /* in[c * T + t] */
+#define HMMSORT_LAYOUT_SAMPLE_MAJOR 1  /* in[t * C + c]: what acquisition systems write */
+#define HMMSORT_REF_NONE 0
+#define HMMSORT_REF_MEDIAN 1
+#define HMMSORT_REF_MEAN 2
+#define HMMSORT_PRE_MAX_HALF 4096
+#define HMMSORT_PRE_MAX_CHANNELS 1024
+#define HMMSORT_PRE_MAX_GROUP 64
+typedef struct hmmsort_pre_opt {
+    const double *taps;    /* [half + 1] or NULL: no filter */
+    int64_t half;          /* P */
+    int reference;         /* HMMSORT_REF_* */
+    const int32_t *group;  /* [C] or NULL: one group */
+    const int32_t *keep;   /* host form only: rows of the result to return, NULL: all C */
+    int64_t nkeep;
+} hmmsort_pre_opt;
+int hmmsort_preprocess(const void *in, int sample_type, int layout, int64_t C, int64_t T,
+                       const hmmsort_pre_opt *opt, double *out /* [nkeep or C][T] */);
+int hmmsort_preprocess_device(const void *d_in, int sample_type, int layout, int64_t C, int64_t T,
+                              const hmmsort_pre_opt *opt, double *d_out /* [C][T] */, void *stream);
 
 /* fit.jl:24-36 on a decoded chunk in device memory.  d_x: the chunk's k states (1 = silent), 1 <= k <= 2^31 - 1.
  * lead  != 0 (the chunk is not the recording's first, fit.jl:24):  l  = 1 + number of leading samples with x > 1,

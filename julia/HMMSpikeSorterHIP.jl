@@ -337,6 +337,69 @@ function seed_templates_device(d_y::Ptr{Float64}, n::Integer, N::Integer=3, K::I
     _seed_finish(N, K, resolve_overlaps, μ, σ, lp, counts, ne, iters, times, labels)
 end
 
+# struct hmmsort_pre_opt (include/hmmsort.h) and the constants of hmmsort_preprocess
+struct CPreOpt
+    taps::Ptr{Float64}; half::Int64; reference::Cint; group::Ptr{Int32}; keep::Ptr{Int32}; nkeep::Int64
+end
+const HMMSORT_SAMPLES_I32 = Cint(1)
+const HMMSORT_SAMPLES_F32 = Cint(2)
+const HMMSORT_LAYOUT_CHANNEL_MAJOR = Cint(0)
+const HMMSORT_LAYOUT_SAMPLE_MAJOR = Cint(1)
+const HMMSORT_REF = Dict(:none => Cint(0), :median => Cint(1), :mean => Cint(2))
+_sample_type(::Type{Int16}) = HMMSORT_SAMPLES_I16
+_sample_type(::Type{Int32}) = HMMSORT_SAMPLES_I32
+_sample_type(::Type{Float32}) = HMMSORT_SAMPLES_F32
+_sample_type(::Type{Float64}) = HMMSORT_SAMPLES_F64
+
+# half of an odd-length symmetric filter, centre first; an empty vector stands for "no filter"
+_half(taps::Vector{Float64}) = isempty(taps) ? Float64[] :
+    (isodd(length(taps)) ? taps[(length(taps) + 1) ÷ 2:end] : error("preprocess: taps must have odd length"))
+
+"""
+    preprocess(raw; taps=Float64[], reference=:none, groups=Int32[], keep=Int32[], sample_major=false) -> Matrix{Float64}
+
+Front end for a raw recording block (`hmmsort_preprocess`; an extension, INTEGRATION.md "Front end"; the reference reads a
+channel an upstream tool has filtered, hmmsort.jl:66-88): a zero-phase FIR filter per channel (`taps`: the full
+odd-length symmetric filter; empty: none), then the `:median` or `:mean` of every group of channels (`groups`: one id per
+channel, negative: filtered only; empty: one group) subtracted per sample.  `raw` is the reference's `data` array,
+samples × channels (column-major, so channel-major in memory), or channels × samples with `sample_major=true`, of
+Int16, Int32, Float32 or Float64 samples; it goes to the device as it is.  `keep`: 1-based channels to return (empty:
+all).  Returns samples × channels (one column per kept channel), Float64.
+"""
+function preprocess(raw::Matrix{T}; taps::Vector{Float64}=Float64[], reference::Symbol=:none,
+                    groups::Vector{Int32}=Int32[], keep::Vector{<:Integer}=Int32[],
+                    sample_major::Bool=false) where T <: Union{Int16,Int32,Float32,Float64}
+    n, C = sample_major ? reverse(size(raw)) : size(raw)
+    isempty(groups) || length(groups) == C || error("preprocess: groups needs one entry per channel")
+    half = _half(taps); keep0 = Int32.(keep .- 1)
+    out = zeros(Float64, n, isempty(keep0) ? C : length(keep0))
+    GC.@preserve raw half groups keep0 out begin
+        opt = Ref(CPreOpt(isempty(half) ? C_NULL : pointer(half), max(length(half) - 1, 0), HMMSORT_REF[reference],
+                          isempty(groups) ? C_NULL : pointer(groups), isempty(keep0) ? C_NULL : pointer(keep0),
+                          length(keep0)))
+        check(ccall((:hmmsort_preprocess, lib), Cint,
+            (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Ref{CPreOpt}, Ptr{Float64}),
+            raw, _sample_type(T), sample_major ? HMMSORT_LAYOUT_SAMPLE_MAJOR : HMMSORT_LAYOUT_CHANNEL_MAJOR, C, n, opt,
+            out))
+    end
+    out
+end
+
+"`preprocess` of a block of `C` channels × `n` samples in device memory into the resident `[C][n]` Float64 array `d_out` the batched plans take (`hmmsort_preprocess_device`); `taps`, `groups` are host arrays; synchronises `stream`"
+function preprocess_device(d_raw::Ptr{T}, layout::Cint, C::Integer, n::Integer, d_out::Ptr{Float64};
+                           taps::Vector{Float64}=Float64[], reference::Symbol=:none, groups::Vector{Int32}=Int32[],
+                           stream::Ptr{Cvoid}=C_NULL) where T <: Union{Int16,Int32,Float32,Float64}
+    half = _half(taps)
+    GC.@preserve half groups begin
+        opt = Ref(CPreOpt(isempty(half) ? C_NULL : pointer(half), max(length(half) - 1, 0), HMMSORT_REF[reference],
+                          isempty(groups) ? C_NULL : pointer(groups), C_NULL, 0))
+        check(ccall((:hmmsort_preprocess_device, lib), Cint,
+            (Ptr{Cvoid}, Cint, Cint, Int64, Int64, Ref{CPreOpt}, Ptr{Float64}, Ptr{Cvoid}),
+            d_raw, _sample_type(T), layout, C, n, opt, d_out, stream))
+    end
+    d_out
+end
+
 # struct hmmsort_spike_fit_out (include/hmmsort.h)
 struct CSpikeFitOut
     times::Ptr{Int64}; amp::Ptr{Float64}; rss::Ptr{Float64}; energy::Ptr{Float64}; nused::Ptr{Int32}; cap::Int64
