@@ -7,9 +7,10 @@ import it through the root-level shim:  `import hmmsort_amd`.
 from . import _lib, dist, synth
 from ._lib import (ENGINE_AUTO, ENGINE_BLOCKED, ENGINE_RING, ENGINE_STRICT, ENGINE_WAVE, HmmsortError, device_count,
                    get_option, set_option, shutdown)
-from .api import (Correlograms, HMMSpikeTemplateModel, HMMSpikingModel, ModelTrack, Posteriors, SpikeFit, StateMatrix, UnitQuality,
+from .api import (Correlograms, Footprints, HMMSpikeTemplateModel, HMMSpikingModel, ModelTrack, Posteriors, SpikeFit, StateMatrix, UnitQuality,
                   backward, extract_spiketimes, fit, fit_adaptive, fit_channels, fit_step_channels, forward, get_energy,
-                  quality_from_summary, spike_fit, unit_quality, correlograms, duplicate_units,
+                  quality_from_summary, spike_fit, unit_quality, correlograms, duplicate_units, footprints, unit_locations,
+                  footprint_similarity, resolve_duplicates,
                   posterior_decode, posteriors, predict, design_fir, preprocess, reconstruct_signal, reconstruct_tracked, seed_templates, spike_confidence, train_model, train_step, unroll_mlseq, update,
                   viterbi, viterbi_step)
 from .device import Plan, stats_blend, stats_sum
@@ -27,4 +28,5 @@ __all__ = ["StateMatrix", "HMMSpikeTemplateModel", "HMMSpikingModel", "forward",
            "match_templates", "Posteriors", "posteriors", "posterior_decode", "spike_confidence",
            "viterbi_step", "fit_adaptive", "reconstruct_tracked", "ModelTrack", "stats_blend", "seed_templates",
            "learn_templates", "SpikeFit", "UnitQuality", "spike_fit", "unit_quality", "quality_from_summary",
-           "get_energy", "Correlograms", "correlograms", "duplicate_units", "design_fir", "preprocess"]
+           "get_energy", "Correlograms", "correlograms", "duplicate_units", "design_fir", "preprocess", "Footprints",
+           "footprints", "unit_locations", "footprint_similarity", "resolve_duplicates"]

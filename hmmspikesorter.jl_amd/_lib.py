@@ -89,6 +89,18 @@ class CcgOut(C.Structure):
     _fields_ = [("ccg", _vp), ("viol", _vp), ("coinc", _vp), ("n", _vp)]
 
 
+class FpOpt(C.Structure):
+    """struct hmmsort_fp_opt: samples before the spike time, window length, slots per unit and the host table [U][M] of
+    block channels (NULL: all C channels in order)"""
+    _fields_ = [("pre", _i64), ("W", _i64), ("M", _i64), ("chan", _vp)]
+
+
+class FpOut(C.Structure):
+    """struct hmmsort_fp_out: host arrays hmmsort_footprints fills ([U][M][W] doubles twice, [U] int64 twice; n is
+    required)"""
+    _fields_ = [("sum", _vp), ("sumsq", _vp), ("nused", _vp), ("n", _vp)]
+
+
 class PreOpt(C.Structure):
     """struct hmmsort_pre_opt: half filter (taps NULL: none), reference mode, group id per channel (NULL: one group)
     and, in the host form, the rows to return (NULL: all)"""
@@ -100,6 +112,7 @@ LAYOUT_CHANNEL_MAJOR, LAYOUT_SAMPLE_MAJOR = 0, 1
 REF_NONE, REF_MEDIAN, REF_MEAN = 0, 1, 2
 PRE_MAX_HALF, PRE_MAX_CHANNELS, PRE_MAX_GROUP = 4096, 1024, 64
 CCG_MAX_UNITS, CCG_MAX_HALF_BINS = 4096, 2048
+FP_MAX_UNITS, FP_MAX_W, FP_MAX_SLOTS = 4096, 1024, 1024
 
 # name -> (restype, argtypes); every symbol include/hmmsort.h declares
 SIGNATURES = {
@@ -181,6 +194,10 @@ SIGNATURES = {
     "hmmsort_plan_spike_fit": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, C.POINTER(SpikeFitOut), _vp]),
     "hmmsort_correlograms": (_int, [_i64, C.POINTER(_vp), _vp, C.POINTER(CcgOpt), C.POINTER(CcgOut)]),
     "hmmsort_plan_correlograms": (_int, [_vp, _vp, C.POINTER(CcgOpt), C.POINTER(CcgOut), _vp]),
+    "hmmsort_footprints": (_int, [_vp, _int, _i64, _i64, _i64, C.POINTER(_vp), _vp, C.POINTER(FpOpt),
+                                  C.POINTER(FpOut)]),
+    "hmmsort_footprints_device": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, C.POINTER(FpOpt), C.POINTER(FpOut), _vp]),
+    "hmmsort_plan_footprints": (_int, [_vp, _vp, _vp, _i64, C.POINTER(FpOpt), C.POINTER(FpOut), _vp]),
     "hmmsort_plan_profile": (_int, [_vp, _int]),
     "hmmsort_plan_profile_read": (_int, [_vp, _vp, C.c_char_p, _i64, C.POINTER(_f64), _pi64, _i64,
                                          _pi64]),

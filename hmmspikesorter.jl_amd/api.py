@@ -1005,13 +1005,7 @@ def correlograms(models_or_time_lists, bin=30, half_bins=50, refractory=30, coin
     pair, how many spikes of one unit the other also has.  `units` is a list whose entries are spike-time arrays
     (1-based samples, strictly ascending) or HMMSpikingModels; a model contributes its extract_spiketimes lists in
     order, so a list of per-channel models (fit_channels) gives units channel by channel.  All options in samples."""
-    lists = []
-    for item in models_or_time_lists:
-        if isinstance(item, HMMSpikingModel):
-            lists.extend(extract_spiketimes(item))
-        else:
-            lists.append(item)
-    lists = [np.ascontiguousarray(t, dtype=np.int64).ravel() for t in lists]
+    lists = _time_lists(models_or_time_lists)
     U = len(lists)
     ptrs = (C.c_void_p * max(U, 1))(*[t.ctypes.data if len(t) else None for t in lists])
     cnt = np.array([len(t) for t in lists] + [0] * (U == 0), dtype=np.int64)
@@ -1030,6 +1024,192 @@ def duplicate_units(cg, min_fraction=0.5):
             if u != v and n[u] > 0 and cg.coincidence[u, v] >= min_fraction * n[u]:
                 out.append((u, v, float(cg.coincidence[u, v]) / float(n[u])))
     return out
+
+
+@dataclass
+class Footprints:
+    """What hmmsort_footprints sums for U units over M channel slots and W window samples (definitions in
+    include/hmmsort.h), and what follows from the sums on the host."""
+    sum: np.ndarray       # [U, M, W]: sum of the used spikes' snippets
+    sumsq: np.ndarray     # [U, M, W]: sum of their squares
+    n_used: np.ndarray    # [U]: spikes whose window lies inside the block
+    n: np.ndarray         # [U]: spikes per unit
+    channels: np.ndarray  # [U, M] int32: block channel of every slot, -1 for an empty slot
+    pre: int              # window samples before the spike time
+
+    @property
+    def mean(self):
+        """[U, M, W]: sum / n_used, zeros for a unit without a used spike"""
+        nu = np.asarray(self.n_used, dtype=np.float64)[:, None, None]
+        return np.divide(self.sum, nu, out=np.zeros_like(self.sum), where=nu > 0)
+
+    @property
+    def std(self):
+        """[U, M, W]: sample spread sqrt(max(0, sumsq - sum * mean) / (n_used - 1)), zeros below two used spikes"""
+        nu = np.asarray(self.n_used, dtype=np.float64)[:, None, None]
+        var = np.maximum(0.0, self.sumsq - self.sum * self.mean)
+        return np.sqrt(np.divide(var, nu - 1.0, out=np.zeros_like(var), where=nu > 1))
+
+    @property
+    def ptp(self):
+        """[U, M]: peak to peak of the mean over the window"""
+        m = self.mean
+        return m.max(axis=2) - m.min(axis=2)
+
+    @property
+    def peak_channel(self):
+        """[U]: block channel of the slot with the largest ptp (ties to the lower slot, empty slots never), -1 for a
+        unit without a used spike"""
+        ch = np.asarray(self.channels)
+        slot = np.argmax(np.where(ch >= 0, self.ptp, -1.0), axis=1)
+        peak = ch[np.arange(len(ch)), slot]
+        return np.where(np.asarray(self.n_used) > 0, peak, -1).astype(np.int64)
+
+
+def _fp_run(call, U, nC, pre, W, channels):
+    """call(byref(hmmsort_fp_opt), byref(hmmsort_fp_out)) -> rc into the Footprints of U units on a block of nC
+    channels; `channels`: None (every channel in order), one list of block channels for all units, or a [U][M] table
+    (-1: empty slot)"""
+    pre, W = int(pre), int(W)
+    if channels is None:
+        chan, M = None, nC
+        table = np.tile(np.arange(max(nC, 0), dtype=np.int32), (max(U, 0), 1))
+    else:
+        chan = np.asarray(channels, dtype=np.int32)
+        if chan.ndim == 1:
+            chan = np.tile(chan, (max(U, 1), 1))
+        if chan.ndim != 2 or (U >= 1 and chan.shape[0] != U):
+            raise ValueError("footprints: channels must be one list of channels or a table of %d rows" % U)
+        table = chan = np.ascontiguousarray(chan)
+        M = chan.shape[1]
+    # sizes the library refuses get token arrays: it checks before it writes, and its message says what is wrong
+    ok = (1 <= U <= _lib.FP_MAX_UNITS and 1 <= W <= _lib.FP_MAX_W and 1 <= M <= _lib.FP_MAX_SLOTS
+          and U * M * W <= 1 << 28)
+    Ua, Ma, Wa = (U, M, W) if ok else (1, 1, 1)
+    s, q = np.zeros((Ua, Ma, Wa)), np.zeros((Ua, Ma, Wa))
+    nused, n = np.zeros(Ua, dtype=np.int64), np.zeros(Ua, dtype=np.int64)
+    opt = _lib.FpOpt(pre, W, M, chan.ctypes.data if chan is not None else None)
+    out = _lib.FpOut(s.ctypes.data, q.ctypes.data, nused.ctypes.data, n.ctypes.data)
+    check(call(C.byref(opt), C.byref(out)))
+    return Footprints(s, q, nused, n, table, pre)
+
+
+def _time_lists(models_or_time_lists):
+    """the units of correlograms / footprints as contiguous int64 arrays: a model contributes its extract_spiketimes
+    lists in order"""
+    lists = []
+    for item in models_or_time_lists:
+        if isinstance(item, HMMSpikingModel):
+            lists.extend(extract_spiketimes(item))
+        else:
+            lists.append(item)
+    return [np.ascontiguousarray(t, dtype=np.int64).ravel() for t in lists]
+
+
+def footprints(block, units, pre=20, W=60, channels=None):
+    """footprints(block, units; pre, W, channels) -> Footprints (an extension, INTEGRATION.md "Footprints"): the
+    spike-triggered sum and sum of squares of every unit on every channel of `block`, a [C, T] float64 or int16 array
+    (1-D: one channel) -- typically api.preprocess's output.  `units` is a list of spike-time arrays (1-based samples,
+    strictly ascending) or HMMSpikingModels, as correlograms takes them.  The window of a spike at t is samples
+    t - 1 - pre .. t - 2 - pre + W (0-based); a spike whose window leaves the block is not used.  `channels`: None for
+    all channels, one list of block channels for every unit, or a table [U][M] with -1 for empty slots."""
+    y = np.asarray(block)
+    if y.ndim == 1:
+        y = y[None, :]
+    if y.ndim != 2:
+        raise ValueError("footprints: block must be channels x samples")
+    raw = y.dtype == np.int16
+    y = np.ascontiguousarray(y, dtype=np.int16 if raw else np.float64)
+    lists = _time_lists(units)
+    U = len(lists)
+    ptrs = (C.c_void_p * max(U, 1))(*[t.ctypes.data if len(t) else None for t in lists])
+    cnt = np.array([len(t) for t in lists] + [0] * (U == 0), dtype=np.int64)
+    stype = _lib.SAMPLES_I16 if raw else _lib.SAMPLES_F64
+    nC, T = y.shape
+    return _fp_run(lambda opt, out: lib().hmmsort_footprints(ptr(y), stype, nC, T, U, ptrs, ptr(cnt), opt, out),
+                   U, nC, pre, W, channels)
+
+
+def unit_locations(fp, positions):
+    """unit_locations(fp::Footprints, positions) -> [U, D]: per unit the centre of mass of positions[channel] (a [C]
+    or [C, D] array of electrode coordinates) weighted by ptp^2 over the unit's listed slots.  NaN for a unit without
+    a used spike (or without any amplitude).  Host code."""
+    pos = np.asarray(positions, dtype=np.float64)
+    flat = pos.ndim == 1
+    if flat:
+        pos = pos[:, None]
+    ch = np.asarray(fp.channels)
+    w = np.where(ch >= 0, fp.ptp, 0.0) ** 2
+    w[np.asarray(fp.n_used) == 0] = 0.0
+    num = np.einsum("um,umd->ud", w, pos[np.where(ch >= 0, ch, 0)])
+    den = w.sum(axis=1)[:, None]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        loc = np.where(den > 0, num / den, np.nan)
+    return loc[:, 0] if flat else loc
+
+
+def footprint_similarity(fp, max_lag=10):
+    """footprint_similarity(fp::Footprints; max_lag) -> (similarity [U, U], lag [U, U]).  For u != v the similarity is
+    the maximum over l in -max_lag..max_lag of the cosine between mean_u[c][k] and mean_v[c][k + l], taken over the
+    channels both units list (a channel listed twice counts once, by its first slot) and the k for which both indices
+    lie in 0..W-1; lag[u, v] is the l that attains it (the smallest |l|, then the negative one, among equals), so
+    lag[v, u] == -lag[u, v].  0 (and lag 0) without a common channel or when either norm is 0; the diagonal is 1.
+    Host code."""
+    mean, ch = fp.mean, np.asarray(fp.channels)
+    U, _, W = mean.shape
+    sim, lag = np.zeros((U, U)), np.zeros((U, U), dtype=np.int64)
+    first = [{} for _ in range(U)]          # channel -> its first slot
+    for u in range(U):
+        for m, c in enumerate(ch[u]):
+            if c >= 0:
+                first[u].setdefault(int(c), m)
+    lags = sorted(range(-int(max_lag), int(max_lag) + 1), key=lambda l: (abs(l), l))
+    for u in range(U):
+        sim[u, u] = 1.0
+        for v in range(u + 1, U):
+            common = sorted(set(first[u]) & set(first[v]))
+            if not common:
+                continue
+            a = mean[u, [first[u][c] for c in common]]
+            b = mean[v, [first[v][c] for c in common]]
+            best, best_l = 0.0, 0
+            for l in lags:
+                if abs(l) >= W:
+                    continue
+                x, y = (a[:, :W - l], b[:, l:]) if l >= 0 else (a[:, -l:], b[:, :W + l])
+                nx, ny = np.sqrt(np.sum(x * x)), np.sqrt(np.sum(y * y))
+                if nx > 0 and ny > 0:
+                    c = float(np.sum(x * y) / (nx * ny))
+                    if c > best:
+                        best, best_l = c, l
+            sim[u, v] = sim[v, u] = best
+            lag[u, v], lag[v, u] = best_l, -best_l
+    return sim, lag
+
+
+def resolve_duplicates(cg, fp, min_fraction=0.5, min_similarity=0.8, max_lag=10):
+    """resolve_duplicates(cg::Correlograms, fp::Footprints; min_fraction, min_similarity, max_lag) -> (keep, pairs): a
+    pair {u, v} is a duplicate when duplicate_units(cg, min_fraction) lists it in either direction and
+    footprint_similarity is at least min_similarity -- a neuron seen twice has one shape across the channels, two
+    neurons that fire together do not.  Pairs are taken in ascending (min, max) order and skipped when a member is
+    already dropped; the member whose largest ptp is smaller is dropped, the higher index on a tie.  `keep` is the
+    boolean mask over the units, `pairs` the list (kept, dropped, fraction, similarity, lag) with the larger of the two
+    directions' fractions and lag = lag[kept, dropped].  Host code."""
+    frac = {}
+    for u, v, f in duplicate_units(cg, min_fraction):
+        key = (min(u, v), max(u, v))
+        frac[key] = max(f, frac.get(key, 0.0))
+    sim, lag = footprint_similarity(fp, max_lag)
+    amp = fp.ptp.max(axis=1)
+    keep = np.ones(len(amp), dtype=bool)
+    pairs = []
+    for (u, v) in sorted(frac):
+        if sim[u, v] < min_similarity or not (keep[u] and keep[v]):
+            continue
+        kept, dropped = (v, u) if amp[u] < amp[v] else (u, v)
+        keep[dropped] = False
+        pairs.append((kept, dropped, frac[(u, v)], float(sim[u, v]), int(lag[kept, dropped])))
+    return keep, pairs
 
 
 def get_energy(waveforms, cinv):

@@ -917,37 +917,71 @@ int hmmsort_plan_spike_fit(hmmsort_plan *p, const double *d_y, const int16_t *d_
 
 // ---- correlograms (correlogram.hip) ---------------------------------------------------
 
-int hmmsort_plan_correlograms(hmmsort_plan *p, const int16_t *d_x, const hmmsort_ccg_opt *opt, hmmsort_ccg_out *out,
-                              void *stream)
+// Every channel's events under the plan's current model, compacted on the device exactly as
+// hmmsort_plan_extract_spiketimes finds them and concatenated into dt in unit order u = ch N + a behind the host
+// offsets offs[0 .. U]; only the counts come to the host.  Shared by the calls that work on the units of a plan.  The
+// copies into dt are enqueued on st and read `rows`, so the record must outlive the caller's next synchronisation.
+struct PlanUnits {
+    std::vector<DevBuf> rows;   // per channel: rows of dcap[ch] entries per template
+    DevBuf dt;
+    std::vector<int64_t> offs;
+};
+
+static int plan_compact_units(hmmsort_plan *p, const int16_t *d_x, hipStream_t st, PlanUnits *pu)
 {
-    HS_CHECK(p && d_x, HMMSORT_EINVAL, "plan_correlograms: null argument");
     const int64_t N = p->model.N, nC = p->C, U = nC * N, T = p->T;
-    HS_CHECK(N <= 32, HMMSORT_EINVAL, "plan_correlograms: more than 32 templates");
-    int rc = ccg_check("plan_correlograms", U, opt, out);
-    if (rc) return rc;
-    if ((rc = need_device())) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    // every channel's events, compacted on the device as hmmsort_plan_extract_spiketimes finds them (rows of dcap[ch]
-    // entries); only the counts come to the host
-    std::vector<DevBuf> rows((size_t)nC);
-    std::vector<int64_t> dcap((size_t)nC, 1), offs((size_t)U + 1, 0);
+    int rc;
+    std::vector<int64_t> dcap((size_t)nC, 1), &offs = pu->offs;
+    pu->rows = std::vector<DevBuf>((size_t)nC);
+    offs.assign((size_t)U + 1, 0);
     for (int64_t ch = 0; ch < nC; ch++) {
         const HostModel &m = nC > 1 ? p->models[ch] : p->model;
         int64_t counts[32] = {0};
         if ((rc = extract_from_device(d_x + ch * T, T, m.states.data(), N, m.S, m.mu.data(), m.K, nullptr, 0, counts, st,
-                                      &rows[ch], &dcap[ch])))
+                                      &pu->rows[ch], &dcap[ch])))
             return rc;
         for (int64_t a = 0; a < N; a++) offs[ch * N + a + 1] = offs[ch * N + a] + counts[a];
     }
-    DevBuf dt;
-    if ((rc = dt.alloc((size_t)offs[U] * sizeof(int64_t)))) return rc;
+    if ((rc = pu->dt.alloc((size_t)offs[U] * sizeof(int64_t)))) return rc;
     for (int64_t u = 0; u < U; u++) {
         const int64_t n = offs[u + 1] - offs[u], ch = u / N, a = u % N;
         if (n > 0)
-            HS_HIP(hipMemcpyAsync(dt.as<int64_t>() + offs[u], rows[ch].as<int64_t>() + a * dcap[ch],
+            HS_HIP(hipMemcpyAsync(pu->dt.as<int64_t>() + offs[u], pu->rows[ch].as<int64_t>() + a * dcap[ch],
                                   (size_t)n * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
     }
-    return dev_correlograms(U, dt.as<int64_t>(), offs.data(), opt, out, st);
+    return HMMSORT_OK;
+}
+
+int hmmsort_plan_correlograms(hmmsort_plan *p, const int16_t *d_x, const hmmsort_ccg_opt *opt, hmmsort_ccg_out *out,
+                              void *stream)
+{
+    HS_CHECK(p && d_x, HMMSORT_EINVAL, "plan_correlograms: null argument");
+    const int64_t N = p->model.N, U = p->C * N;
+    HS_CHECK(N <= 32, HMMSORT_EINVAL, "plan_correlograms: more than 32 templates");
+    int rc = ccg_check("plan_correlograms", U, opt, out);
+    if (rc) return rc;
+    if ((rc = need_device())) return rc;
+    PlanUnits pu;
+    if ((rc = plan_compact_units(p, d_x, (hipStream_t)stream, &pu))) return rc;
+    return dev_correlograms(U, pu.dt.as<int64_t>(), pu.offs.data(), opt, out, (hipStream_t)stream);
+}
+
+// ---- footprints (footprint.hip) -------------------------------------------------------
+
+int hmmsort_plan_footprints(hmmsort_plan *p, const int16_t *d_x, const double *d_block, int64_t Cb,
+                            const hmmsort_fp_opt *opt, hmmsort_fp_out *out, void *stream)
+{
+    HS_CHECK(p && d_x && d_block, HMMSORT_EINVAL, "plan_footprints: null argument (the plan, d_x and d_block are "
+             "required)");
+    const int64_t N = p->model.N, U = p->C * N;
+    HS_CHECK(N <= 32, HMMSORT_EINVAL, "plan_footprints: more than 32 templates");
+    int64_t M;
+    int rc = fp_check("plan_footprints", Cb, p->T, U, opt, out, &M);
+    if (rc) return rc;
+    if ((rc = need_device())) return rc;
+    PlanUnits pu;
+    if ((rc = plan_compact_units(p, d_x, (hipStream_t)stream, &pu))) return rc;
+    return dev_footprints(d_block, Cb, p->T, U, pu.dt.as<int64_t>(), pu.offs.data(), opt, out, (hipStream_t)stream);
 }
 
 }  // extern "C"

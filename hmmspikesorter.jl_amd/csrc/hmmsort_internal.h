@@ -344,6 +344,15 @@ int dev_spike_fit(const double *d_y, const int16_t *d_x, int64_t T, const int16_
 int ccg_check(const char *who, int64_t U, const hmmsort_ccg_opt *opt, const hmmsort_ccg_out *out);
 int dev_correlograms(int64_t U, const int64_t *d_times, const int64_t *offs, const hmmsort_ccg_opt *opt,
                      const hmmsort_ccg_out *out, hipStream_t st);
+// footprints (footprint.hip; rules in include/hmmsort.h): fp_check is what the three entry points refuse about the
+// sizes, the options and the output record before any GPU work (*M_out: the slots per unit, C without a table).
+// dev_footprints takes the resident fp64 block and the U lists as dev_correlograms does (offs already checked), fills
+// the caller's host arrays and synchronises st.  Every read is guarded by the window rule, so the times need not be
+// checked: nothing outside d_y[0 .. C T) and d_times[offs[0] .. offs[U]) is read.
+int fp_check(const char *who, int64_t C, int64_t T, int64_t U, const hmmsort_fp_opt *opt, const hmmsort_fp_out *out,
+             int64_t *M_out);
+int dev_footprints(const double *d_y, int64_t C, int64_t T, int64_t U, const int64_t *d_times, const int64_t *offs,
+                   const hmmsort_fp_opt *opt, const hmmsort_fp_out *out, hipStream_t st);
 
 }  // namespace hmmsort
 

@@ -80,6 +80,36 @@ def preprocess(d_raw, layout, taps=None, reference=None, groups=None, stream=Non
     return d_out
 
 
+def _fp_block(d_block):
+    """(C, T) of a resident float64 block [C][T] (1-D: one channel)"""
+    if not (d_block.is_floating_point() and d_block.element_size() == 8 and d_block.is_contiguous()
+            and d_block.dim() in (1, 2)):
+        raise TypeError("footprints: the block must be a contiguous float64 device tensor of shape (C, T)")
+    return (1, int(d_block.numel())) if d_block.dim() == 1 else tuple(int(n) for n in d_block.shape)
+
+
+def footprints(d_block, d_times, offs, pre=20, W=60, channels=None, stream=None):
+    """api.footprints for a block and spike lists that are already resident (hmmsort_footprints_device): d_block the
+    [C][T] float64 tensor (device.preprocess's output), d_times one int64 device tensor holding the U lists one after
+    the other (1-based samples, each list ascending), offs the U + 1 host offsets into it.  Returns api.Footprints;
+    only the sums cross to the host.  `stream`: a raw HIP stream handle, default torch's current one; the call
+    synchronises it."""
+    from .api import _fp_run
+    nC, T = _fp_block(d_block)
+    if stream is None:
+        import torch
+        stream = torch.cuda.current_stream().cuda_stream
+    offs = np.ascontiguousarray(offs, dtype=np.int64).ravel()
+    U = len(offs) - 1
+    if d_times.element_size() != 8 or d_times.is_floating_point() or not d_times.is_contiguous():
+        raise TypeError("footprints: d_times must be a contiguous int64 device tensor")
+    if U >= 1 and int(offs[-1]) > int(d_times.numel()):
+        raise ValueError("footprints: offs ends at %d, d_times has %d entries" % (offs[-1], d_times.numel()))
+    return _fp_run(lambda opt, out: lib().hmmsort_footprints_device(_dptr(d_block), nC, T, U, _dptr(d_times),
+                                                                    ptr(offs), opt, out, C.c_void_p(stream)),
+                   U, nC, pre, W, channels)
+
+
 class Plan:
     """One recording channel of length T with a fixed model shape."""
 
@@ -303,6 +333,21 @@ class Plan:
         return _ccg_run(lambda opt, out: lib().hmmsort_plan_correlograms(self._h, _dptr(d_x), opt, out,
                                                                          C.c_void_p(stream)),
                         U, bin, half_bins, refractory, coincidence)
+
+    def footprints(self, d_x, d_block, pre=20, W=60, channels=None, stream=0):
+        """api.Footprints of the events extract_spiketimes reports on the resident path(s) d_x under the plan's current
+        model, on every channel of the resident float64 block d_block [Cb][T] of the plan's T (hmmsort_plan_footprints):
+        units are u = channel * N + template.  Cb need not be the plan's channel count: a one-channel plan can be
+        measured against the whole block its channel came from.  The events are compacted on the device and stay
+        there; only the sums cross."""
+        from .api import _fp_run
+        nC, T = _fp_block(d_block)
+        if T != self.T:
+            raise ValueError("footprints: the block has %d samples per channel, the plan %d" % (T, self.T))
+        U = getattr(self, "C", 1) * self.N
+        return _fp_run(lambda opt, out: lib().hmmsort_plan_footprints(self._h, _dptr(d_x), _dptr(d_block), nC, opt, out,
+                                                                      C.c_void_p(stream)),
+                       U, nC, pre, W, channels)
 
     def expected_counts(self, stream=0):
         """expected number of spikes per template, sum_t onset[a, t] ([C][N]; [N] for a single-channel plan)"""

@@ -73,11 +73,8 @@ def _chunk_confidence(templates, dataf, ml_seq, chunksize, jitter):
 _FRONT_END_KEYS = ("fs", "low", "high", "ntaps", "taps", "reference", "groups")
 
 
-def front_end(data, preprocess, channel=0):
-    """Channel `channel` of the raw block `data` ((T, C) or 1-D) through api.preprocess, as sort_data and
-    learn_templates do with their `preprocess` dictionary: either "taps" (the full filter) or "fs" with "low" and / or
-    "high" in Hz and "ntaps" (default 257) for api.design_fir; "reference" ("median" or "mean") and "groups" as
-    api.preprocess takes them.  An empty dictionary selects and widens the channel, nothing else."""
+def _front_end_taps(preprocess):
+    """the options of a `preprocess` dictionary and the filter they ask for (None: no filter)"""
     opts = dict(preprocess)
     bad = sorted(set(opts) - set(_FRONT_END_KEYS))
     if bad:
@@ -87,12 +84,37 @@ def front_end(data, preprocess, channel=0):
         if opts.get("fs") is None:
             raise ValueError("preprocess: low / high need the sampling rate fs")
         taps = api.design_fir(opts["fs"], opts.get("low"), opts.get("high"), opts.get("ntaps") or 257)
+    return opts, taps
+
+
+def front_end(data, preprocess, channel=0):
+    """Channel `channel` of the raw block `data` ((T, C) or 1-D) through api.preprocess, as sort_data and
+    learn_templates do with their `preprocess` dictionary: either "taps" (the full filter) or "fs" with "low" and / or
+    "high" in Hz and "ntaps" (default 257) for api.design_fir; "reference" ("median" or "mean") and "groups" as
+    api.preprocess takes them.  An empty dictionary selects and widens the channel, nothing else."""
+    opts, taps = _front_end_taps(preprocess)
     return api.preprocess(data, taps, opts.get("reference"), opts.get("groups"), keep=[int(channel)])[0]
+
+
+def front_end_block(data, preprocess):
+    """The whole raw block through the front end, left on the device: the [C][T] float64 tensor of
+    device.preprocess, same dictionary and same values as front_end gives channel by channel.  For what looks at a
+    unit on every channel (sort_data's `footprints`)."""
+    import torch
+    from . import _lib, device
+    opts, taps = _front_end_taps(preprocess)
+    raw = np.asarray(data)
+    if raw.ndim == 1:
+        raw = raw[:, None]
+    if raw.dtype not in (np.int16, np.int32, np.float32, np.float64):
+        raw = raw.astype(np.float64)
+    d_raw = torch.from_numpy(np.ascontiguousarray(raw)).cuda()
+    return device.preprocess(d_raw, _lib.LAYOUT_SAMPLE_MAJOR, taps, opts.get("reference"), opts.get("groups"))
 
 
 def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_templates=4,
               chunksize=100_000, confidence=False, jitter=2, refine_steps=0, adapt_halflife=None, quality=False,
-              correlograms=None, preprocess=None, channel=0):
+              correlograms=None, preprocess=None, channel=0, footprints=None):
     """sort_data(inputfile, datafile, outputfile; dosave, max_templates)   hmmsort.jl:36-104.
 
     Returns the reference's output dictionary; {} when there are more templates than
@@ -132,7 +154,16 @@ def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_temp
     `preprocess=dict(...)` (an extension; default None, output unchanged) takes `data` as the raw block of all
     channels: the whole block goes through the front end (front_end: zero-phase FIR filter, common reference) on the
     device and channel `channel` of the result is what gets sorted.  Without it the first column is sorted as it is,
-    as in the reference, and `channel` must stay 0."""
+    as in the reference, and `channel` must stay 0.
+
+    `footprints=True` or dict(pre=, W=) (an extension; default None, output unchanged; needs `preprocess`) keeps the
+    whole preprocessed block on the device instead of one channel of it and adds "footprint" (templates x channels x
+    W: the mean waveform of every template on every channel of the block, api.footprints on the stitched path),
+    "footprint_n" (spikes used per template) and "peak_channel" (the channel where each template is largest)."""
+    want_fp = footprints is not None and footprints is not False
+    if want_fp and preprocess is None:
+        raise ValueError("sort_data: footprints needs preprocess (an empty dict takes the block as it is): the "
+                         "footprint is measured on every channel of the preprocessed block")
     spike_forms = np.asarray(spike_forms, dtype=np.float64)
     nstates, _nchannels, ntemplates = spike_forms.shape
     pp = np.atleast_1d(np.asarray(p, dtype=np.float64))
@@ -144,7 +175,13 @@ def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_temp
     templates = api.HMMSpikeTemplateModel(sm, np.asfortranarray(spike_forms[:, 0, :]), sigma)
     lp, _ii = get_lp(sm)                                                       # :61
     data = np.asarray(data)
-    if preprocess is not None:
+    d_block = None
+    if want_fp:
+        d_block = front_end_block(data, preprocess)
+        if not 0 <= int(channel) < d_block.shape[0]:
+            raise ValueError("sort_data: channel = %r of a block of %d channels" % (channel, d_block.shape[0]))
+        data = d_block[int(channel)].cpu().numpy()
+    elif preprocess is not None:
         data = front_end(data, preprocess, channel)
     elif channel != 0:
         raise ValueError("sort_data: channel = %r needs preprocess (an empty dict selects the channel alone)" % channel)
@@ -193,6 +230,14 @@ def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_temp
     if correlograms is not None and correlograms is not False:
         cg = api.correlograms([modelf], **({} if correlograms is True else dict(correlograms)))
         out["ccg"], out["ccg_lags"], out["isi_violations"] = cg.counts, cg.lags, cg.isi_violations
+    if want_fp:
+        import torch
+        from . import device
+        lists = api.extract_spiketimes(modelf)
+        offs = np.concatenate([[0], np.cumsum([len(t) for t in lists])]).astype(np.int64)
+        d_times = torch.from_numpy(np.concatenate(lists + [np.zeros(0, dtype=np.int64)]).astype(np.int64)).cuda()
+        fp = device.footprints(d_block, d_times, offs, **({} if footprints is True else dict(footprints)))
+        out["footprint"], out["footprint_n"], out["peak_channel"] = fp.mean, fp.n_used, fp.peak_channel
     if dosave and outputfile is not None:
         from scipy.io import savemat
         savemat(outputfile, out)                                              # MAT.matwrite :100

@@ -782,6 +782,62 @@ int hmmsort_correlograms(int64_t U, const int64_t *const *times, const int64_t *
 int hmmsort_plan_correlograms(hmmsort_plan *plan, const int16_t *d_x, const hmmsort_ccg_opt *opt, hmmsort_ccg_out *out,
                               void *stream);
 
+/* Footprints: the spike-triggered sum of every unit on every channel of a block (an extension).  A
+ * per-channel sort looks at a unit on its own channel only; the footprint says on which channel the unit is largest,
+ * whether two coincident units have the same shape across the channels, and where along a probe the unit sits.  All
+ * indices 0-based unless stated.
+ *   block     y[C][T], channel-major, fp64 (the host form also takes int16, widened exactly on the device).
+ *   units     u = 0..U-1; unit u has n_u >= 0 spike times, 1-based samples, strictly ascending, each in 1..2^40 (the
+ *             lists of hmmsort_correlograms).
+ *   options   pre >= 0, W >= 1, M and chan: an optional int32 table [U][M] of block channels per unit; an entry in
+ *             0..C-1 may repeat and may come in any order, -1 marks an empty slot.  chan == NULL: M = C (the M given is
+ *             ignored) and slot m is channel m for every unit.
+ *   snippet   of a spike at time t on channel c: s[k] = y[c][t - 1 - pre + k], k = 0..W-1.  The spike is used iff
+ *             t - 1 - pre >= 0 and t - 1 - pre + W <= T, for all channels alike; a time beyond T is unused, no error.
+ *   outputs   host arrays sum[U][M][W], sumsq[U][M][W], nused[U] (used spikes), n[U] = n_u; sum, sumsq and nused may
+ *             each be NULL, n is required.  An empty slot and a unit without a used spike give zeros.
+ *   order     no floating-point atomics; the same input gives the same bits.  The list of a unit is cut into blocks of
+ *             256 consecutive list entries (the constant of hmmsort_spike_fit's summary), whichever of them are used.
+ *             Within a block, per (slot, k), a serial fold from 0.0 over the used spikes in ascending order:
+ *             ps = ps + s; pq = pq + s * s, the product rounded on its own (never fused).  The block partials are then
+ *             folded serially from 0.0 in block order; a block without a used spike contributes its 0.0.
+ * Refused before any GPU work, HMMSORT_EINVAL with a message that names the argument (and unit and position where one
+ * applies): a null required argument, C outside 1..HMMSORT_PRE_MAX_CHANNELS, T outside 1..2^36, U outside
+ * 1..HMMSORT_FP_MAX_UNITS, W outside 1..HMMSORT_FP_MAX_W, pre outside 0..2^20, M outside 1..HMMSORT_FP_MAX_SLOTS, a chan
+ * entry outside -1..C-1, a negative count, a time outside 1..2^40, a list that is not strictly ascending, a sample type
+ * other than F64 / I16.  HMMSORT_EUNSUP, naming the number of entries: U M W > 2^28.  W > T is legal: every spike is
+ * unused.  A refused call leaves every output array untouched.
+ * hmmsort_footprints: host buffers, no plan; uploads the block once (2-byte samples stay 2 bytes on the way).
+ * hmmsort_footprints_device: d_y the resident fp64 block, the lists concatenated in device memory behind U + 1 host
+ * offsets (offs[0] >= 0, ascending); the times themselves are not checked -- a time whose window leaves the block is
+ * unused whatever it is, so nothing outside d_y[0 .. C T) and d_times[offs[0] .. offs[U]) is read.  Synchronises the
+ * stream.
+ * hmmsort_plan_footprints: units u = ch N + a from the resident path(s) d_x of a plan, exactly the events of
+ * hmmsort_plan_extract_spiketimes under the plan's current model, compacted on the device (they never come to the
+ * host); d_block any resident [Cb][T] fp64 block of the plan's T, Cb need not be the plan's channel count.  Any
+ * engine.  Synchronises the stream. */
+#define HMMSORT_FP_MAX_UNITS 4096
+#define HMMSORT_FP_MAX_W 1024
+#define HMMSORT_FP_MAX_SLOTS 1024
+typedef struct hmmsort_fp_opt {
+    int64_t pre;          /* samples of the window before the spike time */
+    int64_t W;            /* window length */
+    int64_t M;            /* slots per unit (chan != NULL) */
+    const int32_t *chan;  /* [U][M] host table or NULL: all C channels in order */
+} hmmsort_fp_opt;
+typedef struct hmmsort_fp_out {
+    double *sum;      /* [U][M][W], may be NULL */
+    double *sumsq;    /* [U][M][W], may be NULL */
+    int64_t *nused;   /* [U], may be NULL */
+    int64_t *n;       /* [U], required */
+} hmmsort_fp_out;
+int hmmsort_footprints(const void *y, int sample_type, int64_t C, int64_t T, int64_t U, const int64_t *const *times,
+                       const int64_t *counts, const hmmsort_fp_opt *opt, hmmsort_fp_out *out);
+int hmmsort_footprints_device(const double *d_y, int64_t C, int64_t T, int64_t U, const int64_t *d_times,
+                              const int64_t *offs, const hmmsort_fp_opt *opt, hmmsort_fp_out *out, void *stream);
+int hmmsort_plan_footprints(hmmsort_plan *plan, const int16_t *d_x, const double *d_block, int64_t Cb,
+                            const hmmsort_fp_opt *opt, hmmsort_fp_out *out, void *stream);
+
 /* Per-kernel timing of the ring engine with HIP events recorded on the caller's stream (used by
  * bench.py for the roofline line).  hmmsort_plan_profile(plan, 1) switches bracketing on;
  * hmmsort_plan_profile_read synchronises the stream and returns, per kernel name, the total

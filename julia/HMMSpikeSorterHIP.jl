@@ -460,6 +460,74 @@ function spike_fit_device(plan::Ptr{Cvoid}, d_y::Ptr{Float64}, d_x::Ptr{Int16}, 
     end
 end
 
+# struct hmmsort_fp_opt / hmmsort_fp_out (include/hmmsort.h)
+struct CFpOpt
+    pre::Int64; W::Int64; M::Int64; chan::Ptr{Int32}
+end
+struct CFpOut
+    sum::Ptr{Float64}; sumsq::Ptr{Float64}; nused::Ptr{Int64}; n::Ptr{Int64}
+end
+
+# call(opt::Ref{CFpOpt}, out::Ref{CFpOut}) -> code, into (sum, sumsq, nused, n) with sum and sumsq W × M × U; `channels` is
+# empty (all C channels in order) or M × U 0-based block channels, -1 for an empty slot
+function _fp_run(call, U, C, pre, W, channels::Matrix{Int32})
+    isempty(channels) || size(channels, 2) == U || error("footprints: channels needs one column per unit")
+    M = isempty(channels) ? C : size(channels, 1)
+    s = zeros(Float64, W, M, U); q = zeros(Float64, W, M, U); nused = zeros(Int64, U); n = zeros(Int64, U)
+    GC.@preserve channels s q nused n begin
+        check(call(Ref(CFpOpt(pre, W, M, isempty(channels) ? C_NULL : pointer(channels))),
+                   Ref(CFpOut(pointer(s), pointer(q), pointer(nused), pointer(n)))))
+    end
+    (sum=s, sumsq=q, nused=nused, n=n)
+end
+
+"""
+    footprints(block, times; pre=20, W=60, channels=zeros(Int32, 0, 0)) -> (sum, sumsq, nused, n)
+
+Spike-triggered sum and sum of squares of every unit on every channel of a block (`hmmsort_footprints`; an extension,
+INTEGRATION.md "Footprints"): `block` is samples × channels (column-major, so channel-major in memory) of Float64 or
+Int16 samples, `times` one ascending vector of 1-based spike times per unit.  `sum[k, m, u]` adds `block[t - pre + k - 1, c]`
+over the spikes `t` of unit `u` whose window lies inside the block, `c` being channel `m` or `channels[m, u] + 1`;
+`sum ./ nused` is the unit's mean waveform on every channel.  The order of the adds is fixed (include/hmmsort.h).
+"""
+function footprints(block::Matrix{T}, times::Vector{Vector{Int64}}; pre::Integer=20, W::Integer=60,
+                    channels::Matrix{Int32}=zeros(Int32, 0, 0)) where T <: Union{Float64,Int16}
+    n, C = size(block); U = length(times)
+    ptrs = [isempty(t) ? Ptr{Int64}(C_NULL) : pointer(t) for t in times]; counts = Int64.(length.(times))
+    GC.@preserve block times ptrs counts begin
+        _fp_run(U, C, pre, W, channels) do opt, out
+            ccall((:hmmsort_footprints, lib), Cint,
+                (Ptr{Cvoid}, Cint, Int64, Int64, Int64, Ptr{Ptr{Int64}}, Ptr{Int64}, Ref{CFpOpt}, Ref{CFpOut}),
+                block, T === Int16 ? HMMSORT_SAMPLES_I16 : HMMSORT_SAMPLES_F64, C, n, U, ptrs, counts, opt, out)
+        end
+    end
+end
+
+"`footprints` of a resident `[C][n]` Float64 block and spike lists concatenated in device memory behind the `U + 1` host offsets `offs` (`hmmsort_footprints_device`); synchronises `stream`"
+function footprints_device(d_y::Ptr{Float64}, C::Integer, n::Integer, d_times::Ptr{Int64}, offs::Vector{Int64};
+                           pre::Integer=20, W::Integer=60, channels::Matrix{Int32}=zeros(Int32, 0, 0),
+                           stream::Ptr{Cvoid}=C_NULL)
+    U = length(offs) - 1
+    GC.@preserve offs begin
+        _fp_run(U, C, pre, W, channels) do opt, out
+            ccall((:hmmsort_footprints_device, lib), Cint,
+                (Ptr{Float64}, Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ref{CFpOpt}, Ref{CFpOut}, Ptr{Cvoid}),
+                d_y, C, n, U, d_times, offs, opt, out, stream)
+        end
+    end
+end
+
+"`footprints` of the units `u = ch N + a` a plan finds on its resident path(s) `d_x`, on every channel of the resident `[Cb][n]` Float64 block `d_block` of the plan's length (`hmmsort_plan_footprints`); `U` = the plan's channels × templates; synchronises `stream`"
+function footprints_plan(plan::Ptr{Cvoid}, d_x::Ptr{Int16}, d_block::Ptr{Float64}, Cb::Integer, U::Integer;
+                         pre::Integer=20, W::Integer=60, channels::Matrix{Int32}=zeros(Int32, 0, 0),
+                         stream::Ptr{Cvoid}=C_NULL)
+    _fp_run(U, Cb, pre, W, channels) do opt, out
+        ccall((:hmmsort_plan_footprints, lib), Cint,
+            (Ptr{Cvoid}, Ptr{Int16}, Ptr{Float64}, Int64, Ref{CFpOpt}, Ref{CFpOut}, Ptr{Cvoid}),
+            plan, d_x, d_block, Cb, opt, out, stream)
+    end
+end
+
 function reconstruct_signal(x::Array{T,1}, lA::StateMatrix, μ::Array{Float64,2}, σ::Float64) where T <: Integer
     xs = T === Int16 ? x : Int16.(x)
     Y2 = zeros(Float64, length(xs))
