@@ -11,6 +11,7 @@ from .api import (Correlograms, Footprints, HMMSpikeTemplateModel, HMMSpikingMod
                   backward, extract_spiketimes, fit, fit_adaptive, fit_channels, fit_step_channels, forward, get_energy,
                   quality_from_summary, spike_fit, unit_quality, correlograms, duplicate_units, footprints, unit_locations,
                   footprint_similarity, resolve_duplicates,
+                  Whitening, channel_mix, noise_covariance, noise_sums, whiten, whitening_matrix,
                   posterior_decode, posteriors, predict, design_fir, preprocess, reconstruct_signal, reconstruct_tracked, seed_templates, spike_confidence, train_model, train_step, unroll_mlseq, update,
                   viterbi, viterbi_step)
 from .device import Plan, stats_blend, stats_sum
@@ -29,4 +30,5 @@ __all__ = ["StateMatrix", "HMMSpikeTemplateModel", "HMMSpikingModel", "forward",
            "viterbi_step", "fit_adaptive", "reconstruct_tracked", "ModelTrack", "stats_blend", "seed_templates",
            "learn_templates", "SpikeFit", "UnitQuality", "spike_fit", "unit_quality", "quality_from_summary",
            "get_energy", "Correlograms", "correlograms", "duplicate_units", "design_fir", "preprocess", "Footprints",
-           "footprints", "unit_locations", "footprint_similarity", "resolve_duplicates"]
+           "footprints", "unit_locations", "footprint_similarity", "resolve_duplicates", "Whitening", "channel_mix",
+           "noise_covariance", "noise_sums", "whiten", "whitening_matrix"]

@@ -107,12 +107,24 @@ class PreOpt(C.Structure):
     _fields_ = [("taps", _vp), ("half", _i64), ("reference", _int), ("group", _vp), ("keep", _vp), ("nkeep", _i64)]
 
 
+class NoiseOpt(C.Structure):
+    """struct hmmsort_noise_opt: threshold in noise scales (NaN: 4.0), absolute thresholds per channel (NULL: from the
+    noise scale) and the guard either side of a loud sample (negative: 30)"""
+    _fields_ = [("threshold", _f64), ("thr", _vp), ("guard", _i64)]
+
+
+class NoiseOut(C.Structure):
+    """struct hmmsort_noise_out: host arrays hmmsort_noise_cov fills (sigma may be NULL) and the optional device mask"""
+    _fields_ = [("sigma", _vp), ("n_quiet", _vp), ("s1", _vp), ("s2", _vp), ("d_quiet", _vp)]
+
+
 SEED_MAX_K, SEED_MAX_N, SEED_MAX_R = 1025, 16, 1024
 LAYOUT_CHANNEL_MAJOR, LAYOUT_SAMPLE_MAJOR = 0, 1
 REF_NONE, REF_MEDIAN, REF_MEAN = 0, 1, 2
 PRE_MAX_HALF, PRE_MAX_CHANNELS, PRE_MAX_GROUP = 4096, 1024, 64
 CCG_MAX_UNITS, CCG_MAX_HALF_BINS = 4096, 2048
 FP_MAX_UNITS, FP_MAX_W, FP_MAX_SLOTS = 4096, 1024, 1024
+WHITEN_MAX_CHANNELS, WHITEN_MAX_GUARD = 1024, 65536
 
 # name -> (restype, argtypes); every symbol include/hmmsort.h declares
 SIGNATURES = {
@@ -141,6 +153,11 @@ SIGNATURES = {
     "hmmsort_samples_to_f64": (_int, [_vp, C.c_int, _i64, _i64, _vp, _vp]),
     "hmmsort_preprocess": (_int, [_vp, _int, _int, _i64, _i64, C.POINTER(PreOpt), _vp]),
     "hmmsort_preprocess_device": (_int, [_vp, _int, _int, _i64, _i64, C.POINTER(PreOpt), _vp, _vp]),
+    "hmmsort_noise_scale_device": (_int, [_vp, _i64, _i64, _vp, _vp]),
+    "hmmsort_noise_cov_device": (_int, [_vp, _i64, _i64, C.POINTER(NoiseOpt), C.POINTER(NoiseOut), _vp]),
+    "hmmsort_noise_cov": (_int, [_vp, _i64, _i64, C.POINTER(NoiseOpt), C.POINTER(NoiseOut)]),
+    "hmmsort_channel_mix_device": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "hmmsort_channel_mix": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
     "hmmsort_seed_templates": (_int, [_vp, _int, _i64, _i64, _i64, C.POINTER(SeedOpt), C.POINTER(SeedOut)]),
     "hmmsort_seed_templates_device": (_int, [_vp, _i64, _i64, _i64, C.POINTER(SeedOpt), C.POINTER(SeedOut), _vp]),
     "hmmsort_forward": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _f64, _vp]),

@@ -467,6 +467,163 @@ def preprocess(raw, taps=None, reference=None, groups=None, keep=None):
     return out
 
 
+def _noise_args(nC, threshold, guard, thr):
+    """struct hmmsort_noise_opt / hmmsort_noise_out for a block of nC channels, and the arrays they point into"""
+    th = None
+    if thr is not None:
+        th = np.ascontiguousarray(np.broadcast_to(np.asarray(thr, dtype=np.float64), (nC,)))
+    opt = _lib.NoiseOpt(float("nan") if threshold is None else float(threshold), None if th is None else th.ctypes.data,
+                        -1 if guard is None else int(guard))
+    sigma, n = np.zeros(nC), np.zeros(1, dtype=np.int64)
+    s1, s2 = np.zeros(nC), np.zeros((nC, nC))
+    out = _lib.NoiseOut(sigma.ctypes.data, n.ctypes.data, s1.ctypes.data, s2.ctypes.data, None)
+    return opt, out, (th, sigma, n, s1, s2)
+
+
+def _noise_result(opt, alive):
+    """(sigma or None, thr, n_quiet, s1, s2) of a finished noise call"""
+    th, sigma, n, s1, s2 = alive
+    if th is None:
+        th = (4.0 if np.isnan(opt.threshold) else opt.threshold) * sigma
+    else:
+        sigma = None
+    return sigma, th, int(n[0]), s1, s2
+
+
+def _block(block, who):
+    b = np.ascontiguousarray(block, dtype=np.float64)
+    if b.ndim == 1:
+        b = b[None, :]
+    if b.ndim != 2:
+        raise ValueError("%s: the block must be (C, T) float64 (1-D: one channel), got shape %s" % (who, b.shape))
+    return b
+
+
+def noise_sums(block, threshold=4.0, guard=30, thr=None):
+    """Raw noise moments of a host block [C][T] (hmmsort_noise_cov; rules in include/hmmsort.h): the noise scale per
+    channel, the mask of quiet samples (no channel beyond `threshold` noise scales, or beyond thr[c], within `guard`
+    samples) and the sums over them.  Returns (sigma or None when thr is given, thr, n_quiet, s1 [C], s2 [C][C]);
+    noise_covariance turns the last three into the covariance.  Equal bit for bit to tests/whiten_model.py."""
+    b = _block(block, "noise_sums")
+    opt, out, alive = _noise_args(b.shape[0], threshold, guard, thr)
+    check(lib().hmmsort_noise_cov(ptr(b), b.shape[0], b.shape[1], C.byref(opt), C.byref(out)))
+    return _noise_result(opt, alive)
+
+
+def _mix_args(nbr, w, who):
+    nbr = np.ascontiguousarray(nbr, dtype=np.int32)
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    if nbr.ndim != 2 or nbr.shape != w.shape:
+        raise ValueError("%s: nbr and w must both be (R, M), got %s and %s" % (who, nbr.shape, w.shape))
+    return nbr, w
+
+
+def channel_mix(block, nbr, w):
+    """out[r] = sum over m (ascending, empty slots nbr[r][m] = -1 skipped) of w[r][m] * block[nbr[r][m]], on a host
+    block [C][T] (hmmsort_channel_mix): global or local whitening, or any re-montage.  Returns (R, T) float64."""
+    b = _block(block, "channel_mix")
+    nbr, w = _mix_args(nbr, w, "channel_mix")
+    out = np.empty((nbr.shape[0], b.shape[1]), dtype=np.float64)
+    check(lib().hmmsort_channel_mix(ptr(b), b.shape[0], b.shape[1], nbr.shape[0], nbr.shape[1], ptr(nbr), ptr(w),
+                                    ptr(out)))
+    return out
+
+
+def noise_covariance(n, s1, s2):
+    """Covariance of the quiet samples from their raw sums: m = s1 / n; cov = s2 / n - outer(m, m), in that order."""
+    if int(n) < 2:
+        raise ValueError("noise_covariance: %d quiet samples; a covariance needs two at least (lower guard or raise "
+                         "threshold)" % int(n))
+    m = np.asarray(s1, dtype=np.float64) / float(n)
+    return np.asarray(s2, dtype=np.float64) / float(n) - np.outer(m, m)
+
+
+def _zca(cov, eps_rel):
+    lam, V = np.linalg.eigh(cov)
+    lam = np.maximum(lam, 0.0)
+    return (V * (1.0 / np.sqrt(lam + eps_rel * lam.max()))) @ V.T
+
+
+def whitening_matrix(cov, neighbors=None, eps_rel=1e-6):
+    """The channel mix (nbr int32 [C][M], w [C][M]) that whitens noise of covariance `cov`.  neighbors=None: ZCA of the
+    whole matrix, W = V diag(1 / sqrt(max(lam, 0) + eps_rel max(lam))) V^T with lam, V = eigh(cov), M = C.  With
+    `neighbors`, the usual local whitening: per channel the ZCA of the sub-covariance of its neighbours, of which the
+    row of the channel itself is kept.  neighbors is [C][M] channel ids (own channel included, -1 padding) or a pair
+    (positions [C][d], M): the M nearest channels by distance, then by index."""
+    cov = np.asarray(cov, dtype=np.float64)
+    nC = cov.shape[0]
+    if cov.shape != (nC, nC):
+        raise ValueError("whitening_matrix: cov must be square, got %s" % (cov.shape,))
+    if neighbors is None:
+        return np.ascontiguousarray(np.tile(np.arange(nC, dtype=np.int32), (nC, 1))), _zca(cov, eps_rel)
+    if isinstance(neighbors, tuple):
+        pos, M = np.asarray(neighbors[0], dtype=np.float64).reshape(nC, -1), min(int(neighbors[1]), nC)
+        d = np.sqrt(((pos[:, None, :] - pos[None, :, :]) ** 2).sum(-1))
+        d[np.arange(nC), np.arange(nC)] = -1.0                                  # the channel itself comes first
+        nbr = np.argsort(d, axis=1, kind="stable")[:, :M].astype(np.int32)
+    else:
+        nbr = np.array(neighbors, dtype=np.int32)
+        if nbr.ndim != 2 or nbr.shape[0] != nC:
+            raise ValueError("whitening_matrix: neighbors must be (C, M), got %s" % (nbr.shape,))
+        if nbr.min() < -1 or nbr.max() >= nC:
+            raise ValueError("whitening_matrix: a neighbour outside -1 .. C - 1")
+    w = np.zeros(nbr.shape)
+    for c in range(nC):
+        slots = np.nonzero(nbr[c] >= 0)[0]
+        ids = nbr[c, slots]
+        own = np.nonzero(ids == c)[0]
+        if len(own) != 1 or len(set(ids.tolist())) != len(ids):
+            raise ValueError("whitening_matrix: neighbors[%d] must hold channel %d once and no channel twice" % (c, c))
+        w[c, slots] = _zca(cov[np.ix_(ids, ids)], eps_rel)[own[0]]
+    return np.ascontiguousarray(nbr), w
+
+
+class Whitening:
+    """What api.whiten estimated and applied: the noise scale `sigma` per channel (None when thresholds were given),
+    the thresholds `thr` and `guard` of the quiet mask, `n_quiet`, the raw sums `s1`, `s2`, the covariance `cov` and the
+    channel mix (`nbr`, `w`)."""
+
+    def __init__(self, sigma, thr, guard, n_quiet, s1, s2, cov, nbr, w):
+        self.sigma, self.thr, self.guard, self.n_quiet = sigma, thr, guard, n_quiet
+        self.s1, self.s2, self.cov, self.nbr, self.w = s1, s2, cov, nbr, w
+
+    @property
+    def matrix(self):
+        """the mix as a dense [C][C] matrix (repeated slots add)"""
+        nC = self.nbr.shape[0]
+        W = np.zeros((nC, nC))
+        r, m = np.nonzero(self.nbr >= 0)
+        np.add.at(W, (r, self.nbr[r, m]), self.w[r, m])
+        return W
+
+    def apply(self, block):
+        """the mix on a host block [C][T] (api.channel_mix)"""
+        return channel_mix(block, self.nbr, self.w)
+
+    def scale_templates(self, mu, channel):
+        """templates that live on `channel` alone and were learned before whitening, as they appear on the whitened
+        channel: mu times the weight of the channel's own slot"""
+        own = self.w[channel][self.nbr[channel] == channel].sum()
+        return np.asarray(mu, dtype=np.float64) * own
+
+    def as_dict(self):
+        """the "whitening" entry of sort_data's and learn_templates' output"""
+        return {"nbr": self.nbr, "w": self.w, "sigma": np.zeros(0) if self.sigma is None else self.sigma,
+                "n_quiet": self.n_quiet}
+
+
+def whiten(block, threshold=4.0, guard=30, thr=None, neighbors=None, eps_rel=1e-6, whitening=None):
+    """Spatial whitening of a host block [C][T] (an extension, INTEGRATION.md "Front end"): one upload, the noise
+    scale, quiet mask, sums and the channel mix on the device (device.whiten), the C x C matrix on the host in between,
+    one download.  Returns (out [C][T], Whitening).  A given `whitening` is applied as it is, nothing is estimated."""
+    import torch
+    from . import device
+    b = _block(block, "whiten")
+    d = torch.from_numpy(b).cuda()
+    d, wh = device.whiten(d, threshold, guard, thr, neighbors, eps_rel, whitening, inplace=True)
+    return d.cpu().numpy(), wh
+
+
 def train_model(X, *args, callback=None, verbose=0, p0=None, rng=None, postprocess="reference",
                 method="baum-welch", init="random", seed_options=None):
     """The three `train_model` methods of baumwelch.jl:

@@ -489,6 +489,63 @@ int hmmsort_preprocess(const void *in, int sample_type, int layout, int64_t C, i
     return HMMSORT_OK;
 }
 
+// Spatial whitening (whiten.hip).  No plan and no cached slot.
+int hmmsort_noise_scale_device(const double *d_y, int64_t C, int64_t T, double *sigma, void *stream)
+{
+    int rc = wh_scale_check("noise_scale_device", d_y, C, T, sigma);
+    if (rc) return rc;
+    if ((rc = need_device())) return rc;
+    return dev_noise_scale(d_y, C, T, sigma, (hipStream_t)stream);
+}
+
+int hmmsort_noise_cov_device(const double *d_y, int64_t C, int64_t T, const hmmsort_noise_opt *opt,
+                             hmmsort_noise_out *out, void *stream)
+{
+    NoiseParams p;
+    int rc = wh_noise_check("noise_cov_device", d_y, C, T, opt, out, false, &p);
+    if (rc) return rc;
+    if ((rc = need_device())) return rc;
+    return dev_noise_cov(d_y, C, T, p, out, (hipStream_t)stream);
+}
+
+int hmmsort_noise_cov(const double *y, int64_t C, int64_t T, const hmmsort_noise_opt *opt, hmmsort_noise_out *out)
+{
+    NoiseParams p;
+    int rc = wh_noise_check("noise_cov", y, C, T, opt, out, true, &p);
+    if (rc) return rc;
+    if ((rc = need_device())) return rc;
+    DevBuf dy;
+    if ((rc = dy.alloc((size_t)C * T * sizeof(double)))) return rc;
+    HS_HIP(hipMemcpy(dy.p, y, (size_t)C * T * sizeof(double), hipMemcpyHostToDevice));
+    return dev_noise_cov(dy.as<double>(), C, T, p, out, nullptr);
+}
+
+int hmmsort_channel_mix_device(const double *d_in, int64_t C, int64_t T, int64_t R, int64_t M, const int32_t *nbr,
+                               const double *w, double *d_out, void *stream)
+{
+    int rc = wh_mix_check("channel_mix_device", d_in, C, T, R, M, nbr, w, d_out);
+    if (rc) return rc;
+    if ((rc = need_device())) return rc;
+    return dev_channel_mix(d_in, C, T, R, M, nbr, w, d_out, (hipStream_t)stream);
+}
+
+int hmmsort_channel_mix(const double *in, int64_t C, int64_t T, int64_t R, int64_t M, const int32_t *nbr,
+                        const double *w, double *out)
+{
+    int rc = wh_mix_check("channel_mix", in, C, T, R, M, nbr, w, out);
+    if (rc) return rc;
+    if ((rc = need_device())) return rc;
+    // one device buffer of max(C, R) rows, mixed in place when R == C
+    DevBuf din, dout;
+    if ((rc = din.alloc((size_t)C * T * sizeof(double)))) return rc;
+    if (R != C && (rc = dout.alloc((size_t)R * T * sizeof(double)))) return rc;
+    double *d_o = R != C ? dout.as<double>() : din.as<double>();
+    HS_HIP(hipMemcpy(din.p, in, (size_t)C * T * sizeof(double), hipMemcpyHostToDevice));
+    if ((rc = dev_channel_mix(din.as<double>(), C, T, R, M, nbr, w, d_o, nullptr))) return rc;
+    HS_HIP(hipMemcpy(out, d_o, (size_t)R * T * sizeof(double), hipMemcpyDeviceToHost));
+    return HMMSORT_OK;
+}
+
 int hmmsort_reconstruct(const int16_t *x, int64_t T, const int16_t *states, int64_t N, int64_t S,
                         const double *mu, int64_t K, double *y_out)
 {

@@ -424,5 +424,23 @@ int pre_resolve(const char *who, const void *in, int sample_type, int layout, in
                 const hmmsort_pre_opt *opt, const double *out, bool host_form, PrePlan *p);
 int dev_preprocess(const void *d_in, int sample_type, int layout, int64_t C, int64_t T, const PrePlan &p,
                    const std::vector<int32_t> *rows, double *d_out, hipStream_t st);
+// spatial whitening (whiten.hip; rules in include/hmmsort.h).  wh_noise_check / wh_mix_check are what the entry
+// points refuse before any GPU work; the check of a noise call fills in the defaults (guard, threshold).  The dev_
+// functions take the resident fp64 block, fill the caller's host arrays and synchronise st.
+struct NoiseParams {
+    double threshold = 4.0;
+    const double *thr = nullptr;
+    int64_t guard = 30;
+};
+int wh_scale_check(const char *who, const double *y, int64_t C, int64_t T, const double *sigma);
+int wh_noise_check(const char *who, const double *y, int64_t C, int64_t T, const hmmsort_noise_opt *opt,
+                   const hmmsort_noise_out *out, bool host_form, NoiseParams *p);
+int wh_mix_check(const char *who, const double *in, int64_t C, int64_t T, int64_t R, int64_t M, const int32_t *nbr,
+                 const double *w, const double *out);
+int dev_noise_scale(const double *d_y, int64_t C, int64_t T, double *sigma, hipStream_t st);
+int dev_noise_cov(const double *d_y, int64_t C, int64_t T, const NoiseParams &p, const hmmsort_noise_out *out,
+                  hipStream_t st);
+int dev_channel_mix(const double *d_in, int64_t C, int64_t T, int64_t R, int64_t M, const int32_t *nbr,
+                    const double *w, double *d_out, hipStream_t st);
 void host_slots_trim(size_t keep);   // idle plans of the host-buffer entry points: keep the newest `keep`
 }  // namespace hmmsort

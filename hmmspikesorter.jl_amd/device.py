@@ -80,6 +80,79 @@ def preprocess(d_raw, layout, taps=None, reference=None, groups=None, stream=Non
     return d_out
 
 
+def _f64_block(d_block, who):
+    """(C, T) of a resident float64 block [C][T] (1-D: one channel)"""
+    if not (d_block.is_floating_point() and d_block.element_size() == 8 and d_block.is_contiguous()
+            and d_block.dim() in (1, 2)):
+        raise TypeError("%s: the block must be a contiguous float64 device tensor of shape (C, T)" % who)
+    return (1, int(d_block.numel())) if d_block.dim() == 1 else tuple(int(n) for n in d_block.shape)
+
+
+def _stream(stream):
+    if stream is None:
+        import torch
+        stream = torch.cuda.current_stream().cuda_stream
+    return C.c_void_p(stream)
+
+
+def noise_scale(d_block, stream=None):
+    """sigma per channel of a resident block [C][T]: the lower median of |y| over 0.6744897501960817, exact
+    (hmmsort_noise_scale_device).  The call synchronises the stream."""
+    nC, T = _f64_block(d_block, "noise_scale")
+    sigma = np.zeros(nC)
+    check(lib().hmmsort_noise_scale_device(_dptr(d_block), nC, T, ptr(sigma), _stream(stream)))
+    return sigma
+
+
+def noise_covariance(d_block, threshold=4.0, guard=30, thr=None, d_quiet=None, stream=None):
+    """api.noise_sums for a block that is already resident (hmmsort_noise_cov_device): (sigma or None, thr, n_quiet, s1,
+    s2); only these cross to the host.  d_quiet: an optional uint8 device tensor of T entries that receives the quiet
+    mask.  `stream`: a raw HIP stream handle, default torch's current one; the call synchronises it."""
+    from .api import _noise_args, _noise_result
+    nC, T = _f64_block(d_block, "noise_covariance")
+    opt, out, alive = _noise_args(nC, threshold, guard, thr)
+    if d_quiet is not None:
+        if d_quiet.element_size() != 1 or not d_quiet.is_contiguous() or int(d_quiet.numel()) != T:
+            raise TypeError("noise_covariance: d_quiet must be a contiguous uint8 device tensor of T = %d entries" % T)
+        out.d_quiet = d_quiet.data_ptr()
+    check(lib().hmmsort_noise_cov_device(_dptr(d_block), nC, T, C.byref(opt), C.byref(out), _stream(stream)))
+    return _noise_result(opt, alive)
+
+
+def channel_mix(d_in, nbr, w, d_out=None, stream=None):
+    """api.channel_mix for a resident block [C][T] (hmmsort_channel_mix_device): nbr and w are host arrays (R, M).
+    d_out: the (R, T) float64 tensor to write, default a new one; d_out = d_in mixes in place (R == C), and no second
+    block exists.  Returns d_out.  The call synchronises the stream."""
+    import torch
+    from .api import _mix_args
+    nC, T = _f64_block(d_in, "channel_mix")
+    nbr, w = _mix_args(nbr, w, "channel_mix")
+    R, M = nbr.shape
+    if d_out is None:
+        d_out = torch.empty((R, T), dtype=torch.float64, device=d_in.device)
+    elif _f64_block(d_out, "channel_mix") != (R, T):
+        raise ValueError("channel_mix: d_out must be (%d, %d), got %s" % (R, T, tuple(d_out.shape)))
+    check(lib().hmmsort_channel_mix_device(_dptr(d_in), nC, T, R, M, ptr(nbr), ptr(w), _dptr(d_out), _stream(stream)))
+    return d_out
+
+
+def whiten(d_block, threshold=4.0, guard=30, thr=None, neighbors=None, eps_rel=1e-6, whitening=None, inplace=False,
+           stream=None):
+    """api.whiten on a resident block [C][T]: noise scale, quiet mask and sums on the device, api.noise_covariance and
+    api.whitening_matrix on the host (C x C numbers), the mix on the device.  Returns (d_out, api.Whitening);
+    inplace=True writes the block itself, and no second [C][T] buffer exists.  A given `whitening` is applied as it
+    is."""
+    from . import api
+    wh = whitening
+    if wh is None:
+        sigma, th, n, s1, s2 = noise_covariance(d_block, threshold, guard, thr, stream=stream)
+        cov = api.noise_covariance(n, s1, s2)
+        nbr, w = api.whitening_matrix(cov, neighbors, eps_rel)
+        wh = api.Whitening(sigma, th, 30 if guard is None or guard < 0 else int(guard), n, s1, s2, cov, nbr, w)
+    d2 = d_block if d_block.dim() == 2 else d_block[None, :]
+    return channel_mix(d2, wh.nbr, wh.w, d2 if inplace else None, stream), wh
+
+
 def _fp_block(d_block):
     """(C, T) of a resident float64 block [C][T] (1-D: one channel)"""
     if not (d_block.is_floating_point() and d_block.element_size() == 8 and d_block.is_contiguous()

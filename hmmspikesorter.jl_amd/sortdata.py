@@ -70,11 +70,14 @@ def _chunk_confidence(templates, dataf, ml_seq, chunksize, jitter):
     return cat(times, np.int64), cat(conf, np.float64)
 
 
-_FRONT_END_KEYS = ("fs", "low", "high", "ntaps", "taps", "reference", "groups")
+_FRONT_END_KEYS = ("fs", "low", "high", "ntaps", "taps", "reference", "groups", "whiten")
+_WHITEN_KEYS = ("threshold", "guard", "thr", "neighbors", "eps_rel")
 
 
 def _front_end_taps(preprocess):
-    """the options of a `preprocess` dictionary and the filter they ask for (None: no filter)"""
+    """the options of a `preprocess` dictionary and the filter they ask for (None: no filter).  "whiten" comes back
+    as None (off), an api.Whitening (applied as it is) or a dictionary of api.whiten's options (estimated from the
+    block)."""
     opts = dict(preprocess)
     bad = sorted(set(opts) - set(_FRONT_END_KEYS))
     if bad:
@@ -84,22 +87,45 @@ def _front_end_taps(preprocess):
         if opts.get("fs") is None:
             raise ValueError("preprocess: low / high need the sampling rate fs")
         taps = api.design_fir(opts["fs"], opts.get("low"), opts.get("high"), opts.get("ntaps") or 257)
+    wh = opts.get("whiten")
+    if wh is None or wh is False:
+        opts["whiten"] = None
+    elif wh is True:
+        opts["whiten"] = {}
+    elif not isinstance(wh, api.Whitening):
+        opts["whiten"] = dict(wh)
+        bad = sorted(set(opts["whiten"]) - set(_WHITEN_KEYS))
+        if bad:
+            raise TypeError("preprocess: unknown whiten key(s) %s; known: %s" % (", ".join(bad),
+                                                                                  ", ".join(_WHITEN_KEYS)))
     return opts, taps
 
 
-def front_end(data, preprocess, channel=0):
+def front_end(data, preprocess, channel=0, info=None):
     """Channel `channel` of the raw block `data` ((T, C) or 1-D) through api.preprocess, as sort_data and
     learn_templates do with their `preprocess` dictionary: either "taps" (the full filter) or "fs" with "low" and / or
     "high" in Hz and "ntaps" (default 257) for api.design_fir; "reference" ("median" or "mean") and "groups" as
-    api.preprocess takes them.  An empty dictionary selects and widens the channel, nothing else."""
+    api.preprocess takes them.  An empty dictionary selects and widens the channel, nothing else.
+
+    "whiten": True or a dictionary of api.whiten's options (threshold, guard, thr, neighbors, eps_rel; neighbors may
+    also be an int M, the M nearest channels by index) whitens the block after the reference, with the matrix estimated
+    from the block itself; an api.Whitening is applied as it is.  The whole block then takes the device path of
+    front_end_block (filter, reference, whitening) and row `channel` of it returns.  `info`: a dictionary that receives
+    the api.Whitening under "whitening"."""
     opts, taps = _front_end_taps(preprocess)
+    if opts["whiten"] is not None:
+        d_block = front_end_block(data, preprocess, info)
+        if not 0 <= int(channel) < d_block.shape[0]:
+            raise ValueError("preprocess: channel = %r of a block of %d channels" % (channel, d_block.shape[0]))
+        return d_block[int(channel)].cpu().numpy()
     return api.preprocess(data, taps, opts.get("reference"), opts.get("groups"), keep=[int(channel)])[0]
 
 
-def front_end_block(data, preprocess):
+def front_end_block(data, preprocess, info=None):
     """The whole raw block through the front end, left on the device: the [C][T] float64 tensor of
     device.preprocess, same dictionary and same values as front_end gives channel by channel.  For what looks at a
-    unit on every channel (sort_data's `footprints`)."""
+    unit on every channel (sort_data's `footprints`).  With "whiten" the block is whitened in place on the device
+    (device.whiten) and `info["whitening"]` receives the api.Whitening."""
     import torch
     from . import _lib, device
     opts, taps = _front_end_taps(preprocess)
@@ -109,7 +135,19 @@ def front_end_block(data, preprocess):
     if raw.dtype not in (np.int16, np.int32, np.float32, np.float64):
         raw = raw.astype(np.float64)
     d_raw = torch.from_numpy(np.ascontiguousarray(raw)).cuda()
-    return device.preprocess(d_raw, _lib.LAYOUT_SAMPLE_MAJOR, taps, opts.get("reference"), opts.get("groups"))
+    d_block = device.preprocess(d_raw, _lib.LAYOUT_SAMPLE_MAJOR, taps, opts.get("reference"), opts.get("groups"))
+    wh = opts["whiten"]
+    if wh is not None:
+        if isinstance(wh, api.Whitening):
+            d_block, wh = device.whiten(d_block, whitening=wh, inplace=True)
+        else:
+            kw = dict(wh)
+            if isinstance(kw.get("neighbors"), (int, np.integer)):
+                kw["neighbors"] = (np.arange(d_block.shape[0], dtype=np.float64)[:, None], int(kw["neighbors"]))
+            d_block, wh = device.whiten(d_block, inplace=True, **kw)
+        if info is not None:
+            info["whitening"] = wh
+    return d_block
 
 
 def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_templates=4,
@@ -154,7 +192,10 @@ def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_temp
     `preprocess=dict(...)` (an extension; default None, output unchanged) takes `data` as the raw block of all
     channels: the whole block goes through the front end (front_end: zero-phase FIR filter, common reference) on the
     device and channel `channel` of the result is what gets sorted.  Without it the first column is sorted as it is,
-    as in the reference, and `channel` must stay 0.
+    as in the reference, and `channel` must stay 0.  With "whiten" in the dictionary (front_end) the block is whitened
+    after the reference and the output gains the key "whitening": a dictionary of the channel mix ("nbr", "w"), the
+    noise scales "sigma" and "n_quiet".  The templates and sigma given must be those of the whitened channel
+    (api.Whitening.scale_templates).  Without "whiten" the output is unchanged key for key.
 
     `footprints=True` or dict(pre=, W=) (an extension; default None, output unchanged; needs `preprocess`) keeps the
     whole preprocessed block on the device instead of one channel of it and adds "footprint" (templates x channels x
@@ -175,14 +216,14 @@ def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_temp
     templates = api.HMMSpikeTemplateModel(sm, np.asfortranarray(spike_forms[:, 0, :]), sigma)
     lp, _ii = get_lp(sm)                                                       # :61
     data = np.asarray(data)
-    d_block = None
+    d_block, info = None, {}
     if want_fp:
-        d_block = front_end_block(data, preprocess)
+        d_block = front_end_block(data, preprocess, info)
         if not 0 <= int(channel) < d_block.shape[0]:
             raise ValueError("sort_data: channel = %r of a block of %d channels" % (channel, d_block.shape[0]))
         data = d_block[int(channel)].cpu().numpy()
     elif preprocess is not None:
-        data = front_end(data, preprocess, channel)
+        data = front_end(data, preprocess, channel, info)
     elif channel != 0:
         raise ValueError("sort_data: channel = %r needs preprocess (an empty dict selects the channel alone)" % channel)
     if data.ndim == 2:
@@ -207,6 +248,8 @@ def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_temp
         modelf = api.fit(templates, dataf, chunksize)                          # :90
     mlseq = api.unroll_mlseq(modelf.ml_seq, sm)                                # :92
     out = {"mlseq": mlseq, "ll": modelf.ll, "waveforms": templates.mu, "lp": lp, "sigma": sigma}
+    if "whitening" in info:
+        out["whitening"] = info["whitening"].as_dict()
     if track is not None:
         out["waveforms_track"], out["sigma_track"] = np.ascontiguousarray(track.mu), np.array(track.sigma)
         out["chunk_first"] = np.array(track.first)
@@ -274,10 +317,12 @@ def learn_templates(data, N=3, K=60, nsteps=4, method="viterbi", resolve_overlap
     and train them with api.train_model(..., init="detect"); `postprocess` is train_model's (default: the reference's
     merge-and-prune stage, see merge_and_prune).  Returns the dictionary sort_data takes: "spikeForms" (K, 1, n),
     "cinv" [1 / sigma^2] and "p" (entry probability per template), n <= N being the templates that are left with a
-    finite entry transition.  `preprocess`, `channel`: as in sort_data."""
+    finite entry transition.  `preprocess`, `channel`: as in sort_data; with "whiten" the templates are those of the
+    whitened channel and the dictionary gains the key "whitening" as sort_data's output does."""
     data = np.asarray(data)
+    info = {}
     if preprocess is not None:
-        data = front_end(data, preprocess, channel)
+        data = front_end(data, preprocess, channel, info)
     elif channel != 0:
         raise ValueError("learn_templates: channel = %r needs preprocess (an empty dict selects the channel alone)"
                          % channel)
@@ -289,11 +334,16 @@ def learn_templates(data, N=3, K=60, nsteps=4, method="viterbi", resolve_overlap
     p = np.exp(_entry_lp(sm)) if sm.N > 0 else np.zeros(0)
     keep = np.nonzero(p > 0)[0]
     mu = np.asarray(mu, dtype=np.float64).reshape(int(K), -1)
-    return {"spikeForms": np.ascontiguousarray(mu[:, keep][:, None, :]), "cinv": np.array([1.0 / (sigma * sigma)]),
-            "p": p[keep]}
+    out = {"spikeForms": np.ascontiguousarray(mu[:, keep][:, None, :]), "cinv": np.array([1.0 / (sigma * sigma)]),
+           "p": p[keep]}
+    if "whitening" in info:
+        out["whitening"] = info["whitening"].as_dict()
+    return out
 
 
 def main(argv=None):
+    """The command line.  With --whiten and --learn the learning stage and the sort each run the front end on the
+    block: every stage is deterministic, so the same whitening matrix is estimated twice, to the bit."""
     import argparse
     ap = argparse.ArgumentParser(description="HMM spike sorting of one channel (hmmsort.jl CLI)")
     ap.add_argument("--sourcefile", help=".npz/.mat with spikeForms, cinv, p (not needed with --learn)")
@@ -311,12 +361,22 @@ def main(argv=None):
     ap.add_argument("--reference", choices=("median", "mean"),
                     help="subtract the common reference of all channels of the block, per sample")
     ap.add_argument("--channel", type=int, default=0, help="column of the raw block to sort (0-based)")
+    ap.add_argument("--whiten", action="store_true",
+                    help="whiten the block across channels after the reference (noise covariance of its quiet samples)")
+    ap.add_argument("--whiten-threshold", type=float, default=4.0, metavar="X",
+                    help="a sample beyond X noise scales on any channel is not quiet")
+    ap.add_argument("--whiten-guard", type=int, default=30, metavar="N", help="nor are the N samples either side of it")
+    ap.add_argument("--whiten-neighbors", type=int, metavar="M",
+                    help="local whitening: each channel against its M nearest by channel index (default: all)")
     a = ap.parse_args(argv)
     pre = None
-    if a.highpass is not None or a.lowpass is not None or a.reference is not None or a.channel != 0:
+    if a.highpass is not None or a.lowpass is not None or a.reference is not None or a.channel != 0 or a.whiten:
         if (a.highpass is not None or a.lowpass is not None) and a.fs is None:
             ap.error("--highpass / --lowpass need --fs")
         pre = {"fs": a.fs, "low": a.highpass, "high": a.lowpass, "ntaps": a.ntaps, "reference": a.reference}
+        if a.whiten:
+            pre["whiten"] = {"threshold": a.whiten_threshold, "guard": a.whiten_guard,
+                             "neighbors": a.whiten_neighbors}
     data = None
     if a.learn > 0:
         data = load_data(a.datafile, a.dataname)

@@ -838,6 +838,61 @@ int hmmsort_footprints_device(const double *d_y, int64_t C, int64_t T, int64_t U
 int hmmsort_plan_footprints(hmmsort_plan *plan, const int16_t *d_x, const double *d_block, int64_t Cb,
                             const hmmsort_fp_opt *opt, hmmsort_fp_out *out, void *stream);
 
+/* Spatial whitening (an extension): the noise covariance of the quiet samples of a block, and a mix of
+ * its channels, on the fp64 channel-major block [C][T] that hmmsort_preprocess_device writes.  The C x C matrix itself
+ * (ZCA, global or local) is the host's work: api.whitening_matrix.  All indices 0-based.  No floating-point atomics,
+ * no fused multiply-add and no matrix-core instructions: every result is a fixed function of the input that
+ * tests/whiten_model.py reproduces bit for bit.
+ *   1. noise scale   sigma[c] = (order statistic (T-1)/2 of |y[c][.]|, exact) / 0.6744897501960817, the rule of
+ *                    hmmsort_seed_templates; all channels in one grid.  A row that holds a NaN gives an unspecified
+ *                    sigma.
+ *   2. quiet mask    thr[c] = threshold * sigma[c] (threshold NaN: 4.0), or the caller's thr[C], and then stage 1 is
+ *                    skipped.  loud[t] iff some channel has !(|y[c][t]| <= thr[c]), so a NaN or Inf sample is loud.
+ *                    quiet[t] iff no u in [max(0, t - guard), min(T - 1, t + guard)] is loud (guard < 0: 30).
+ *                    n_quiet counts the quiet samples; d_quiet, when given, receives quiet[t] as 0 / 1 bytes.
+ *   3. sums          s1[C], s2[C][C] over the quiet samples, raw (the host divides).  The block is cut into tiles of
+ *                    256 consecutive samples, quiet or not.  Within a tile every entry is a serial fold from +0.0 over
+ *                    the tile's quiet samples in ascending t: p1_i = p1_i + y_i; p2_ij = p2_ij + y_i * y_j, the product
+ *                    rounded on its own.  A sample that is not quiet contributes nothing (a NaN in it never enters).
+ *                    The tile partials are folded serially from +0.0 in tile order.  j >= i is computed and mirrored.
+ *                    n_quiet == 0 is no error: the sums are zeros.
+ *   4. channel mix   out[r][t]: acc = +0.0; for m = 0..M-1 ascending with nbr[r][m] >= 0:
+ *                    acc = acc + w[r][m] * in[nbr[r][m]][t], multiply and add rounded separately.  nbr int32 [R][M] and
+ *                    w double [R][M] are host memory (the library uploads them); -1 is an empty slot, repeats and any
+ *                    order are allowed, a row of empty slots comes out as zeros.  Global whitening is R = M = C with
+ *                    nbr[r] = 0..C-1; local whitening and any re-montage use the same call.  d_out == d_in exactly
+ *                    with R == C is allowed (a workgroup stages all rows of its samples before it writes any).
+ * Refused before any GPU work, HMMSORT_EINVAL with a message that names the argument, every output untouched: a null
+ * required pointer, C, R or M outside 1..HMMSORT_WHITEN_MAX_CHANNELS, T outside 1..2^36, guard above
+ * HMMSORT_WHITEN_MAX_GUARD, a thr[c] that is not positive (NaN included), a negative threshold, an nbr entry outside
+ * -1..C-1, input and output ranges that overlap in part, in place with R != C, d_quiet in the host form.
+ * The device forms synchronise the stream; their workspace does not depend on T except the mask (T bytes), the mask's
+ * per-tile records and a bounded buffer of tile partials.  The host forms upload the block once and run the device
+ * forms.  No plan is involved. */
+#define HMMSORT_WHITEN_MAX_CHANNELS 1024
+#define HMMSORT_WHITEN_MAX_GUARD 65536
+typedef struct hmmsort_noise_opt {
+    double threshold;   /* in units of sigma[c]; NaN: 4.0 */
+    const double *thr;  /* [C] absolute thresholds or NULL */
+    int64_t guard;      /* samples either side of a loud one; < 0: 30 */
+} hmmsort_noise_opt;
+typedef struct hmmsort_noise_out {
+    double *sigma;     /* [C], written only when thr == NULL; may be NULL */
+    int64_t *n_quiet;  /* 1 */
+    double *s1;        /* [C] */
+    double *s2;        /* [C*C] */
+    uint8_t *d_quiet;  /* device [T], may be NULL */
+} hmmsort_noise_out;
+int hmmsort_noise_scale_device(const double *d_y, int64_t C, int64_t T, double *sigma /* host [C] */, void *stream);
+int hmmsort_noise_cov_device(const double *d_y, int64_t C, int64_t T, const hmmsort_noise_opt *opt /* NULL: defaults */,
+                             hmmsort_noise_out *out, void *stream);
+int hmmsort_noise_cov(const double *y /* host [C][T] */, int64_t C, int64_t T, const hmmsort_noise_opt *opt,
+                      hmmsort_noise_out *out /* d_quiet must be NULL */);
+int hmmsort_channel_mix_device(const double *d_in, int64_t C, int64_t T, int64_t R, int64_t M, const int32_t *nbr,
+                               const double *w, double *d_out /* [R][T] */, void *stream);
+int hmmsort_channel_mix(const double *in, int64_t C, int64_t T, int64_t R, int64_t M, const int32_t *nbr,
+                        const double *w, double *out);
+
 /* Per-kernel timing of the ring engine with HIP events recorded on the caller's stream (used by
  * bench.py for the roofline line).  hmmsort_plan_profile(plan, 1) switches bracketing on;
  * hmmsort_plan_profile_read synchronises the stream and returns, per kernel name, the total

@@ -400,6 +400,57 @@ function preprocess_device(d_raw::Ptr{T}, layout::Cint, C::Integer, n::Integer, 
     d_out
 end
 
+# struct hmmsort_noise_opt / hmmsort_noise_out (include/hmmsort.h, "Spatial whitening")
+struct CNoiseOpt
+    threshold::Float64; thr::Ptr{Float64}; guard::Int64
+end
+struct CNoiseOut
+    sigma::Ptr{Float64}; n_quiet::Ptr{Int64}; s1::Ptr{Float64}; s2::Ptr{Float64}; d_quiet::Ptr{UInt8}
+end
+
+"""
+    noise_cov_device(d_y, C, n; threshold=4.0, guard=30, thr=Float64[], d_quiet=C_NULL, stream=C_NULL)
+        -> (sigma, n_quiet, s1, s2)
+
+Noise scale per channel, quiet mask and the raw sums over the quiet samples of the resident Float64 block `[C][n]`
+(`hmmsort_noise_cov_device`; an extension, INTEGRATION.md "Front end").  `thr`: absolute thresholds per channel
+(then `sigma` comes back empty); `d_quiet`: optional device array of `n` bytes that receives the mask.  The covariance
+is `s2 / n_quiet - m m'` with `m = s1 / n_quiet`.  Synchronises `stream`.
+"""
+function noise_cov_device(d_y::Ptr{Float64}, C::Integer, n::Integer; threshold::Float64=4.0, guard::Integer=30,
+                          thr::Vector{Float64}=Float64[], d_quiet::Ptr{UInt8}=Ptr{UInt8}(C_NULL),
+                          stream::Ptr{Cvoid}=C_NULL)
+    isempty(thr) || length(thr) == C || error("noise_cov_device: thr needs one entry per channel")
+    sigma = zeros(Float64, C); nq = zeros(Int64, 1); s1 = zeros(Float64, C); s2 = zeros(Float64, C, C)
+    GC.@preserve thr sigma nq s1 s2 begin
+        opt = Ref(CNoiseOpt(threshold, isempty(thr) ? C_NULL : pointer(thr), guard))
+        out = Ref(CNoiseOut(pointer(sigma), pointer(nq), pointer(s1), pointer(s2), d_quiet))
+        check(ccall((:hmmsort_noise_cov_device, lib), Cint,
+            (Ptr{Float64}, Int64, Int64, Ref{CNoiseOpt}, Ref{CNoiseOut}, Ptr{Cvoid}), d_y, C, n, opt, out, stream))
+    end
+    (isempty(thr) ? sigma : Float64[], nq[1], s1, s2)
+end
+
+"""
+    channel_mix_device(d_in, C, n, nbr, w, d_out; stream=C_NULL) -> d_out
+
+`out[r][t] = sum over m of w[r, m] * in[nbr[r, m]][t]` on the resident Float64 block `[C][n]`
+(`hmmsort_channel_mix_device`): `nbr` (R × M, 1-based channels, 0 for an empty slot) and `w` (R × M) are host
+matrices.  `d_out == d_in` mixes in place (R == C).  Synchronises `stream`.
+"""
+function channel_mix_device(d_in::Ptr{Float64}, C::Integer, n::Integer, nbr::Matrix{<:Integer}, w::Matrix{Float64},
+                            d_out::Ptr{Float64}; stream::Ptr{Cvoid}=C_NULL)
+    size(nbr) == size(w) || error("channel_mix_device: nbr and w must have the same size")
+    R, M = size(nbr)
+    nbr0 = Matrix{Int32}(permutedims(nbr .- 1)); wt = Matrix{Float64}(permutedims(w))    # row-major [R][M], 0-based
+    GC.@preserve nbr0 wt begin
+        check(ccall((:hmmsort_channel_mix_device, lib), Cint,
+            (Ptr{Float64}, Int64, Int64, Int64, Int64, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+            d_in, C, n, R, M, nbr0, wt, d_out, stream))
+    end
+    d_out
+end
+
 # struct hmmsort_spike_fit_out (include/hmmsort.h)
 struct CSpikeFitOut
     times::Ptr{Int64}; amp::Ptr{Float64}; rss::Ptr{Float64}; energy::Ptr{Float64}; nused::Ptr{Int32}; cap::Int64
