@@ -1,5 +1,5 @@
-// Internal declarations shared by the C ABI (capi.cpp, host_calls.cpp), the host-side state-space code
-// (statespace.cpp) and the device engines (generic_engine.hip, ring_engine.hip, wave_engine.hip).
+// Internal declarations shared by the C ABI (capi.cpp, host_calls.cpp, analysis_calls.cpp), the host-side
+// state-space code (statespace.cpp) and the device engines (generic_engine.hip, ring_engine.hip, wave_engine.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -397,6 +397,24 @@ int plan_path_finish(hmmsort_plan *p, const double *d_stats, double *d_out, int6
 int dev_stats_sum(const double *d_parts, int64_t nparts, int64_t len, double *d_out, hipStream_t st);
 // acc[i] = w * acc[i] + new[i] in two rounded steps for i < len - plain_tail, acc[i] += new[i] for the rest
 int dev_stats_blend(double *d_acc, double w, const double *d_new, int64_t len, int64_t plain_tail, hipStream_t st);
+// radix select (radix_select.hip): `slots` exact order statistics side by side.  Slot s selects among n keys -- the
+// patterns of |d_y[s * stride + i]|, or d_keys[s * stride + i] when d_keys is given; stride 0: every slot reads the
+// same array -- with `blocks` histogram workgroups per slot.  d_st holds the ranks and zero prefixes on entry, the
+// selected keys and the ranks among equal keys on return; d_hist: slots * kSelBins zeros, zeros again on return.
+// Everything is enqueued on st.  sel_sigmas: the noise scale of n selected lower medians, pattern as a double over the
+// upper quartile of the normal distribution -- the one rule of hmmsort_seed_templates and hmmsort_noise_scale_device.
+struct RadixSel {   // one select in flight: the key's leading digits found so far, and the rank among what matches them
+    unsigned long long prefix;
+    long long rank;
+};
+constexpr int kSelBins = 2048;      // 11-bit digits: 8 KB of LDS counters per workgroup
+__device__ __forceinline__ unsigned long long sel_key(double v)   // the 63-bit pattern of |v|
+{
+    return (unsigned long long)__double_as_longlong(v) & 0x7fffffffffffffffULL;
+}
+int dev_radix_select(const double *d_y, const unsigned long long *d_keys, int64_t stride, int64_t n, int slots,
+                     int blocks, RadixSel *d_st, unsigned long long *d_hist, hipStream_t st);
+void sel_sigmas(const RadixSel *sel, int64_t n, double *sigma);
 // template seed (seed_templates.hip): the options with the defaults filled in, checked against the limits of
 // include/hmmsort.h before any GPU work; then the seed of the resident signal d_y into the caller's host arrays
 // (synchronises st)

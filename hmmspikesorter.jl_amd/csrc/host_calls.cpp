@@ -1236,132 +1236,4 @@ int hmmsort_posteriors(const double *y, int64_t T, const int16_t *states, int64_
         });
 }
 
-// Template seed (seed_templates.hip).  No plan and no cached slot: the signal goes up once, int16 samples as they are.
-int hmmsort_seed_templates_device(const double *d_y, int64_t T, int64_t N, int64_t K, const hmmsort_seed_opt *opt,
-                                  hmmsort_seed_out *out, void *stream)
-{
-    HS_CHECK(d_y, HMMSORT_EINVAL, "seed_templates_device: null signal");
-    SeedParams p;
-    int rc = seed_resolve(T, N, K, opt, out, &p);
-    if (rc) return rc;
-    if ((rc = need_device())) return rc;
-    return dev_seed_templates(d_y, T, N, K, p, out, (hipStream_t)stream);
-}
-
-int hmmsort_seed_templates(const void *y, int sample_type, int64_t T, int64_t N, int64_t K,
-                           const hmmsort_seed_opt *opt, hmmsort_seed_out *out)
-{
-    HS_CHECK(y, HMMSORT_EINVAL, "seed_templates: null signal");
-    HS_CHECK(sample_type == HMMSORT_SAMPLES_F64 || sample_type == HMMSORT_SAMPLES_I16, HMMSORT_EINVAL,
-             "seed_templates: samples must be HMMSORT_SAMPLES_F64 or HMMSORT_SAMPLES_I16");
-    SeedParams p;
-    int rc = seed_resolve(T, N, K, opt, out, &p);
-    if (rc) return rc;
-    if ((rc = need_device())) return rc;
-    DevBuf draw, dy;
-    if ((rc = dy.alloc((size_t)T * sizeof(double)))) return rc;
-    if (sample_type == HMMSORT_SAMPLES_I16) {
-        if ((rc = draw.alloc((size_t)T * sizeof(int16_t)))) return rc;
-        HS_HIP(hipMemcpy(draw.p, y, (size_t)T * sizeof(int16_t), hipMemcpyHostToDevice));
-        if ((rc = dev_widen(draw.p, sample_type, T, 1, dy.as<double>(), nullptr))) return rc;
-    } else {
-        HS_HIP(hipMemcpy(dy.p, y, (size_t)T * sizeof(double), hipMemcpyHostToDevice));
-    }
-    return dev_seed_templates(dy.as<double>(), T, N, K, p, out, nullptr);
-}
-
-// Correlograms of host lists (correlogram.hip).  No plan and no cached slot: the lists go up once, concatenated.
-int hmmsort_correlograms(int64_t U, const int64_t *const *times, const int64_t *counts, const hmmsort_ccg_opt *opt,
-                         hmmsort_ccg_out *out)
-{
-    HS_CHECK(times && counts, HMMSORT_EINVAL, "correlograms: null argument (times and counts are required)");
-    int rc = ccg_check("correlograms", U, opt, out);
-    if (rc) return rc;
-    std::vector<int64_t> offs((size_t)U + 1, 0);
-    for (int64_t u = 0; u < U; u++) {
-        HS_CHECK(counts[u] >= 0, HMMSORT_EINVAL, "correlograms: unit %lld has a count of %lld", (long long)u,
-                 (long long)counts[u]);
-        HS_CHECK(counts[u] == 0 || times[u], HMMSORT_EINVAL, "correlograms: unit %lld has a null list of %lld times",
-                 (long long)u, (long long)counts[u]);
-        for (int64_t i = 0; i < counts[u]; i++) {
-            const int64_t t = times[u][i];
-            HS_CHECK(t >= 1 && t <= (1ll << 40), HMMSORT_EINVAL, "correlograms: unit %lld, position %lld: time %lld "
-                     "outside 1..2^40", (long long)u, (long long)i, (long long)t);
-            HS_CHECK(i == 0 || t > times[u][i - 1], HMMSORT_EINVAL, "correlograms: unit %lld, position %lld: time %lld "
-                     "after %lld (a list must be strictly ascending)", (long long)u, (long long)i, (long long)t,
-                     (long long)times[u][i - 1]);
-        }
-        offs[u + 1] = offs[u] + counts[u];
-    }
-    if ((rc = need_device())) return rc;
-    DevBuf dt;
-    if ((rc = dt.alloc((size_t)offs[U] * sizeof(int64_t)))) return rc;
-    for (int64_t u = 0; u < U; u++)
-        if (counts[u] > 0)
-            HS_HIP(hipMemcpy(dt.as<int64_t>() + offs[u], times[u], (size_t)counts[u] * sizeof(int64_t),
-                             hipMemcpyHostToDevice));
-    return dev_correlograms(U, dt.as<int64_t>(), offs.data(), opt, out, nullptr);
-}
-
-// Footprints (footprint.hip).  No plan and no cached slot.  The device form takes the resident block and lists; the
-// host form uploads the block once (int16 samples as they are, widened on the device) and the lists concatenated.
-int hmmsort_footprints_device(const double *d_y, int64_t C, int64_t T, int64_t U, const int64_t *d_times,
-                              const int64_t *offs, const hmmsort_fp_opt *opt, hmmsort_fp_out *out, void *stream)
-{
-    HS_CHECK(d_y && offs, HMMSORT_EINVAL, "footprints_device: null argument (d_y and offs are required)");
-    int64_t M;
-    int rc = fp_check("footprints_device", C, T, U, opt, out, &M);
-    if (rc) return rc;
-    HS_CHECK(offs[0] >= 0, HMMSORT_EINVAL, "footprints_device: offs[0] = %lld", (long long)offs[0]);
-    for (int64_t u = 0; u < U; u++)
-        HS_CHECK(offs[u + 1] >= offs[u], HMMSORT_EINVAL, "footprints_device: offs: unit %lld has a count of %lld",
-                 (long long)u, (long long)(offs[u + 1] - offs[u]));
-    HS_CHECK(d_times || offs[U] == offs[0], HMMSORT_EINVAL, "footprints_device: null d_times");
-    if ((rc = need_device())) return rc;
-    return dev_footprints(d_y, C, T, U, d_times, offs, opt, out, (hipStream_t)stream);
-}
-
-int hmmsort_footprints(const void *y, int sample_type, int64_t C, int64_t T, int64_t U, const int64_t *const *times,
-                       const int64_t *counts, const hmmsort_fp_opt *opt, hmmsort_fp_out *out)
-{
-    HS_CHECK(y && times && counts, HMMSORT_EINVAL, "footprints: null argument (y, times and counts are required)");
-    HS_CHECK(sample_type == HMMSORT_SAMPLES_F64 || sample_type == HMMSORT_SAMPLES_I16, HMMSORT_EINVAL,
-             "footprints: sample_type = %d: samples must be HMMSORT_SAMPLES_F64 or HMMSORT_SAMPLES_I16", sample_type);
-    int64_t M;
-    int rc = fp_check("footprints", C, T, U, opt, out, &M);
-    if (rc) return rc;
-    std::vector<int64_t> offs((size_t)U + 1, 0);
-    for (int64_t u = 0; u < U; u++) {
-        HS_CHECK(counts[u] >= 0, HMMSORT_EINVAL, "footprints: counts: unit %lld has a count of %lld", (long long)u,
-                 (long long)counts[u]);
-        HS_CHECK(counts[u] == 0 || times[u], HMMSORT_EINVAL, "footprints: times: unit %lld has a null list of %lld "
-                 "times", (long long)u, (long long)counts[u]);
-        for (int64_t i = 0; i < counts[u]; i++) {
-            const int64_t t = times[u][i];
-            HS_CHECK(t >= 1 && t <= (1ll << 40), HMMSORT_EINVAL, "footprints: times: unit %lld, position %lld: time "
-                     "%lld outside 1..2^40", (long long)u, (long long)i, (long long)t);
-            HS_CHECK(i == 0 || t > times[u][i - 1], HMMSORT_EINVAL, "footprints: times: unit %lld, position %lld: time "
-                     "%lld after %lld (a list must be strictly ascending)", (long long)u, (long long)i, (long long)t,
-                     (long long)times[u][i - 1]);
-        }
-        offs[u + 1] = offs[u] + counts[u];
-    }
-    if ((rc = need_device())) return rc;
-    const size_t CT = (size_t)C * (size_t)T;
-    DevBuf draw, dy, dt;
-    if ((rc = dy.alloc(CT * sizeof(double))) || (rc = dt.alloc((size_t)offs[U] * sizeof(int64_t)))) return rc;
-    if (sample_type == HMMSORT_SAMPLES_I16) {
-        if ((rc = draw.alloc(CT * sizeof(int16_t)))) return rc;
-        HS_HIP(hipMemcpy(draw.p, y, CT * sizeof(int16_t), hipMemcpyHostToDevice));
-        if ((rc = dev_widen(draw.p, sample_type, (int64_t)CT, 1, dy.as<double>(), nullptr))) return rc;
-    } else {
-        HS_HIP(hipMemcpy(dy.p, y, CT * sizeof(double), hipMemcpyHostToDevice));
-    }
-    for (int64_t u = 0; u < U; u++)
-        if (counts[u] > 0)
-            HS_HIP(hipMemcpy(dt.as<int64_t>() + offs[u], times[u], (size_t)counts[u] * sizeof(int64_t),
-                             hipMemcpyHostToDevice));
-    return dev_footprints(dy.as<double>(), C, T, U, dt.as<int64_t>(), offs.data(), opt, out, nullptr);
-}
-
 }  // extern "C"

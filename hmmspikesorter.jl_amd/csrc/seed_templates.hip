@@ -1,8 +1,6 @@
 // Template seed (hmmsort_seed_templates, include/hmmsort.h; DESIGN "Template seed"): approximate templates from the
 // recording alone, so that training can start on the device.  Four stages, all on the caller's stream:
-//   1. noise scale: the exact lower median of |y| by a most-significant-digit radix select over the 63-bit patterns
-//      (non-negative doubles order as their integer patterns).  Per-workgroup LDS histograms are merged with integer
-//      atomics, whose sums do not depend on arrival order.
+//   1. noise scale: the exact lower median of |y| by the radix select of radix_select.hip over the 63-bit patterns.
 //   2. detection: a sample above threshold that is the extremum of its +-R window (earliest sample of a plateau).
 //      One streaming pass, a tile plus R halo samples each side in LDS; per-tile counts, a scan, a compaction into
 //      the ascending event list.
@@ -15,7 +13,6 @@
 // multiply and add per snippet sample, in ascending sample order, as the numpy model of the tests does.
 #include <algorithm>
 #include <cmath>
-#include <cstring>
 #include <limits>
 
 #include "hmmsort_internal.h"
@@ -26,25 +23,12 @@ namespace {
 constexpr int kSeedThreads = 256;
 constexpr int kSeedWaves = kSeedThreads / 64;
 constexpr int kSeedMaxBlocks = 2048;
-constexpr int kSelBins = 2048;      // 11-bit digits: 8 KB of LDS counters per workgroup
-constexpr int kSelPasses = 6;       // 5 x 11 bits + 9 bits = 64
 constexpr int kDetTile = 1024;      // samples a detection workgroup owns
 constexpr int kSumTile = kSeedThreads;   // events per partial centre sum: fixed, so the sum order is
-constexpr double kMadToSigma = 0.6744897501960817;   // upper quartile of the normal distribution
 
 static_assert(kDetTile % kSeedThreads == 0, "detection rounds");
 
-struct SelState {   // one select in flight: the key's leading digits found so far, and the rank among what matches them
-    unsigned long long prefix;
-    long long rank;
-};
-
 __device__ __forceinline__ double seed_polar(double y, int pol) { return pol < 0 ? -y : (pol == 0 ? fabs(y) : y); }
-
-__device__ __forceinline__ unsigned long long seed_bits(double v)
-{
-    return (unsigned long long)__double_as_longlong(v) & 0x7fffffffffffffffULL;
-}
 
 // position of a flagged thread among the flagged threads of its workgroup, in thread order, and their number.
 // Two barriers; s_w is kSeedWaves ints the caller provides.
@@ -62,58 +46,6 @@ __device__ __forceinline__ int block_rank(bool flag, int *s_w, int *total)
     __syncthreads();
     *total = tot;
     return off + __popcll(b & ((1ULL << lane) - 1ULL));
-}
-
-// ---- radix select ----------------------------------------------------------------------------------------------
-// One pass: the histogram of digit (key >> shift) & (2^bits - 1) over the keys whose higher bits equal the slot's
-// prefix.  kFromY: key i is the pattern of |y[i]|, else keys[i].  grid = (blocks, slots).
-template <bool kFromY>
-__global__ __launch_bounds__(kSeedThreads) void k_sel_hist(const double *__restrict__ y,
-                                                           const unsigned long long *__restrict__ keys, int64_t n,
-                                                           int shift, int bits, int first,
-                                                           const SelState *__restrict__ st,
-                                                           unsigned long long *__restrict__ hist)
-{
-    __shared__ unsigned int s_h[kSelBins];
-    const int slot = blockIdx.y;
-    for (int i = threadIdx.x; i < kSelBins; i += kSeedThreads) s_h[i] = 0;
-    __syncthreads();
-    const unsigned long long prefix = st[slot].prefix;
-    const unsigned int mask = (1u << bits) - 1u;
-    const int hs = first ? 0 : shift + bits;   // first pass: no higher bits (and no shift by 64)
-    const int64_t step = (int64_t)gridDim.x * kSeedThreads;
-    for (int64_t i = (int64_t)blockIdx.x * kSeedThreads + threadIdx.x; i < n; i += step) {
-        const unsigned long long k = kFromY ? seed_bits(y[i]) : keys[i];
-        if (first || (k >> hs) == (prefix >> hs)) atomicAdd(&s_h[(unsigned int)(k >> shift) & mask], 1u);
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < kSelBins; i += kSeedThreads)
-        if (s_h[i]) atomicAdd(&hist[(size_t)slot * kSelBins + i], (unsigned long long)s_h[i]);
-}
-
-// the digit that holds the slot's rank: prefix gets it, rank becomes the rank within it; the histogram is zeroed for
-// the next pass.  One workgroup per slot.
-__global__ __launch_bounds__(kSeedThreads) void k_sel_pick(unsigned long long *__restrict__ hist,
-                                                           SelState *__restrict__ st, int shift)
-{
-    constexpr int kPer = kSelBins / kSeedThreads;
-    __shared__ unsigned long long s_part[kSeedThreads];
-    unsigned long long *h = hist + (size_t)blockIdx.x * kSelBins;
-    unsigned long long sum = 0;
-    for (int q = 0; q < kPer; q++) sum += h[threadIdx.x * kPer + q];
-    s_part[threadIdx.x] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long r = (unsigned long long)st[blockIdx.x].rank;
-        int g = 0;
-        while (g < kSeedThreads - 1 && r >= s_part[g]) r -= s_part[g++];
-        int b = g * kPer;
-        while (b < g * kPer + kPer - 1 && r >= h[b]) r -= h[b++];
-        st[blockIdx.x].prefix |= (unsigned long long)b << shift;
-        st[blockIdx.x].rank = (long long)r;
-    }
-    __syncthreads();
-    for (int q = 0; q < kPer; q++) h[threadIdx.x * kPer + q] = 0;
 }
 
 // ---- detection -------------------------------------------------------------------------------------------------
@@ -215,7 +147,7 @@ __global__ __launch_bounds__(kSeedThreads) void k_compact(const double *__restri
         for (int q = 0; q < n && off + q < E; q++) {
             const int64_t t = tile_ev[b * per_tile + q];
             ev_t[off + q] = t;
-            ev_key[off + q] = seed_bits(seed_polar(y[t], pol));
+            ev_key[off + q] = sel_key(seed_polar(y[t], pol));
         }
     }
 }
@@ -226,7 +158,7 @@ __global__ __launch_bounds__(kSeedThreads) void k_compact(const double *__restri
 __global__ __launch_bounds__(kSeedThreads) void k_seed_centres(const double *__restrict__ y,
                                                                const int64_t *__restrict__ ev_t,
                                                                const unsigned long long *__restrict__ ev_key,
-                                                               int64_t E, const SelState *__restrict__ st, int a,
+                                                               int64_t E, const RadixSel *__restrict__ st, int a,
                                                                int D, double *__restrict__ c)
 {
     __shared__ int s_w[kSeedWaves];
@@ -378,27 +310,6 @@ inline int seed_blocks(int64_t n)
     return (int)std::max<int64_t>(1, std::min<int64_t>((n + kSeedThreads - 1) / kSeedThreads, kSeedMaxBlocks));
 }
 
-// `slots` selects side by side over n keys (|y| patterns when d_keys is null); d_st holds their ranks and zero
-// prefixes on entry, the selected keys and the ranks among equal keys on return.  d_hist: slots * kSelBins zeros.
-int seed_select(const double *d_y, const unsigned long long *d_keys, int64_t n, int slots, SelState *d_st,
-                unsigned long long *d_hist, hipStream_t st)
-{
-    const dim3 grid(seed_blocks(n), slots);
-    for (int p = 0; p < kSelPasses; p++) {
-        const int shift = std::max(0, 64 - 11 * (p + 1));
-        const int bits = p + 1 < kSelPasses ? 11 : 64 - 11 * (kSelPasses - 1);
-        if (d_keys)
-            hipLaunchKernelGGL(k_sel_hist<false>, grid, dim3(kSeedThreads), 0, st, d_y, d_keys, n, shift, bits,
-                               (int)(p == 0), d_st, d_hist);
-        else
-            hipLaunchKernelGGL(k_sel_hist<true>, grid, dim3(kSeedThreads), 0, st, d_y, d_keys, n, shift, bits,
-                               (int)(p == 0), d_st, d_hist);
-        hipLaunchKernelGGL(k_sel_pick, dim3(slots), dim3(kSeedThreads), 0, st, d_hist, d_st, shift);
-    }
-    HS_HIP(hipGetLastError());
-    return HMMSORT_OK;
-}
-
 }  // namespace
 
 int seed_resolve(int64_t T, int64_t N, int64_t K, const hmmsort_seed_opt *opt, const hmmsort_seed_out *out,
@@ -443,25 +354,23 @@ int dev_seed_templates(const double *d_y, int64_t T, int64_t N, int64_t K, const
     if (out->iters) *out->iters = 0;
 
     DevBuf b_st, b_hist;
-    if ((rc = b_st.alloc(sizeof(SelState) * HMMSORT_SEED_MAX_N))) return rc;
+    if ((rc = b_st.alloc(sizeof(RadixSel) * HMMSORT_SEED_MAX_N))) return rc;
     if ((rc = b_hist.alloc(sizeof(unsigned long long) * kSelBins * HMMSORT_SEED_MAX_N))) return rc;
-    SelState *d_st = b_st.as<SelState>();
+    RadixSel *d_st = b_st.as<RadixSel>();
     unsigned long long *d_hist = b_hist.as<unsigned long long>();
     HS_HIP(hipMemsetAsync(d_hist, 0, b_hist.cap, st));
-    SelState h_st[HMMSORT_SEED_MAX_N];
+    RadixSel h_st[HMMSORT_SEED_MAX_N];
 
     // 1. noise scale
     double sigma_n = p.sigma;
     if (!(sigma_n > 0)) {
         h_st[0].prefix = 0;
         h_st[0].rank = (T - 1) / 2;
-        HS_HIP(hipMemcpyAsync(d_st, h_st, sizeof(SelState), hipMemcpyHostToDevice, st));
-        if ((rc = seed_select(d_y, nullptr, T, 1, d_st, d_hist, st))) return rc;
-        HS_HIP(hipMemcpyAsync(h_st, d_st, sizeof(SelState), hipMemcpyDeviceToHost, st));
+        HS_HIP(hipMemcpyAsync(d_st, h_st, sizeof(RadixSel), hipMemcpyHostToDevice, st));
+        if ((rc = dev_radix_select(d_y, nullptr, 0, T, 1, seed_blocks(T), d_st, d_hist, st))) return rc;
+        HS_HIP(hipMemcpyAsync(h_st, d_st, sizeof(RadixSel), hipMemcpyDeviceToHost, st));
         HS_HIP(hipStreamSynchronize(st));
-        double m;
-        std::memcpy(&m, &h_st[0].prefix, sizeof m);
-        sigma_n = m / kMadToSigma;
+        sel_sigmas(h_st, 1, &sigma_n);
     }
     *out->sigma = sigma_n;
     const double thr = p.threshold * sigma_n;
@@ -509,8 +418,8 @@ int dev_seed_templates(const double *d_y, int64_t T, int64_t N, int64_t K, const
         h_st[i].prefix = 0;
         h_st[i].rank = std::min<int64_t>(E - 1, ((2 * (int64_t)i + 1) * E) / (2 * N));
     }
-    HS_HIP(hipMemcpyAsync(d_st, h_st, sizeof(SelState) * n, hipMemcpyHostToDevice, st));
-    if ((rc = seed_select(nullptr, d_key, E, n, d_st, d_hist, st))) return rc;
+    HS_HIP(hipMemcpyAsync(d_st, h_st, sizeof(RadixSel) * n, hipMemcpyHostToDevice, st));
+    if ((rc = dev_radix_select(nullptr, d_key, 0, E, n, seed_blocks(E), d_st, d_hist, st))) return rc;
     hipLaunchKernelGGL(k_seed_centres, dim3(n), dim3(kSeedThreads), 0, st, d_y, d_evt, d_key, E, d_st, a, D, d_c);
 
     // 4. Lloyd iterations; no event carries label -1, so the first assignment changes every label

@@ -6,11 +6,10 @@
 // Every floating-point result is the work of one thread in a fixed order, every multiplication and addition rounded
 // on its own (no fused multiply-add, no floating-point atomics, no matrix-core instructions), so the result is a fixed
 // function of the input that tests/whiten_model.py reproduces bit for bit, whatever the launch geometry.  The only
-// atomics are on integers (the histogram counters of the noise scale).
+// atomics are on integers (the histogram counters of the noise scale's select, radix_select.hip).
 #include <algorithm>
 #include <climits>
 #include <cmath>
-#include <cstring>
 #include <vector>
 
 #include "hmmsort_internal.h"
@@ -21,70 +20,12 @@ namespace hmmsort {
 namespace {
 
 constexpr int kWhThreads = 256;
-constexpr int kWhSelBins = 2048;    // 11-bit digits, as the template seed's select
-constexpr int kWhSelPasses = 6;     // 5 x 11 bits + 9 bits = 64
-constexpr double kWhMadToSigma = 0.6744897501960817;   // upper quartile of the normal distribution
 constexpr int kMaskPer = 4, kMaskTile = kWhThreads * kMaskPer;   // samples a mask workgroup owns
 constexpr int kSumTile = 256;       // samples of one partial sum: fixed, it is part of the result
 constexpr int kNoLoud = 1 << 30;    // in-tile index of "no loud sample to the right"
 constexpr int64_t kNoLoud64 = INT64_MAX;
 constexpr size_t kPartBudget = 32u << 20;    // bytes of tile partials in flight: what a call allocates and frees
 constexpr int kMixRows = 4;         // output rows a thread of the dense mix shares an LDS read among
-
-struct WhSel {   // one select per channel: the key's leading digits found so far, and the rank among what matches them
-    unsigned long long prefix;
-    long long rank;
-};
-
-// ---- 1. noise scale: radix select of the lower median of |y[c][.]|, all channels in one grid -------------------
-// One pass: the histogram of digit (key >> shift) & (2^bits - 1) over the samples of channel blockIdx.y whose higher
-// bits equal the channel's prefix; the key of a sample is the 63-bit pattern of its magnitude.
-__global__ __launch_bounds__(kWhThreads) void k_wh_hist(const double *__restrict__ y, int64_t T, int shift, int bits,
-                                                        int first, const WhSel *__restrict__ st,
-                                                        unsigned long long *__restrict__ hist)
-{
-    __shared__ unsigned int s_h[kWhSelBins];
-    const int c = blockIdx.y;
-    for (int i = threadIdx.x; i < kWhSelBins; i += kWhThreads) s_h[i] = 0;
-    __syncthreads();
-    const unsigned long long prefix = st[c].prefix;
-    const unsigned int mask = (1u << bits) - 1u;
-    const int hs = first ? 0 : shift + bits;   // first pass: no higher bits (and no shift by 64)
-    const int64_t step = (int64_t)gridDim.x * kWhThreads;
-    const double *row = y + (int64_t)c * T;
-    for (int64_t i = (int64_t)blockIdx.x * kWhThreads + threadIdx.x; i < T; i += step) {
-        const unsigned long long k = (unsigned long long)__double_as_longlong(row[i]) & 0x7fffffffffffffffULL;
-        if (first || (k >> hs) == (prefix >> hs)) atomicAdd(&s_h[(unsigned int)(k >> shift) & mask], 1u);
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < kWhSelBins; i += kWhThreads)
-        if (s_h[i]) atomicAdd(&hist[(size_t)c * kWhSelBins + i], (unsigned long long)s_h[i]);
-}
-
-// the digit that holds the channel's rank: prefix gets it, rank becomes the rank within it; the histogram is zeroed
-// for the next pass.  One workgroup per channel.
-__global__ __launch_bounds__(kWhThreads) void k_wh_pick(unsigned long long *__restrict__ hist, WhSel *__restrict__ st,
-                                                        int shift)
-{
-    constexpr int kPer = kWhSelBins / kWhThreads;
-    __shared__ unsigned long long s_part[kWhThreads];
-    unsigned long long *h = hist + (size_t)blockIdx.x * kWhSelBins;
-    unsigned long long sum = 0;
-    for (int q = 0; q < kPer; q++) sum += h[threadIdx.x * kPer + q];
-    s_part[threadIdx.x] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long r = (unsigned long long)st[blockIdx.x].rank;
-        int g = 0;
-        while (g < kWhThreads - 1 && r >= s_part[g]) r -= s_part[g++];
-        int b = g * kPer;
-        while (b < g * kPer + kPer - 1 && r >= h[b]) r -= h[b++];
-        st[blockIdx.x].prefix |= (unsigned long long)b << shift;
-        st[blockIdx.x].rank = (long long)r;
-    }
-    __syncthreads();
-    for (int q = 0; q < kPer; q++) h[threadIdx.x * kPer + q] = 0;
-}
 
 // ---- 2. quiet mask -----------------------------------------------------------------------------------------------
 // The mask is the dilation of the loud samples by `guard` either side, for any guard, from the nearest loud sample on
@@ -487,39 +428,29 @@ __global__ __launch_bounds__(kWhThreads) void k_wh_mix(const double *in, int64_t
     }
 }
 
-// sigma of every channel into the host array (synchronises st)
+// sigma of every channel into the host array (synchronises st): the lower median of |y[c][.]| by the radix select
+// of radix_select.hip, all channels in one grid, slot c on row c
 int run_noise_scale(const double *d_y, int64_t C, int64_t T, double *sigma, hipStream_t st)
 {
     int rc;
     DevBuf b_st, b_hist;
-    if ((rc = b_st.alloc(sizeof(WhSel) * C))) return rc;
-    if ((rc = b_hist.alloc(sizeof(unsigned long long) * kWhSelBins * C))) return rc;
-    std::vector<WhSel> h_st((size_t)C);
+    if ((rc = b_st.alloc(sizeof(RadixSel) * C))) return rc;
+    if ((rc = b_hist.alloc(sizeof(unsigned long long) * kSelBins * C))) return rc;
+    std::vector<RadixSel> h_st((size_t)C);
     for (auto &s : h_st) {
         s.prefix = 0;
         s.rank = (T - 1) / 2;
     }
     HS_HIP(hipMemsetAsync(b_hist.p, 0, b_hist.cap, st));
-    HS_HIP(hipMemcpyAsync(b_st.p, h_st.data(), sizeof(WhSel) * C, hipMemcpyHostToDevice, st));
+    HS_HIP(hipMemcpyAsync(b_st.p, h_st.data(), sizeof(RadixSel) * C, hipMemcpyHostToDevice, st));
     const int64_t per = std::max<int64_t>(1, 8192 / C);
-    const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>((T + 8 * kWhThreads - 1) / (8 * kWhThreads), per)),
-                    (unsigned)C);
-    for (int p = 0; p < kWhSelPasses; p++) {
-        const int shift = std::max(0, 64 - 11 * (p + 1));
-        const int bits = p + 1 < kWhSelPasses ? 11 : 64 - 11 * (kWhSelPasses - 1);
-        hipLaunchKernelGGL(k_wh_hist, grid, dim3(kWhThreads), 0, st, d_y, T, shift, bits, (int)(p == 0),
-                           b_st.as<WhSel>(), b_hist.as<unsigned long long>());
-        hipLaunchKernelGGL(k_wh_pick, dim3((unsigned)C), dim3(kWhThreads), 0, st, b_hist.as<unsigned long long>(),
-                           b_st.as<WhSel>(), shift);
-    }
-    HS_HIP(hipGetLastError());
-    HS_HIP(hipMemcpyAsync(h_st.data(), b_st.p, sizeof(WhSel) * C, hipMemcpyDeviceToHost, st));
+    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((T + 8 * kWhThreads - 1) / (8 * kWhThreads), per));
+    if ((rc = dev_radix_select(d_y, nullptr, T, T, (int)C, blocks, b_st.as<RadixSel>(),
+                               b_hist.as<unsigned long long>(), st)))
+        return rc;
+    HS_HIP(hipMemcpyAsync(h_st.data(), b_st.p, sizeof(RadixSel) * C, hipMemcpyDeviceToHost, st));
     HS_HIP(hipStreamSynchronize(st));
-    for (int64_t c = 0; c < C; c++) {
-        double m;
-        std::memcpy(&m, &h_st[c].prefix, sizeof m);
-        sigma[c] = m / kWhMadToSigma;
-    }
+    sel_sigmas(h_st.data(), C, sigma);
     return HMMSORT_OK;
 }
 
