@@ -124,6 +124,9 @@ int hmmsort_set_option(const char *key, int64_t value)
     } else if (!strcmp(key, "cert_rounds")) {
         HS_CHECK(value >= 0 && value <= 1, HMMSORT_EINVAL, "set_option: cert_rounds must be 0 or 1");
         options_modify([&](Options &o) { o.cert_rounds = value; });
+    } else if (!strcmp(key, "interior")) {
+        HS_CHECK(value >= 0 && value <= 1, HMMSORT_EINVAL, "set_option: interior must be 0 or 1");
+        options_modify([&](Options &o) { o.interior = value; });
     } else if (!strcmp(key, "backtrace")) {
         HS_CHECK(value >= 0 && value <= 2, HMMSORT_EINVAL, "set_option: backtrace must be 0..2");
         options_modify([&](Options &o) { o.backtrace = value; });
@@ -155,6 +158,7 @@ int hmmsort_get_option(const char *key, int64_t *value)
     else if (!strcmp(key, "tie_scale")) *value = o.tie_scale;
     else if (!strcmp(key, "tie_debug")) *value = o.tie_debug;
     else if (!strcmp(key, "cert_rounds")) *value = o.cert_rounds;
+    else if (!strcmp(key, "interior")) *value = o.interior;
     else if (!strcmp(key, "backtrace")) *value = o.backtrace;
     else if (!strcmp(key, "fit_streams")) *value = o.fit_streams;
     else if (!strcmp(key, "last_escalations")) *value = last_escalations();

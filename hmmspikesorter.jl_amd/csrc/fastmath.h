@@ -6,9 +6,42 @@
 // transcendentals there).  fma() is used explicitly: the translation unit is compiled with
 // -ffp-contract=off.
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#define HS_HOST_DEVICE __host__ __device__
+#else
+#define HS_HOST_DEVICE   // a plain host compiler sees div_invariant only (tests/test_div_invariant_cpu.py)
+#endif
 
 namespace hmmsort {
+
+// n / den for a divisor that stays the same over many quotients: r = 1.0 / den is divided once (div_invariant_of),
+// and a quotient is a product and two fused multiply-adds.  With r the correctly rounded reciprocal, q = n r is
+// within an ulp of n / den, e = n - den q is exact in one fma, and q + e r rounds to the correctly rounded
+// quotient (Markstein, "Computation of elementary functions on the IBM RISC System/6000 processor", 1990, Th. 2) --
+// the same bits as `/`.  That argument needs every intermediate to be a normal number: den in [2^-200, 2^200] and
+// n in [2^-800, 2^800] keep q within 2^+-1000 and e above 2^-1060.  Everything else (n = 0, subnormal, infinite or
+// NaN; a divisor outside the range, which sets nlo to infinity) takes the IEEE division.
+struct DivInv {
+    double den, r, nlo;
+};
+HS_HOST_DEVICE inline DivInv div_invariant_of(double den)
+{
+    DivInv d;
+    d.den = den;
+    d.r = 1.0 / den;
+    d.nlo = (den >= 0x1p-200 && den <= 0x1p200) ? 0x1p-800 : __builtin_inf();
+    return d;
+}
+HS_HOST_DEVICE inline double div_invariant(double n, const DivInv &d)
+{
+    if (!(n >= d.nlo && n <= 0x1p800)) return n / d.den;
+    const double q = n * d.r;
+    const double e = __builtin_fma(-d.den, q, n);
+    return __builtin_fma(e, d.r, q);
+}
+
+#if defined(__HIPCC__)
 
 // exp(x) for any x <= ~700 (callers pass x <= 0 after max-subtraction); exp(-inf) = 0
 __device__ __forceinline__ double fexp(double x)
@@ -131,5 +164,6 @@ __device__ __forceinline__ void flog_n(double (&x)[M])
         x[i] = x[i] > 0.0 ? r : -INFINITY;
     }
 }
+#endif  // __HIPCC__
 
 }  // namespace hmmsort

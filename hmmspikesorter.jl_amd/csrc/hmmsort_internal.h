@@ -47,6 +47,7 @@ struct Options {
     int64_t tie_debug = 0;         // test aids: 1 the resolver folds the exact prefix to the end, 2 resolver off
     int64_t fit_streams = 4;       // hmmsort_fit_channels: channels one worker keeps in flight, each on its own stream
     int64_t cert_rounds = 0;       // test aid: 1 the wave decode runs every certificate round in full (0: a round that repeats nothing returns at once)
+    int64_t interior = 1;          // test aid: 0 the wave engine's sweeps run every super-step in the general form (no interior range)
     int64_t backtrace = 0;         // wave engine's backtrace kernel: 0 auto (light beside an E-step, register rows alone), 1 register rows, 2 light
 };
 // process-wide options behind a mutex: entry points work on a snapshot taken when they start

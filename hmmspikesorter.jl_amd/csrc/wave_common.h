@@ -49,6 +49,7 @@ struct WaveGeom {
     double thr_scale;        // test aid: multiplier of the near-tie threshold (option "tie_scale")
     int tie_debug;           // test aids (option "tie_debug"): 1 exact prefix folded to the end, 2 resolver off (flagged = unresolved)
     int cert_rounds;         // test aid (option "cert_rounds"): 1 every certificate round of a decode runs in full
+    int interior;            // test aid (option "interior"): 0 no interior range in kw_fwd, kw_vit, kw_vit_redo and kw_bwd (general super-steps everywhere)
     int backtrace;           // option "backtrace": 0 auto (light form beside an E-step, register rows alone), 1 register rows, 2 light
 };
 

@@ -56,7 +56,7 @@ static int make_geometry(WaveGeom &g, int64_t T, int C, int N, int L, int64_t bl
     g.T = T; g.C = C; g.N = N; g.L = L;
     g.own_lo = 0; g.own_hi = T; g.first = 1; g.last = 1;
     { const Options o = options_get(); g.thr_scale = (double)o.tie_scale; g.tie_debug = (int)o.tie_debug;
-      g.backtrace = (int)o.backtrace; g.cert_rounds = (int)o.cert_rounds; }
+      g.backtrace = (int)o.backtrace; g.cert_rounds = (int)o.cert_rounds; g.interior = (int)o.interior; }
     g.W = std::min(L, 64);
     g.RB = (int)wround_up(L + g.W, 32);
     // warm-up: four ring lengths, at least 256 samples; with chains of thousands of samples this is

@@ -35,6 +35,19 @@ __device__ __forceinline__ double scale_of(double v, double s)  // s + log2-expo
     return v > 0.0 ? s + (double)ilogb(v) * kLn2 : -INFINITY;
 }
 
+// Round 11: the parts of the interior form of the forward sweep, each 1 = on, 0 = the parent's form
+#ifndef HS_FWD_INT
+#define HS_FWD_INT 1    // the full owned super-steps run without the bookkeeping of partial steps
+#endif
+#ifndef HS_DL_REG
+#define HS_DL_REG 1     // rings of at most 64 states: interior steps take the delay line's values from registers, not from LDS
+#endif
+
+// The carry holds 2 N more doubles through the junction update.  With 2, 5 and 6 rings that costs kw_fwd a wave per
+// SIMD in the compiler's report (129, 171 and 183 registers against 117, 151 and 165), so those keep the delay
+// line's LDS reads; 1, 3, 4, 7 and 8 rings stay at the waves they had.
+constexpr bool fwd_carry(int N) { return HS_DL_REG && (N == 1 || N == 3 || N == 4 || N == 7 || N == 8); }
+
 template <int N>
 struct FIn {
     double y;
@@ -130,7 +143,22 @@ __global__ __launch_bounds__(64, N <= 4 ? 3 : (N <= 8 ? 2 : 1)) void kw_fwd(Wave
     __syncthreads();
 
     const int n_total = (int)(tend - 1 - tinit);
-    auto load = [&](FIn<N> &d, int off) {
+    // Interior super-steps (MODE 3 and 4 of run): the FULL owned steps, nact = W.  No load of a full step meets the
+    // clamp against T, every lane below W stores into the planes, and the carry leaves from lane W - 1.  The scans and
+    // lane_prev* move data from lower to higher lanes only, so what the lanes from W up hold is read by no live lane:
+    // their inputs go unselected; only what reaches memory (wsl, the stores of the planes) keeps its predicate.  The
+    // input pipeline looks D steps past the range; the loads clamp that offset to its last step (imax).
+    const bool liveW = lane < W;
+    const int liW = liveW ? lane : 0;
+    int imax = 0;
+    auto load = [&](FIn<N> &d, int off, auto mode_tag) {
+        if constexpr (decltype(mode_tag)::value >= 3) {
+            const int64_t tb = tinit + 1 + (off < imax ? off : imax);
+            d.y = (yc + tb)[liW];
+#pragma unroll
+            for (int a = 0; a < N; a++) d.R[a] = (Rc + (int64_t)a * T + tb)[liW];
+            return;
+        }
         const int nact = n_total - off < W ? n_total - off : W;
         const int li = lane < nact ? lane : 0;
         int64_t tb = tinit + 1 + off;
@@ -144,12 +172,17 @@ __global__ __launch_bounds__(64, N <= 4 ? 3 : (N <= 8 ? 2 : 1)) void kw_fwd(Wave
     // the last partial step into a trash line); 2: the last super-steps of the warm-up, which also leave
     // the boundary record (conditional stores).  Modes 0 and 1 have straight-line global accesses only,
     // so hipcc counts vmcnt exactly and the input pipeline stays D super-steps deep.
+    // MODE 3: interior super-step (above); 4: interior super-step of a ring with W == L (ring counts of fwd_carry), where rs and
+    // ws both advance by W with ws - rs = L, so lane j reads the slot it wrote one step earlier: (v_a, s_a) come from
+    // the lane's own registers (Vr, Sr, primed from the delay line before the sweep).  Every LDS write stays.
+    [[maybe_unused]] double Vr[fwd_carry(N) ? N : 1], Sr[fwd_carry(N) ? N : 1];
     auto run = [&](const FIn<N> &d, int off, auto mode_tag) {
         constexpr int MODE = decltype(mode_tag)::value;
-        const int nact = n_total - off < W ? n_total - off : W;
-        const bool live = lane < nact;
+        constexpr bool INT = MODE >= 3, CARRY = MODE == 4 && fwd_carry(N);
+        const int nact = INT ? W : (n_total - off < W ? n_total - off : W);
+        const bool live = INT ? liveW : lane < nact;
         const int64_t tb = tinit + 1 + off;
-        const int64_t t = tb + lane;
+        [[maybe_unused]] const int64_t t = tb + lane;
         const double sc0 = KC[0];
         double v[N], E[N + 1];
         double e = -INFINITY;
@@ -157,18 +190,22 @@ __global__ __launch_bounds__(64, N <= 4 ? 3 : (N <= 8 ? 2 : 1)) void kw_fwd(Wave
         for (int a = 0; a < N; a++) {
             if (LOGDL) {
                 v[a] = 1.0;
-                E[a] = live ? DLs[a * (RB + 1) + rs] + sc0 : -INFINITY;   // log of the exit of ring a
+                E[a] = (INT || live) ? DLs[a * (RB + 1) + rs] + sc0 : -INFINITY;   // log of the exit of ring a
                 e = fmax(e, E[a]);
+            } else if constexpr (CARRY) {
+                v[a] = Vr[a];
+                E[a] = Sr[a] + sc0;
+                e = fmax(e, scale_of(v[a], E[a]));
             } else {
-                v[a] = live ? DLv[a * (RB + 1) + rs] : 0.0;
+                v[a] = (INT || live) ? DLv[a * (RB + 1) + rs] : 0.0;
                 E[a] = DLs[a * (RB + 1) + rs] + sc0;            // scale of the exit of ring a
                 e = fmax(e, scale_of(v[a], E[a]));
             }
         }
         const double dd = d.y - KC[1];
         const double q0 = -((dd * dd) * KC[2]);           // KC[2] = 1/den: 1 ulp from the reference's division (bar here: 1e-6)
-        float fa = live ? (float)(sc0 + q0) : 0.0f;
-        float fb = live ? (float)(e + q0) : -INFINITY;
+        float fa = (INT || live) ? (float)(sc0 + q0) : 0.0f;
+        float fb = (INT || live) ? (float)(e + q0) : -INFINITY;
         scan_maxplus_f32(fa, fb);                         // the envelope is a scale: single precision
         const float Mf = (float)M;                        // exact: the carry is kept float-representable
         const float Mtf = fmaxf(Mf + fa, fb);
@@ -187,8 +224,10 @@ __global__ __launch_bounds__(64, N <= 4 ? 3 : (N <= 8 ? 2 : 1)) void kw_fwd(Wave
             Ea[a] = LOGDL ? E[a] : v[a] * E[a];
             be = __builtin_fma(Ea[a], KC[KPEND + a], be);
         }
-        al = live ? al : 1.0;
-        be = live ? be : 0.0;
+        if constexpr (!INT) {
+            al = live ? al : 1.0;
+            be = live ? be : 0.0;
+        }
         scan_linear(al, be);
         const double xt = __builtin_fma(al, x, be);
         const double xprev = lane_prev(xt, x);
@@ -224,8 +263,19 @@ __global__ __launch_bounds__(64, N <= 4 ? 3 : (N <= 8 ? 2 : 1)) void kw_fwd(Wave
         } else {
 #pragma unroll
             for (int a = 0; a < N; a++) {
+                const double sn = (ref + KC[KSC + a]) + d.R[a];
                 DLv[a * (RB + 1) + wsl] = u[a];
-                DLs[a * (RB + 1) + wsl] = (ref + KC[KSC + a]) + d.R[a];
+                DLs[a * (RB + 1) + wsl] = sn;
+                if constexpr (CARRY) { Vr[a] = u[a]; Sr[a] = sn; }
+            }
+        }
+        if constexpr (INT) {   // one uniform base per plane + the lane; the lanes from W up store nothing
+            const double la0 = Mt + flog(xt);
+            if (liveW) {
+                (FAc + tb)[lane] = la0;
+                (FRc + tb)[lane] = ref;
+#pragma unroll
+                for (int a = 0; a < N; a++) (FVc + (int64_t)a * T + tb)[lane] = u[a];
             }
         }
         if (MODE == 1) {
@@ -263,13 +313,17 @@ __global__ __launch_bounds__(64, N <= 4 ? 3 : (N <= 8 ? 2 : 1)) void kw_fwd(Wave
     auto sweep = [&](int from, int to, auto mode_tag) {
         FIn<N> buf[D];
 #pragma unroll
-        for (int i = 0; i < D; i++) load(buf[i], from + i * W);
+        for (int i = 0; i < D; i++) load(buf[i], from + i * W, mode_tag);
+        if constexpr (decltype(mode_tag)::value == 4 && fwd_carry(N)) {
+#pragma unroll
+            for (int a = 0; a < N; a++) { Vr[a] = DLv[a * (RB + 1) + rs]; Sr[a] = DLs[a * (RB + 1) + rs]; }
+        }
         int off = from;
         for (; off + D * W <= to; off += D * W) {
 #pragma unroll
             for (int i = 0; i < D; i++) {
                 run(buf[i], off + i * W, mode_tag);
-                load(buf[i], off + (i + D) * W);
+                load(buf[i], off + (i + D) * W, mode_tag);
             }
         }
 #pragma unroll
@@ -280,7 +334,17 @@ __global__ __launch_bounds__(64, N <= 4 ? 3 : (N <= 8 ? 2 : 1)) void kw_fwd(Wave
     const int n_rec = ((L + W - 1) / W) * W < n_warm ? ((L + W - 1) / W) * W : n_warm;
     if (n_warm - n_rec > 0) sweep(0, n_warm - n_rec, std::integral_constant<int, 0>());
     if (n_rec > 0) sweep(n_warm - n_rec, n_warm, std::integral_constant<int, 2>());
-    sweep(n_warm, n_total, std::integral_constant<int, 1>());
+    // the interior range [n_warm, n_int): the full owned steps (option "interior" = 0: none)
+    int n_int = n_warm;
+    if constexpr (HS_FWD_INT) {
+        if (g.interior && n_total > n_warm) n_int = n_warm + ((n_total - n_warm) / W) * W;
+    }
+    if (n_int > n_warm) {
+        imax = n_int - W;
+        if (fwd_carry(N) && W == L) sweep(n_warm, n_int, std::integral_constant<int, fwd_carry(N) ? 4 : 3>());
+        else sweep(n_warm, n_int, std::integral_constant<int, 3>());
+    }
+    if (n_total > n_int) sweep(n_int, n_total, std::integral_constant<int, 1>());
 }
 
 // ------------------------------------------------------------------------------------------
@@ -789,7 +853,7 @@ __global__ __launch_bounds__(64, N <= 4 ? HS_BWD_W4 : 1) void kw_bwd(WaveGeom g,
             const int64_t ohi = g.own_hi < tend ? g.own_hi : tend, olo = g.own_lo > tc ? g.own_lo : tc;
             int64_t dlo = te - ohi, dhi = te - 1 - W - olo;
             if (g.last && dlo < te - 1 - (T - L)) dlo = te - 1 - (T - L);
-            if (dhi >= dlo && dhi >= 0) {   // dlo >= 0: te >= tend; both at most n_total
+            if (g.interior && dhi >= dlo && dhi >= 0) {   // dlo >= 0: te >= tend; both at most n_total
                 const int x0 = (int)dlo - w0, x1 = (int)dhi - w0;
                 const int k0i = x0 > 0 ? 1 + (x0 + W - 1) / W : (x0 > -W ? 1 : 0);       // first k with start(k) >= dlo
                 const int k1i = x1 >= 0 ? 2 + x1 / W : (x1 >= -W ? 1 : 0);               // one past the last k with start(k) <= dhi

@@ -31,11 +31,23 @@
 #include <cmath>
 #include <type_traits>
 
+#include "fastmath.h"
 #include "wave_common.h"
 
 namespace hmmsort {
 
 constexpr double kVitTol = 1e-9;
+
+// Round 11: the parts of the interior form of the sweep, each 1 = on, 0 = the parent's form (A/B builds)
+#ifndef HS_VIT_INT
+#define HS_VIT_INT 1    // the full owned super-steps run without the bookkeeping of partial steps
+#endif
+#ifndef HS_DL_REG
+#define HS_DL_REG 1     // rings of at most 64 states: interior steps take the ring exits from registers, not from LDS
+#endif
+#ifndef HS_VIT_RCP
+#define HS_VIT_RCP 1    // the division by the chain's invariant 2 sigma^2: reciprocal once, exact quotient per sample
+#endif
 
 template <int N>
 struct WIn {
@@ -124,8 +136,23 @@ __device__ __forceinline__ void vit_chain(const WaveGeom &g, const WaveConst *__
     __syncthreads();
 
     const int n_total = (int)(tend - 1 - tinit);  // steps t = tinit+1 .. tend-1
+    // Interior super-steps (STORE = 2 and 3 of run): the FULL owned steps, nact = W.  A full step's loads never
+    // meet the clamp against T, every lane below W stores into the planes, and the carry leaves from lane W - 1.  The
+    // scans and lane_prev move data from lower to higher lanes only, so what the lanes from W up hold is read by no
+    // live lane: their inputs go unselected, and only what reaches memory (wsl, the psi stores) keeps its predicate.
+    // The input pipeline looks D steps past the range; the loads clamp that offset to its last step (imax).
+    const bool liveW = lane < W;
+    const int liW = liveW ? lane : 0;
+    int imax = 0;
     // inputs of the super-step that starts `off` steps into the sweep: uniform base + lane offset
-    auto load = [&](WIn<N> &d, int off) {
+    auto load = [&](WIn<N> &d, int off, auto store_tag) {
+        if constexpr (decltype(store_tag)::value >= 2) {
+            const int64_t tb = tinit + 1 + (off < imax ? off : imax);
+            d.y = (yc + tb)[liW];
+#pragma unroll
+            for (int a = 0; a < N; a++) d.R[a] = (Rc + (int64_t)a * T + tb)[liW];
+            return;
+        }
         const int nact = n_total - off < W ? n_total - off : W;
         const int li = lane < nact ? lane : 0;
         int64_t tb = tinit + 1 + off;
@@ -139,16 +166,36 @@ __device__ __forceinline__ void vit_chain(const WaveGeom &g, const WaveConst *__
     // lane, idle lanes of the last partial step into a trash line).  Straight-line global accesses only:
     // with stores under divergent branches hipcc drains vmcnt to 0 every super-step, which serialises the
     // input pipeline on the HBM latency.
+    // STORE = 2: interior super-step (above); 3: interior super-step of a ring with W == L, where rs and ws both
+    // advance by W with ws - rs = L, so lane j reads the slot it wrote one step earlier: the exits X_a come from the
+    // lane's own registers (Xr, primed from the delay line before the sweep).  Every LDS write stays, so the general
+    // modes and dump find the delay line as they left it.
+    [[maybe_unused]] double Xr[N];
+    // The interior form, the register carry and the reciprocal are for the sweep of every chain with one entry value
+    // per ring (UC), which is what every list the reference builds runs.  The re-sweep of a failed chain is held to
+    // 80 registers beside an E-step and the per-source kernels have no registers to spare (DESIGN section 5 Round 11:
+    // with these parts they spill); both are rare and keep the general form.
+    constexpr bool FAST = UC && !redo;
+    // the chain's one division (div_invariant, fastmath.h); wave-uniform, kept in scalar registers
+    [[maybe_unused]] DivInv dv;
+    if constexpr (FAST && HS_VIT_RCP) {
+        dv = div_invariant_of(cst[ch].den);
+        dv.den = wave_bcast(dv.den, 0); dv.r = wave_bcast(dv.r, 0); dv.nlo = wave_bcast(dv.nlo, 0);
+    }
     auto run = [&](const WIn<N> &d, int off, auto store_tag) {
         constexpr int STORE = decltype(store_tag)::value;
-        const int nact = n_total - off < W ? n_total - off : W;
-        const bool live = lane < nact;
+        constexpr bool INT = STORE >= 2, CARRY = STORE == 3;
+        const int nact = INT ? W : (n_total - off < W ? n_total - off : W);
+        const bool live = INT ? liveW : lane < nact;
         const int64_t tb = tinit + 1 + off;
         double X[N];
 #pragma unroll
         for (int a = 0; a < N; a++) {
-            const double v = DL[a * (RB + 1) + rs];
-            X[a] = live ? v : -INFINITY;
+            if constexpr (CARRY) X[a] = Xr[a];
+            else {
+                const double v = DL[a * (RB + 1) + rs];
+                X[a] = (INT || live) ? v : -INFINITY;
+            }
         }
         // ring exits into the silent state: best and runner-up among the rings (first maximum wins)
         double e1 = -INFINITY, e2 = -INFINITY;
@@ -162,9 +209,11 @@ __device__ __forceinline__ void vit_chain(const WaveGeom &g, const WaveConst *__
         }
         const double c00 = KC[0];
         const double dd = d.y - KC[1];
-        const double q0 = -((dd * dd) / KC[2]);
-        double sa = live ? c00 + q0 : 0.0;
-        double sb = live ? e1 + q0 : -INFINITY;
+        double q0;
+        if constexpr (FAST && HS_VIT_RCP) q0 = -div_invariant(dd * dd, dv);
+        else q0 = -((dd * dd) / KC[2]);
+        double sa = (INT || live) ? c00 + q0 : 0.0;
+        double sb = (INT || live) ? e1 + q0 : -INFINITY;
         scan_maxplus(sa, sb);
         const double Dn = fmax(D0 + sa, sb);
         const double Dprev = lane_prev(Dn, D0);
@@ -220,12 +269,19 @@ __device__ __forceinline__ void vit_chain(const WaveGeom &g, const WaveConst *__
             const double u = ring ? r1 : v0;
             const double gap = ring ? r1 - fmax(r2, v0) : v0 - r1;
             const uint32_t fl = gap < thr ? 1u : 0u;
-            DL[a * (RB + 1) + wsl] = u + d.R[a];
+            const double P = u + d.R[a];
+            DL[a * (RB + 1) + wsl] = P;
+            if constexpr (CARRY) Xr[a] = P;
             const uint32_t ent = (ring ? (uint32_t)rarg : 0u) | (fl << (EB - 1));
             pw[(a + 1) / EPW] |= ent << (((a + 1) % EPW) * EB);
             if (!UC) __builtin_amdgcn_sched_barrier(0);   // keep the junctions sequential: N^2 live candidates otherwise
         }
-        if (STORE) {
+        if constexpr (INT) {   // one uniform base per plane + the lane; the lanes from W up store nothing
+            if (liveW) {
+#pragma unroll
+                for (int w = 0; w < PW; w++) (psic + w * planePsi + tb)[lane] = pw[w];
+            }
+        } else if (STORE) {
 #pragma unroll
             for (int w = 0; w < PW; w++) {
                 uint32_t *dst = live ? psic + w * planePsi + tb + lane : trash + lane;
@@ -253,13 +309,17 @@ __device__ __forceinline__ void vit_chain(const WaveGeom &g, const WaveConst *__
     auto sweep = [&](int from, int to, auto store_tag) {
         WIn<N> buf[D];
 #pragma unroll
-        for (int i = 0; i < D; i++) load(buf[i], from + i * W);
+        for (int i = 0; i < D; i++) load(buf[i], from + i * W, store_tag);
+        if constexpr (decltype(store_tag)::value == 3) {
+#pragma unroll
+            for (int a = 0; a < N; a++) Xr[a] = DL[a * (RB + 1) + rs];
+        }
         int off = from;
         for (; off + D * W <= to; off += D * W) {
 #pragma unroll
             for (int i = 0; i < D; i++) {
                 run(buf[i], off + i * W, store_tag);
-                load(buf[i], off + (i + D) * W);
+                load(buf[i], off + (i + D) * W, store_tag);
             }
         }
 #pragma unroll
@@ -271,7 +331,18 @@ __device__ __forceinline__ void vit_chain(const WaveGeom &g, const WaveConst *__
         sweep(0, n_warm, std::integral_constant<int, 0>());
         dump(vpre + cg * SR, tc);
     }
-    sweep(n_warm, n_total, std::integral_constant<int, 1>());
+    // the interior range [n_warm, n_int): the full owned steps (option "interior" = 0: none)
+    int n_int = n_warm;
+    if constexpr (FAST && HS_VIT_INT) {
+        if (g.interior && n_total > n_warm) n_int = n_warm + ((n_total - n_warm) / W) * W;
+    }
+    if (n_int > n_warm) {
+        imax = n_int - W;
+        constexpr bool CARRY_OK = HS_DL_REG && FAST && N <= 8;
+        if (CARRY_OK && W == L) sweep(n_warm, n_int, std::integral_constant<int, CARRY_OK ? 3 : 2>());
+        else sweep(n_warm, n_int, std::integral_constant<int, 2>());
+    }
+    if (n_total > n_int) sweep(n_int, n_total, std::integral_constant<int, 1>());
     dump(vend + cg * SR, tend);
     if (redo) {  // the hand-off was exact by construction
         for (int i = lane; i < SR; i += 64) vpre[cg * SR + i] = vend[(cg - 1) * SR + i];

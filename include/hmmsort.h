@@ -82,7 +82,10 @@ int hmmsort_set_device(int device);
  *       whose margins are inside the reference's own rounding noise; hmmsort_last_error has the text;
  *       after a chunked decode: the retries summed over all chunks and channels), "fit_streams" (channels one
  *       worker of hmmsort_fit_channels keeps in flight, each on a stream of its own: default 4, the runtime's
- *       default number of hardware queues; 1..16, HMMSORT_EINVAL outside).
+ *       default number of hardware queues; 1..16, HMMSORT_EINVAL outside), "interior" (test aid of the wave
+ *       engine, read when a plan is created: 1, the default, lets the forward, Viterbi and backward sweeps run
+ *       the full super-steps they own in their interior form; 0 runs every super-step in the general form;
+ *       the results are the same bit for bit; 0 or 1, HMMSORT_EINVAL outside).
  * Process-wide defaults behind a mutex; an entry point works on the snapshot it takes when it starts,
  * so options may be changed while other host threads are inside the library.  hmmsort_last_error is
  * per thread. */
