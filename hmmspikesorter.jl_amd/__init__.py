@@ -11,6 +11,8 @@ from .api import (Correlograms, Footprints, HMMSpikeTemplateModel, HMMSpikingMod
                   backward, extract_spiketimes, fit, fit_adaptive, fit_channels, fit_step_channels, forward, get_energy,
                   quality_from_summary, spike_fit, unit_quality, correlograms, duplicate_units, footprints, unit_locations,
                   footprint_similarity, resolve_duplicates,
+                  Isolation, SnippetFeatures, cluster_isolation, isolation_scores, pca_basis, snippet_features,
+                  unassigned_events, unit_gaussians,
                   Whitening, channel_mix, noise_covariance, noise_sums, whiten, whitening_matrix,
                   posterior_decode, posteriors, predict, design_fir, preprocess, reconstruct_signal, reconstruct_tracked, seed_templates, spike_confidence, train_model, train_step, unroll_mlseq, update,
                   viterbi, viterbi_step)
@@ -31,4 +33,6 @@ __all__ = ["StateMatrix", "HMMSpikeTemplateModel", "HMMSpikingModel", "forward",
            "learn_templates", "SpikeFit", "UnitQuality", "spike_fit", "unit_quality", "quality_from_summary",
            "get_energy", "Correlograms", "correlograms", "duplicate_units", "design_fir", "preprocess", "Footprints",
            "footprints", "unit_locations", "footprint_similarity", "resolve_duplicates", "Whitening", "channel_mix",
-           "noise_covariance", "noise_sums", "whiten", "whitening_matrix"]
+           "noise_covariance", "noise_sums", "whiten", "whitening_matrix", "Isolation", "SnippetFeatures",
+           "cluster_isolation", "isolation_scores", "pca_basis", "snippet_features", "unassigned_events",
+           "unit_gaussians"]

@@ -101,6 +101,26 @@ class FpOut(C.Structure):
     _fields_ = [("sum", _vp), ("sumsq", _vp), ("nused", _vp), ("n", _vp)]
 
 
+class FeatOpt(C.Structure):
+    """struct hmmsort_feat_opt: the footprints' window and ONE channel row [M] for all units, the components per slot,
+    the host basis [M][P][W] and centre [M][W] (each may be NULL) and the moments mode (0, 1, 2)"""
+    _fields_ = [("pre", _i64), ("W", _i64), ("M", _i64), ("chan", _vp), ("P", _i64), ("basis", _vp), ("centre", _vp),
+                ("moments", _i64)]
+
+
+class FeatOut(C.Structure):
+    """struct hmmsort_feat_out: feat / used (host arrays in the host form, device memory otherwise; cap_rows: what
+    they hold, plan form), host n (required) and nused, and the host moments of mode 1 (b1, b2) or 2 (g1, g2)"""
+    _fields_ = [("feat", _vp), ("used", _vp), ("cap_rows", _i64), ("n", _vp), ("nused", _vp), ("b1", _vp), ("b2", _vp),
+                ("g1", _vp), ("g2", _vp)]
+
+
+class IsoOut(C.Structure):
+    """struct hmmsort_iso_out: host arrays hmmsort_cluster_isolation fills ([U] doubles, [U][U] int64, [U][U] doubles;
+    each may be NULL)"""
+    _fields_ = [("iso_d2", _vp), ("closer", _vp), ("lpair", _vp)]
+
+
 class PreOpt(C.Structure):
     """struct hmmsort_pre_opt: half filter (taps NULL: none), reference mode, group id per channel (NULL: one group)
     and, in the host form, the rows to return (NULL: all)"""
@@ -125,6 +145,7 @@ PRE_MAX_HALF, PRE_MAX_CHANNELS, PRE_MAX_GROUP = 4096, 1024, 64
 CCG_MAX_UNITS, CCG_MAX_HALF_BINS = 4096, 2048
 FP_MAX_UNITS, FP_MAX_W, FP_MAX_SLOTS = 4096, 1024, 1024
 WHITEN_MAX_CHANNELS, WHITEN_MAX_GUARD = 1024, 65536
+FEAT_MAX_P1, FEAT_MAX_F2 = 128, 64
 
 # name -> (restype, argtypes); every symbol include/hmmsort.h declares
 SIGNATURES = {
@@ -215,6 +236,13 @@ SIGNATURES = {
                                   C.POINTER(FpOut)]),
     "hmmsort_footprints_device": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, C.POINTER(FpOpt), C.POINTER(FpOut), _vp]),
     "hmmsort_plan_footprints": (_int, [_vp, _vp, _vp, _i64, C.POINTER(FpOpt), C.POINTER(FpOut), _vp]),
+    "hmmsort_snippet_features": (_int, [_vp, _int, _i64, _i64, _i64, C.POINTER(_vp), _vp, C.POINTER(FeatOpt),
+                                        C.POINTER(FeatOut)]),
+    "hmmsort_snippet_features_device": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, C.POINTER(FeatOpt), C.POINTER(FeatOut),
+                                               _vp]),
+    "hmmsort_plan_snippet_features": (_int, [_vp, _vp, _vp, _i64, C.POINTER(FeatOpt), C.POINTER(FeatOut), _vp]),
+    "hmmsort_cluster_isolation": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, C.POINTER(IsoOut)]),
+    "hmmsort_cluster_isolation_device": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, C.POINTER(IsoOut), _vp]),
     "hmmsort_plan_profile": (_int, [_vp, _int]),
     "hmmsort_plan_profile_read": (_int, [_vp, _vp, C.c_char_p, _i64, C.POINTER(_f64), _pi64, _i64,
                                          _pi64]),

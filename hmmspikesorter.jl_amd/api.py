@@ -1462,3 +1462,220 @@ def spike_confidence(model, jitter=2):
         return plan.spike_confidence(dx, jitter)
     finally:
         plan.close()
+
+
+# ---- waveform features and cluster isolation (an extension; include/hmmsort.h) ------------------------
+
+@dataclass
+class SnippetFeatures:
+    """What hmmsort_snippet_features returns for U units: one row of F features per list entry, rows in unit order
+    (entry e of unit u is row offs[u] + e), and the moments the mode asked for."""
+    features: object          # [n_total, F] (numpy; a device tensor from device.snippet_features) or None
+    used: object              # [n_total] uint8, likewise, or None
+    n: np.ndarray             # [U]: list entries per unit
+    n_used: np.ndarray        # [U]: entries whose window lies inside the block
+    b1: np.ndarray = None     # moments = 1: [U, M, P], [U, M, P, P]
+    b2: np.ndarray = None
+    g1: np.ndarray = None     # moments = 2: [U, F], [U, F, F]
+    g2: np.ndarray = None
+
+    @property
+    def offs(self):
+        return np.concatenate([[0], np.cumsum(self.n)]).astype(np.int64)
+
+
+def _feat_args(U, nC, pre, W, channels, basis, centre, moments):
+    """-> (hmmsort_feat_opt, hmmsort_feat_out, arrays, (M, P, F)): the option record and the host outputs of a features
+    call on a block of nC channels.  Sizes the library refuses get token arrays: it checks before it writes, and its
+    message says what is wrong."""
+    pre, W, moments = int(pre), int(W), int(moments)
+    chan = None if channels is None else np.ascontiguousarray(channels, dtype=np.int32).ravel()
+    M = nC if chan is None else len(chan)
+    P = W
+    if basis is not None:
+        basis = np.ascontiguousarray(basis, dtype=np.float64)
+        if basis.ndim != 3 or basis.shape[0] != M or basis.shape[2] != W:
+            raise ValueError("snippet_features: basis must be [M = %d][P][W = %d], got %s" % (M, W, basis.shape))
+        P = basis.shape[1]
+    if centre is not None:
+        centre = np.ascontiguousarray(centre, dtype=np.float64)
+        if centre.shape != (M, W):
+            raise ValueError("snippet_features: centre must be [M = %d][W = %d], got %s" % (M, W, centre.shape))
+    F = M * P
+    ok = (1 <= U <= _lib.FP_MAX_UNITS and M >= 1 and W >= 1
+          and (moments != 1 or (P <= _lib.FEAT_MAX_P1 and U * M * P * P <= 1 << 26))
+          and (moments != 2 or (F <= _lib.FEAT_MAX_F2 and U * F * F <= 1 << 26)))
+    Ua, Ma, Pa = (U, M, P) if ok else (1, 1, 1)
+    arr = {"n": np.zeros(Ua, dtype=np.int64), "nused": np.zeros(Ua, dtype=np.int64)}
+    if moments == 1:
+        arr["b1"], arr["b2"] = np.zeros((Ua, Ma, Pa)), np.zeros((Ua, Ma, Pa, Pa))
+    if moments == 2:
+        arr["g1"], arr["g2"] = np.zeros((Ua, Ma * Pa)), np.zeros((Ua, Ma * Pa, Ma * Pa))
+    opt = _lib.FeatOpt(pre, W, M, ptr(chan), max(P, 1) if basis is not None else 1, ptr(basis), ptr(centre), moments)
+    out = _lib.FeatOut(None, None, 0, ptr(arr["n"]), ptr(arr["nused"]), ptr(arr.get("b1")), ptr(arr.get("b2")),
+                       ptr(arr.get("g1")), ptr(arr.get("g2")))
+    arr["_keep"] = (chan, basis, centre)
+    return opt, out, arr, (M, P, F)
+
+
+def _host_block(block, who):
+    y = np.asarray(block)
+    if y.ndim == 1:
+        y = y[None, :]
+    if y.ndim != 2:
+        raise ValueError(who + ": block must be channels x samples")
+    raw = y.dtype == np.int16
+    return np.ascontiguousarray(y, dtype=np.int16 if raw else np.float64), \
+        (_lib.SAMPLES_I16 if raw else _lib.SAMPLES_F64)
+
+
+def snippet_features(block, units, pre=20, W=60, channels=None, basis=None, centre=None, moments=0, features=True):
+    """snippet_features(block, units; pre, W, channels, basis, centre, moments, features) -> SnippetFeatures (an
+    extension, INTEGRATION.md "Isolation"; hmmsort_snippet_features).  `block` and `units` as footprints takes them;
+    `channels`: None for all channels or ONE list of block channels for every unit.  Without a basis a row is the
+    spike's snippets on the listed channels minus `centre` (None: the snippets themselves -- the export); with
+    `basis` [M][P][W] it is the P projections per channel.  `moments`: 0 none, 1 the per-channel sums b1 / b2 (what
+    pca_basis takes), 2 the per-unit sums g1 / g2 over whole rows.  features=False skips the rows."""
+    y, stype = _host_block(block, "snippet_features")
+    lists = _time_lists(units)
+    U = len(lists)
+    nC, T = y.shape
+    opt, out, arr, (M, P, F) = _feat_args(U, nC, pre, W, channels, basis, centre, moments)
+    n_total = sum(len(t) for t in lists)
+    feat = used = None
+    if features:
+        fits = n_total * F <= 1 << 31
+        feat = np.zeros((n_total if fits else 1, F if fits else 1))
+        used = np.zeros(n_total if fits else 1, dtype=np.uint8)
+        out.feat, out.used = feat.ctypes.data, used.ctypes.data
+    ptrs = (C.c_void_p * max(U, 1))(*[t.ctypes.data if len(t) else None for t in lists])
+    cnt = np.array([len(t) for t in lists] + [0] * (U == 0), dtype=np.int64)
+    check(lib().hmmsort_snippet_features(ptr(y), stype, nC, T, U, ptrs, ptr(cnt), C.byref(opt), C.byref(out)))
+    return SnippetFeatures(feat, used, arr["n"], arr["nused"], arr.get("b1"), arr.get("b2"), arr.get("g1"),
+                           arr.get("g2"))
+
+
+def pca_basis(b1, b2, n_used, P=3):
+    """pca_basis(b1 [U, M, W], b2 [U, M, W, W], n_used [U]; P) -> (basis [M, P, W], centre [M, W]): per channel slot
+    the mean snippet and the top P principal axes of the snippets of all units pooled (the sums of
+    snippet_features(..., moments=1) without a basis), by decreasing variance, each with the sign that makes its
+    largest-magnitude component positive.  Host code (numpy.linalg.eigh of M matrices W x W)."""
+    b1, b2 = np.asarray(b1, dtype=np.float64), np.asarray(b2, dtype=np.float64)
+    n = float(np.sum(n_used))
+    _, M, W = b1.shape
+    P = int(P)
+    if not 1 <= P <= W:
+        raise ValueError("pca_basis: P = %d components of a window of %d samples" % (P, W))
+    if n < 1:
+        raise ValueError("pca_basis: no used spike")
+    centre = b1.sum(axis=0) / n
+    basis = np.zeros((M, P, W))
+    for m in range(M):
+        cov = b2[:, m].sum(axis=0) / n - np.outer(centre[m], centre[m])
+        _, vec = np.linalg.eigh(0.5 * (cov + cov.T))
+        for p in range(P):
+            v = vec[:, W - 1 - p]
+            basis[m, p] = v if v[np.argmax(np.abs(v))] > 0 else -v
+    return basis, centre
+
+
+def unit_gaussians(g1, g2, n_used):
+    """unit_gaussians(g1 [U, F], g2 [U, F, F], n_used [U]) -> (mu [U, F], Vinv [U, F, F]): per unit the feature mean
+    and the inverse of the sample covariance (g2 / n - mu mu') n / (n - 1).  A unit with n_used <= F or a singular
+    covariance is marked not scored: Vinv[u, 0, 0] = NaN, the rest zeros (hmmsort_cluster_isolation's convention)."""
+    g1, g2 = np.asarray(g1, dtype=np.float64), np.asarray(g2, dtype=np.float64)
+    U, F = g1.shape
+    mu, vinv = np.zeros((U, F)), np.zeros((U, F, F))
+    for u in range(U):
+        n = float(n_used[u])
+        ok = n > F
+        if ok:
+            m = g1[u] / n
+            cov = (g2[u] / n - np.outer(m, m)) * (n / (n - 1.0))
+            try:
+                inv = np.linalg.inv(cov)
+                ok = bool(np.all(np.isfinite(inv))) and np.linalg.cond(cov) < 1.0 / np.finfo(np.float64).eps
+            except np.linalg.LinAlgError:
+                ok = False
+        if ok:
+            mu[u], vinv[u] = m, inv
+        else:
+            vinv[u, 0, 0] = np.nan
+    return mu, vinv
+
+
+def _iso_run(call, U):
+    """call(byref(hmmsort_iso_out)) -> rc into (iso_d2 [U], closer [U, U], lpair [U, U])"""
+    Ua = U if 1 <= U <= _lib.FP_MAX_UNITS else 1
+    d2, closer, lpair = np.zeros(Ua), np.zeros((Ua, Ua), dtype=np.int64), np.zeros((Ua, Ua))
+    out = _lib.IsoOut(ptr(d2), ptr(closer), ptr(lpair))
+    check(call(C.byref(out)))
+    return d2, closer, lpair
+
+
+def isolation_scores(features, offs, mu, Vinv, used=None):
+    """isolation_scores(features [n, F], offs [U + 1], mu [U, F], Vinv [U, F, F]; used [n]) -> (iso_d2 [U],
+    closer [U, U], lpair [U, U]): hmmsort_cluster_isolation as it is, for rows and Gaussians the caller made."""
+    f = np.ascontiguousarray(features, dtype=np.float64)
+    offs = np.ascontiguousarray(offs, dtype=np.int64).ravel()
+    mu, Vinv = np.ascontiguousarray(mu, dtype=np.float64), np.ascontiguousarray(Vinv, dtype=np.float64)
+    U = len(offs) - 1
+    n, F = (int(f.shape[0]), int(f.shape[1])) if f.ndim == 2 else (0, 0)
+    if mu.shape != (U, F) or Vinv.shape != (U, F, F):
+        raise ValueError("isolation_scores: mu must be [%d][%d] and Vinv [%d][%d][%d]" % (U, F, U, F, F))
+    u8 = None if used is None else np.ascontiguousarray(used, dtype=np.uint8).ravel()
+    if u8 is not None and len(u8) != n:
+        raise ValueError("isolation_scores: used has %d entries, features %d rows" % (len(u8), n))
+    return _iso_run(lambda out: lib().hmmsort_cluster_isolation(ptr(f), n, F, U, ptr(offs), ptr(u8), ptr(mu),
+                                                                ptr(Vinv), out), U)
+
+
+@dataclass
+class Isolation:
+    """cluster_isolation's result for U units in a space of F = M P features."""
+    distance: np.ndarray      # [U]: isolation distance (squared Mahalanobis distance of the n_used-th nearest
+                              # non-member spike); NaN for a unit that is not scored or has too few non-members
+    l_ratio: np.ndarray       # [U]: sum over the non-member spikes of Q_F(d2) / n_used; NaN when not scored
+    lpair: np.ndarray         # [U, U]: the L-ratio's sum, split by the unit the spikes belong to
+    closer: np.ndarray        # [U, U] int64: spikes of v nearer to u than to v; -1 when either is not scored
+    n_used: np.ndarray        # [U]
+    basis: np.ndarray         # [M, P, W]
+    centre: np.ndarray        # [M, W]
+    features: object = None   # [n_total, F] when asked for
+
+
+def _isolation_result(d2, closer, lpair, n_used, basis, centre, features):
+    nu = np.asarray(n_used, dtype=np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        lr = np.where(nu > 0, lpair.sum(axis=1) / nu, np.nan)
+    return Isolation(d2, lr, lpair, closer, np.asarray(n_used), basis, centre, features)
+
+
+def cluster_isolation(block, units, pre=20, W=60, channels=None, P=3, keep_features=False):
+    """cluster_isolation(block, units; pre, W, channels, P) -> Isolation (an extension, INTEGRATION.md "Isolation"):
+    isolation distance and L-ratio (Schmitzer-Torbert et al. 2005) of every unit against the spikes of all the other
+    lists, in the space of the top P principal components of the snippets on each listed channel.  Pass the detected
+    events no unit explains (unassigned_events) as one more list to give the units a noise cluster to be isolated
+    from.  Two passes over the block on the device (snippet moments; projections and their moments), the PCA and the
+    F x F inverses on the host, the distances, the order statistic and the sums on the device."""
+    lists = _time_lists(units)
+    p1 = snippet_features(block, lists, pre, W, channels, moments=1, features=False)
+    basis, centre = pca_basis(p1.b1, p1.b2, p1.n_used, P)
+    p2 = snippet_features(block, lists, pre, W, channels, basis, centre, moments=2)
+    mu, vinv = unit_gaussians(p2.g1, p2.g2, p2.n_used)
+    d2, closer, lpair = isolation_scores(p2.features, p2.offs, mu, vinv, p2.used)
+    return _isolation_result(d2, closer, lpair, p2.n_used, basis, centre, p2.features if keep_features else None)
+
+
+def unassigned_events(events, units, tol=10):
+    """unassigned_events(events, units, tol) -> the entries of `events` (sample numbers, e.g. seed_templates' detected
+    events) that lie within `tol` samples of no spike of any unit, ascending and without repeats.  Host numpy."""
+    ev = np.unique(np.asarray(events, dtype=np.int64).ravel())
+    lists = _time_lists(units)
+    spikes = np.sort(np.concatenate(lists + [np.zeros(0, dtype=np.int64)]))
+    if len(spikes) == 0 or len(ev) == 0:
+        return ev
+    i = np.searchsorted(spikes, ev)
+    left = np.abs(ev - spikes[np.maximum(i - 1, 0)])
+    right = np.abs(spikes[np.minimum(i, len(spikes) - 1)] - ev)
+    return ev[np.minimum(left, right) > int(tol)]

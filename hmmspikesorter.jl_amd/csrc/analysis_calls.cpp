@@ -1,6 +1,6 @@
 // Analysis entry points of libhmmsort_hip.so (include/hmmsort.h): what works on a recording, a decoded path or spike
 // lists without the escalation ladder -- sample widening, the front end, whitening, reconstruct / unroll / extract,
-// spike confidence, the per-spike fit, the template seed, correlograms and footprints, each in its host, device and
+// spike confidence, the per-spike fit, the template seed, correlograms, footprints, features and isolation, each in its host, device and
 // plan forms -- and the host staging they share.  Every call checks its arguments before it asks for a device, keeps
 // no plan and no cached slot, and has no CPU compute path.
 #include <algorithm>
@@ -728,6 +728,111 @@ int hmmsort_plan_footprints(hmmsort_plan *p, const int16_t *d_x, const double *d
     PlanUnits pu;
     if ((rc = plan_compact_units(p, d_x, (hipStream_t)stream, &pu))) return rc;
     return dev_footprints(d_block, Cb, p->T, U, pu.dt.as<int64_t>(), pu.offs.data(), opt, out, (hipStream_t)stream);
+}
+
+// ---- features and isolation (features.hip) ----------------------------------------------------------
+// The forms differ in where the block, the lists and the rows live; the rules are one (feat_check, iso_check).
+
+int hmmsort_snippet_features_device(const double *d_y, int64_t C, int64_t T, int64_t U, const int64_t *d_times,
+                                    const int64_t *offs, const hmmsort_feat_opt *opt, hmmsort_feat_out *out,
+                                    void *stream)
+{
+    HS_CHECK(d_y && offs, HMMSORT_EINVAL, "snippet_features_device: null argument (d_y and offs are required)");
+    FeatDims dm;
+    int rc = feat_check("snippet_features_device", C, T, U, opt, out, &dm);
+    if (rc) return rc;
+    HS_CHECK(offs[0] >= 0, HMMSORT_EINVAL, "snippet_features_device: offs[0] = %lld", (long long)offs[0]);
+    for (int64_t u = 0; u < U; u++)
+        HS_CHECK(offs[u + 1] >= offs[u], HMMSORT_EINVAL, "snippet_features_device: offs: unit %lld has a count of "
+                 "%lld", (long long)u, (long long)(offs[u + 1] - offs[u]));
+    HS_CHECK(d_times || offs[U] == offs[0], HMMSORT_EINVAL, "snippet_features_device: null d_times");
+    if ((rc = feat_check_rows("snippet_features_device", offs[U] - offs[0], dm.F))) return rc;
+    if ((rc = need_device())) return rc;
+    return dev_snippet_features(d_y, C, T, U, d_times, offs, opt, out, dm, out->feat, out->used, (hipStream_t)stream);
+}
+
+int hmmsort_snippet_features(const void *y, int sample_type, int64_t C, int64_t T, int64_t U,
+                             const int64_t *const *times, const int64_t *counts, const hmmsort_feat_opt *opt,
+                             hmmsort_feat_out *out)
+{
+    HS_CHECK(y && times && counts, HMMSORT_EINVAL, "snippet_features: null argument (y, times and counts are "
+             "required)");
+    FeatDims dm;
+    int rc = check_sample_type("snippet_features", sample_type);
+    if (rc) return rc;
+    if ((rc = feat_check("snippet_features", C, T, U, opt, out, &dm))) return rc;
+    std::vector<int64_t> offs;
+    DevBuf dy, dt, df, du;
+    if ((rc = check_unit_lists("snippet_features", U, times, counts, offs))) return rc;
+    const int64_t n = offs[(size_t)U];
+    if ((rc = feat_check_rows("snippet_features", n, dm.F))) return rc;
+    if ((rc = need_device())) return rc;
+    if ((rc = upload_samples_f64(y, sample_type, (size_t)C * (size_t)T, dy))) return rc;
+    if ((rc = upload_unit_lists(U, times, counts, offs, dt))) return rc;
+    if (out->feat && (rc = df.alloc((size_t)(n * dm.F) * sizeof(double)))) return rc;
+    if (out->used && (rc = du.alloc((size_t)n))) return rc;
+    if ((rc = dev_snippet_features(dy.as<double>(), C, T, U, dt.as<int64_t>(), offs.data(), opt, out, dm,
+                                   df.as<double>(), du.as<unsigned char>(), nullptr)))
+        return rc;
+    if (out->feat && n > 0) HS_HIP(hipMemcpy(out->feat, df.p, (size_t)(n * dm.F) * sizeof(double), hipMemcpyDeviceToHost));
+    if (out->used && n > 0) HS_HIP(hipMemcpy(out->used, du.p, (size_t)n, hipMemcpyDeviceToHost));
+    return HMMSORT_OK;
+}
+
+int hmmsort_plan_snippet_features(hmmsort_plan *p, const int16_t *d_x, const double *d_block, int64_t Cb,
+                                  const hmmsort_feat_opt *opt, hmmsort_feat_out *out, void *stream)
+{
+    HS_CHECK(p && d_x && d_block, HMMSORT_EINVAL, "plan_snippet_features: null argument (the plan, d_x and d_block "
+             "are required)");
+    const int64_t N = p->model.N, U = p->C * N;
+    HS_CHECK(N <= 32, HMMSORT_EINVAL, "plan_snippet_features: more than 32 templates");
+    FeatDims dm;
+    int rc = feat_check("plan_snippet_features", Cb, p->T, U, opt, out, &dm);
+    if (rc) return rc;
+    HS_CHECK(!(out->feat || out->used) || out->cap_rows >= 0, HMMSORT_EINVAL, "plan_snippet_features: cap_rows = %lld",
+             (long long)out->cap_rows);
+    if ((rc = need_device())) return rc;
+    PlanUnits pu;
+    if ((rc = plan_compact_units(p, d_x, (hipStream_t)stream, &pu))) return rc;
+    const int64_t n = pu.offs[(size_t)U];
+    if ((rc = feat_check_rows("plan_snippet_features", n, dm.F))) {
+        (void)hipStreamSynchronize((hipStream_t)stream);   // the compaction's copies read `pu`
+        return rc;
+    }
+    const bool fits = out->cap_rows >= n;
+    return dev_snippet_features(d_block, Cb, p->T, U, pu.dt.as<int64_t>(), pu.offs.data(), opt, out, dm,
+                                fits ? out->feat : nullptr, fits ? out->used : nullptr, (hipStream_t)stream);
+}
+
+int hmmsort_cluster_isolation_device(const double *d_feat, int64_t n, int64_t F, int64_t U, const int64_t *offs,
+                                     const unsigned char *d_used, const double *mu, const double *Vinv,
+                                     hmmsort_iso_out *out, void *stream)
+{
+    std::vector<unsigned char> scored;
+    int rc = iso_check("cluster_isolation_device", n, F, U, offs, mu, Vinv, out, &scored);
+    if (rc) return rc;
+    HS_CHECK(d_feat || n == 0, HMMSORT_EINVAL, "cluster_isolation_device: null d_feat");
+    if ((rc = need_device())) return rc;
+    return dev_cluster_isolation(d_feat, n, F, U, offs, d_used, mu, Vinv, scored, out, (hipStream_t)stream);
+}
+
+int hmmsort_cluster_isolation(const double *feat, int64_t n, int64_t F, int64_t U, const int64_t *offs,
+                              const unsigned char *used, const double *mu, const double *Vinv, hmmsort_iso_out *out)
+{
+    std::vector<unsigned char> scored;
+    int rc = iso_check("cluster_isolation", n, F, U, offs, mu, Vinv, out, &scored);
+    if (rc) return rc;
+    HS_CHECK(feat || n == 0, HMMSORT_EINVAL, "cluster_isolation: null feat");
+    if ((rc = need_device())) return rc;
+    DevBuf df, du;
+    if ((rc = df.alloc((size_t)(n * F) * sizeof(double)))) return rc;
+    if (n > 0) HS_HIP(hipMemcpy(df.p, feat, (size_t)(n * F) * sizeof(double), hipMemcpyHostToDevice));
+    if (used) {
+        if ((rc = du.alloc((size_t)n))) return rc;
+        if (n > 0) HS_HIP(hipMemcpy(du.p, used, (size_t)n, hipMemcpyHostToDevice));
+    }
+    return dev_cluster_isolation(df.as<double>(), n, F, U, offs, used ? du.as<unsigned char>() : nullptr, mu, Vinv,
+                                 scored, out, nullptr);
 }
 
 }  // extern "C"

@@ -354,6 +354,25 @@ int fp_check(const char *who, int64_t C, int64_t T, int64_t U, const hmmsort_fp_
              int64_t *M_out);
 int dev_footprints(const double *d_y, int64_t C, int64_t T, int64_t U, const int64_t *d_times, const int64_t *offs,
                    const hmmsort_fp_opt *opt, const hmmsort_fp_out *out, hipStream_t st);
+// features and isolation (features.hip; rules in include/hmmsort.h).  feat_check is what the three feature entry points
+// refuse before any GPU work and the sizes that follow (M slots, P components per slot, F = M P); feat_check_rows the
+// one refusal that needs the number of rows.  dev_snippet_features takes the block and lists as dev_footprints does,
+// d_feat / d_used device memory or null, fills the host arrays of `out` (its feat / used are not read) and
+// synchronises st.  iso_check / dev_cluster_isolation: the same split for the isolation; `scored` is per unit.
+struct FeatDims {
+    int64_t M, P, F;
+};
+int feat_check(const char *who, int64_t C, int64_t T, int64_t U, const hmmsort_feat_opt *opt,
+               const hmmsort_feat_out *out, FeatDims *d);
+int feat_check_rows(const char *who, int64_t n_total, int64_t F);
+int dev_snippet_features(const double *d_y, int64_t C, int64_t T, int64_t U, const int64_t *d_times,
+                         const int64_t *offs, const hmmsort_feat_opt *opt, const hmmsort_feat_out *out,
+                         const FeatDims &dm, double *d_feat, unsigned char *d_used, hipStream_t st);
+int iso_check(const char *who, int64_t n, int64_t F, int64_t U, const int64_t *offs, const double *mu,
+              const double *vinv, const hmmsort_iso_out *out, std::vector<unsigned char> *scored);
+int dev_cluster_isolation(const double *d_feat, int64_t n, int64_t F, int64_t U, const int64_t *offs,
+                          const unsigned char *d_used, const double *mu, const double *vinv,
+                          const std::vector<unsigned char> &scored, const hmmsort_iso_out *out, hipStream_t st);
 
 }  // namespace hmmsort
 

@@ -5,6 +5,7 @@ import ctypes as C
 
 import numpy as np
 
+from . import _lib
 from ._lib import TRANS_DTYPE, check, lib, ptr
 
 
@@ -181,6 +182,91 @@ def footprints(d_block, d_times, offs, pre=20, W=60, channels=None, stream=None)
     return _fp_run(lambda opt, out: lib().hmmsort_footprints_device(_dptr(d_block), nC, T, U, _dptr(d_times),
                                                                     ptr(offs), opt, out, C.c_void_p(stream)),
                    U, nC, pre, W, channels)
+
+
+def _feat_device_run(call, U, nC, n_total, pre, W, channels, basis, centre, moments, features, like):
+    """call(byref(opt), byref(out)) -> rc with device rows: the SnippetFeatures of a device or plan features call.
+    n_total None: the plan form, which learns the rows from a first call without them"""
+    import torch
+    from .api import SnippetFeatures, _feat_args
+    opt, out, arr, (M, P, F) = _feat_args(U, nC, pre, W, channels, basis, centre, moments)
+    if n_total is None and features:
+        first = _lib.FeatOpt(opt.pre, opt.W, opt.M, opt.chan, opt.P, opt.basis, opt.centre, 0)
+        check(call(C.byref(first), C.byref(out)))
+        n_total = int(arr["n"].sum())
+    d_feat = d_used = None
+    if features and n_total * F <= 1 << 31:
+        d_feat = torch.zeros((n_total, F), dtype=torch.float64, device=like.device)
+        d_used = torch.zeros(n_total, dtype=torch.uint8, device=like.device)
+        out.feat, out.used, out.cap_rows = d_feat.data_ptr() or None, d_used.data_ptr() or None, n_total
+    elif features:
+        out.feat, out.cap_rows = like.data_ptr(), 0    # the library refuses the size before it looks at the pointer
+    check(call(C.byref(opt), C.byref(out)))
+    return SnippetFeatures(d_feat, d_used, arr["n"], arr["nused"], arr.get("b1"), arr.get("b2"), arr.get("g1"),
+                           arr.get("g2"))
+
+
+def snippet_features(d_block, d_times, offs, pre=20, W=60, channels=None, basis=None, centre=None, moments=0,
+                     features=True, stream=None):
+    """api.snippet_features for a block and spike lists that are already resident (hmmsort_snippet_features_device;
+    arguments as device.footprints, `channels` one list for all units).  The rows and the used bytes stay on the
+    device (torch tensors of the result); the counts and moments come to the host.  Synchronises `stream`."""
+    nC, T = _fp_block(d_block)
+    if stream is None:
+        import torch
+        stream = torch.cuda.current_stream().cuda_stream
+    offs = np.ascontiguousarray(offs, dtype=np.int64).ravel()
+    U = len(offs) - 1
+    if d_times.element_size() != 8 or d_times.is_floating_point() or not d_times.is_contiguous():
+        raise TypeError("snippet_features: d_times must be a contiguous int64 device tensor")
+    if U >= 1 and int(offs[-1]) > int(d_times.numel()):
+        raise ValueError("snippet_features: offs ends at %d, d_times has %d entries" % (offs[-1], d_times.numel()))
+    n_total = max(0, int(offs[-1] - offs[0])) if U >= 1 else 0
+    return _feat_device_run(lambda opt, out: lib().hmmsort_snippet_features_device(
+        _dptr(d_block), nC, T, U, _dptr(d_times), ptr(offs), opt, out, C.c_void_p(stream)),
+        U, nC, n_total, pre, W, channels, basis, centre, moments, features, d_block)
+
+
+def isolation_scores(d_feat, offs, mu, Vinv, d_used=None, stream=None):
+    """api.isolation_scores on resident rows (hmmsort_cluster_isolation_device): d_feat [n][F] float64 and d_used [n]
+    uint8 device tensors (d_used None: every row used).  Returns (iso_d2, closer, lpair) on the host."""
+    from .api import _iso_run
+    if stream is None:
+        import torch
+        stream = torch.cuda.current_stream().cuda_stream
+    if not (d_feat.dim() == 2 and d_feat.is_contiguous() and d_feat.is_floating_point() and d_feat.element_size() == 8):
+        raise TypeError("isolation_scores: d_feat must be a contiguous float64 device tensor [n][F]")
+    n, F = (int(v) for v in d_feat.shape)
+    offs = np.ascontiguousarray(offs, dtype=np.int64).ravel()
+    U = len(offs) - 1
+    mu, Vinv = np.ascontiguousarray(mu, dtype=np.float64), np.ascontiguousarray(Vinv, dtype=np.float64)
+    if mu.shape != (U, F) or Vinv.shape != (U, F, F):
+        raise ValueError("isolation_scores: mu must be [%d][%d] and Vinv [%d][%d][%d]" % (U, F, U, F, F))
+    if d_used is not None and (d_used.element_size() != 1 or not d_used.is_contiguous() or d_used.numel() != n):
+        raise TypeError("isolation_scores: d_used must be a contiguous uint8 device tensor of %d entries" % n)
+    return _iso_run(lambda out: lib().hmmsort_cluster_isolation_device(
+        _dptr(d_feat), n, F, U, ptr(offs), None if d_used is None else _dptr(d_used), ptr(mu), ptr(Vinv), out,
+        C.c_void_p(stream)), U)
+
+
+def _isolation_from(run, P, keep_features):
+    """the two passes of api.cluster_isolation over run(basis, centre, moments, features) -> SnippetFeatures with
+    device rows"""
+    from . import api
+    p1 = run(None, None, 1, False)
+    basis, centre = api.pca_basis(p1.b1, p1.b2, p1.n_used, P)
+    p2 = run(basis, centre, 2, True)
+    mu, vinv = api.unit_gaussians(p2.g1, p2.g2, p2.n_used)
+    d2, closer, lpair = isolation_scores(p2.features, p2.offs, mu, vinv, p2.used)
+    return api._isolation_result(d2, closer, lpair, p2.n_used, basis, centre, p2.features if keep_features else None)
+
+
+def cluster_isolation(d_block, d_times, offs, pre=20, W=60, channels=None, P=3, keep_features=False, stream=None):
+    """api.cluster_isolation for a resident block and resident lists: both feature passes, the distances, the order
+    statistic and the sums on the device, the rows never leave it (keep_features=True returns them as a device
+    tensor); the PCA and the F x F inverses on the host."""
+    return _isolation_from(lambda basis, centre, moments, features: snippet_features(
+        d_block, d_times, offs, pre, W, channels, basis, centre, moments, features, stream), P, keep_features)
 
 
 class Plan:
@@ -421,6 +507,25 @@ class Plan:
         return _fp_run(lambda opt, out: lib().hmmsort_plan_footprints(self._h, _dptr(d_x), _dptr(d_block), nC, opt, out,
                                                                       C.c_void_p(stream)),
                        U, nC, pre, W, channels)
+
+    def snippet_features(self, d_x, d_block, pre=20, W=60, channels=None, basis=None, centre=None, moments=0,
+                         features=True, stream=0):
+        """api.SnippetFeatures of the events extract_spiketimes reports on the resident path(s) d_x under the plan's
+        current model, on the resident float64 block d_block [Cb][T] (hmmsort_plan_snippet_features): units are
+        u = channel * N + template, rows in that order.  With features=True a first call learns the counts, then the
+        rows are written to device tensors of exactly that size; the events themselves never come to the host."""
+        nC, T = _fp_block(d_block)
+        if T != self.T:
+            raise ValueError("snippet_features: the block has %d samples per channel, the plan %d" % (T, self.T))
+        U = getattr(self, "C", 1) * self.N
+        return _feat_device_run(lambda opt, out: lib().hmmsort_plan_snippet_features(
+            self._h, _dptr(d_x), _dptr(d_block), nC, opt, out, C.c_void_p(stream)),
+            U, nC, None, pre, W, channels, basis, centre, moments, features, d_block)
+
+    def cluster_isolation(self, d_x, d_block, pre=20, W=60, channels=None, P=3, keep_features=False, stream=0):
+        """api.Isolation of the plan's units on the resident block: device.cluster_isolation on the plan form."""
+        return _isolation_from(lambda basis, centre, moments, features: self.snippet_features(
+            d_x, d_block, pre, W, channels, basis, centre, moments, features, stream), P, keep_features)
 
     def expected_counts(self, stream=0):
         """expected number of spikes per template, sum_t onset[a, t] ([C][N]; [N] for a single-channel plan)"""

@@ -152,7 +152,7 @@ def front_end_block(data, preprocess, info=None):
 
 def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_templates=4,
               chunksize=100_000, confidence=False, jitter=2, refine_steps=0, adapt_halflife=None, quality=False,
-              correlograms=None, preprocess=None, channel=0, footprints=None):
+              correlograms=None, preprocess=None, channel=0, footprints=None, isolation=None):
     """sort_data(inputfile, datafile, outputfile; dosave, max_templates)   hmmsort.jl:36-104.
 
     Returns the reference's output dictionary; {} when there are more templates than
@@ -200,8 +200,14 @@ def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_temp
     `footprints=True` or dict(pre=, W=) (an extension; default None, output unchanged; needs `preprocess`) keeps the
     whole preprocessed block on the device instead of one channel of it and adds "footprint" (templates x channels x
     W: the mean waveform of every template on every channel of the block, api.footprints on the stitched path),
-    "footprint_n" (spikes used per template) and "peak_channel" (the channel where each template is largest)."""
+    "footprint_n" (spikes used per template) and "peak_channel" (the channel where each template is largest).
+
+    `isolation=True` or dict(pre=, W=, P=, channels=) (an extension; default None, output unchanged) adds
+    "unit_isolation": per-template "distance" (isolation distance), "l_ratio", "n_used" and the templates x templates
+    "lpair" and "closer" of api.cluster_isolation on the stitched path -- measured on every channel (or `channels`) of
+    the preprocessed block, kept on the device, when `preprocess` is given, else on the sorted channel alone."""
     want_fp = footprints is not None and footprints is not False
+    want_iso = isolation is not None and isolation is not False
     if want_fp and preprocess is None:
         raise ValueError("sort_data: footprints needs preprocess (an empty dict takes the block as it is): the "
                          "footprint is measured on every channel of the preprocessed block")
@@ -217,7 +223,7 @@ def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_temp
     lp, _ii = get_lp(sm)                                                       # :61
     data = np.asarray(data)
     d_block, info = None, {}
-    if want_fp:
+    if want_fp or (want_iso and preprocess is not None):
         d_block = front_end_block(data, preprocess, info)
         if not 0 <= int(channel) < d_block.shape[0]:
             raise ValueError("sort_data: channel = %r of a block of %d channels" % (channel, d_block.shape[0]))
@@ -281,6 +287,17 @@ def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_temp
         d_times = torch.from_numpy(np.concatenate(lists + [np.zeros(0, dtype=np.int64)]).astype(np.int64)).cuda()
         fp = device.footprints(d_block, d_times, offs, **({} if footprints is True else dict(footprints)))
         out["footprint"], out["footprint_n"], out["peak_channel"] = fp.mean, fp.n_used, fp.peak_channel
+    if want_iso:
+        import torch
+        from . import device
+        lists = api.extract_spiketimes(modelf)
+        offs = np.concatenate([[0], np.cumsum([len(t) for t in lists])]).astype(np.int64)
+        d_times = torch.from_numpy(np.concatenate(lists + [np.zeros(0, dtype=np.int64)]).astype(np.int64)).cuda()
+        d_iso = d_block if d_block is not None else \
+            torch.from_numpy(np.ascontiguousarray(dataf, dtype=np.float64)[None, :]).cuda()
+        iso = device.cluster_isolation(d_iso, d_times, offs, **({} if isolation is True else dict(isolation)))
+        out["unit_isolation"] = {"distance": iso.distance, "l_ratio": iso.l_ratio, "lpair": iso.lpair,
+                                 "closer": iso.closer, "n_used": iso.n_used}
     if dosave and outputfile is not None:
         from scipy.io import savemat
         savemat(outputfile, out)                                              # MAT.matwrite :100
@@ -368,6 +385,8 @@ def main(argv=None):
     ap.add_argument("--whiten-guard", type=int, default=30, metavar="N", help="nor are the N samples either side of it")
     ap.add_argument("--whiten-neighbors", type=int, metavar="M",
                     help="local whitening: each channel against its M nearest by channel index (default: all)")
+    ap.add_argument("--isolation", action="store_true",
+                    help="add unit_isolation (isolation distance, L-ratio) of the sorted templates to the output")
     a = ap.parse_args(argv)
     pre = None
     if a.highpass is not None or a.lowpass is not None or a.reference is not None or a.channel != 0 or a.whiten:
@@ -391,7 +410,8 @@ def main(argv=None):
         return 0
     if data is None:
         data = load_data(a.datafile, a.dataname)
-    out = sort_data(*t, data, a.outfile, max_templates=a.max_templates, preprocess=pre, channel=a.channel)
+    out = sort_data(*t, data, a.outfile, max_templates=a.max_templates, preprocess=pre, channel=a.channel,
+                    isolation=True if a.isolation else None)
     print("Done! Results saved to %s" % a.outfile if out else "Too many templates. Bailing out...")
     return 0
 

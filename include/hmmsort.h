@@ -841,6 +841,107 @@ int hmmsort_footprints_device(const double *d_y, int64_t C, int64_t T, int64_t U
 int hmmsort_plan_footprints(hmmsort_plan *plan, const int16_t *d_x, const double *d_block, int64_t Cb,
                             const hmmsort_fp_opt *opt, hmmsort_fp_out *out, void *stream);
 
+/* Waveform features and cluster isolation (an extension): one feature row per spike, the moments of the
+ * rows per unit, and from rows, unit means and inverse covariances the figures that say whether a unit is separated
+ * from the other units and the noise in waveform space (isolation distance and L-ratio, Schmitzer-Torbert et al.
+ * 2005).  The small linear algebra between the calls (PCA, the covariance inverse) is the host's: api.pca_basis,
+ * api.cluster_isolation.  No floating-point atomics, no fused multiply-add, no matrix-core instructions: every result
+ * but lpair is a fixed function of the input that tests/feature_model.py reproduces bit for bit.  All indices 0-based
+ * unless stated.
+ *
+ * 1. hmmsort_snippet_features.  Block, units, pre, W, the snippet s_m[k] = y[chan[m]][t - 1 - pre + k] and the rule
+ *    "used iff the window lies inside the block" are those of hmmsort_footprints.
+ *   options   chan: ONE int32 row [M] for all units (entries in 0..C-1, repeats allowed; NULL: M = C, all channels in
+ *             order, the M given is ignored).  basis [M][P][W] and centre [M][W], host doubles; centre NULL means
+ *             zeros; basis NULL: P := W (the P given is only checked to be >= 1).  moments: 0, 1 or 2.
+ *   rows      entry e of unit u is row r = offs[u] - offs[0] + e (host form: offs from the counts); n_total rows of
+ *             F features.  Without a basis F = M W and f[r][m W + k] = s_m[k] - centre[m][k]; with centre NULL that
+ *             is the snippet itself, bit for bit.  With a basis F = M P and f[r][m P + p] = acc, where acc = +0.0 and,
+ *             for k ascending, acc = acc + basis[m][p][k] * (s_m[k] - centre[m][k]): the subtraction, the product
+ *             and the sum each rounded on their own.  An unused entry's row is +0.0 and its used byte 0.
+ *   outputs   feat[n_total][F] and used[n_total] (bytes), each may be NULL: host arrays in the host form, device
+ *             memory in the device and plan forms.  Host arrays n[U] (required), nused[U] (may be NULL), and the
+ *             moments the mode asks for (required then).
+ *   moments   1: per unit and slot b1[U][M][P], b2[U][M][P][P]; 2: per unit g1[U][F], g2[U][F][F].  A unit's list is
+ *             cut into tiles of 256 consecutive list entries, used or not.  Within a tile a serial fold from +0.0
+ *             over the used entries in ascending order: p1_a = p1_a + f_a; p2_ab = p2_ab + f_a * f_b, the product
+ *             rounded on its own.  The tile partials are folded serially from +0.0 in tile order.  b >= a is computed
+ *             and mirrored.
+ *   refused   before any GPU work, every output untouched, the message names the argument.  HMMSORT_EINVAL: what
+ *             hmmsort_footprints refuses (a chan entry must be in 0..C-1 here), moments outside 0..2 or without its
+ *             output arrays, P < 1, P > W with a basis, a basis or centre entry that is not finite.  HMMSORT_EUNSUP,
+ *             naming the numbers: moments = 1 with P > HMMSORT_FEAT_MAX_P1, moments = 2 with F > HMMSORT_FEAT_MAX_F2,
+ *             n_total F > 2^31, U M P P or U F F above 2^26.  (The plan form learns n_total from the compaction, so
+ *             it refuses n_total F after that.)  W > T is legal: every row is unused and nothing is read.
+ *   forms     hmmsort_snippet_features: host buffers; uploads the block once (2-byte samples stay 2 bytes on the way).
+ *             _device: d_y, d_times and host offs as hmmsort_footprints_device; synchronises the stream.
+ *             hmmsort_plan_snippet_features: units u = ch N + a of the plan's resident path(s) as
+ *             hmmsort_plan_footprints finds them, d_block [Cb][T]; cap_rows is what d_feat and d_used can hold in
+ *             rows: cap_rows < n_total writes no row and no byte and is no error (n[U] says how many are needed; a
+ *             first call with feat == NULL is the usual moments pass).  Synchronises the stream.
+ *
+ * 2. hmmsort_cluster_isolation.  feat[n][F] rows in unit order behind host offs[U + 1] (n = offs[U] - offs[0]), used[n]
+ *    bytes or NULL for all used, host mu[U][F] and Vinv[U][F][F] (need not be symmetric); F in
+ *    1..HMMSORT_FEAT_MAX_F2, U in 1..HMMSORT_FP_MAX_UNITS.  A unit whose Vinv[u][0][0] is NaN is not scored: its
+ *    outputs are NaN / -1 (the rest of its mu and Vinv is not read), and its spikes still count as non-members of
+ *    the other units.
+ *   distance  for a scored unit u and a used row r: d_b = f[r][b] - mu[u][b]; q = +0.0; for a ascending: rr = +0.0; for
+ *             b ascending rr = rr + Vinv[u][a][b] * d_b; then q = q + d_a * rr; every product and sum rounded on its
+ *             own.  d2[u][r] = q if q > 0, else +0.0.
+ *   outputs   host arrays, each may be NULL.  iso_d2[U]: with n_u the used members and n_o the used non-members, if
+ *             n_u >= 1 and n_o >= n_u the exact order statistic of rank n_u - 1 (0-based) of d2[u][.] over the used
+ *             non-member rows, else NaN.  closer[U][U] int64: the count of {r in v, used: d2[u][r] < d2[v][r]},
+ *             strict; 0 on the diagonal, -1 when either unit is not scored.  lpair[U][U]: the sum over the used r in
+ *             v of Q_F(d2[u][r]), folded by tiles of 256 list entries of v, serially within a tile and across tiles;
+ *             0 on the diagonal, NaN for a u that is not scored.  Q_F is the chi-square survival function: with
+ *             h = x / 2, e = exp(-h); e == 0 gives 0; even F: e * sum_{j < F/2} t_j, t_0 = 1, t_j = t_{j-1} * h / j;
+ *             odd F: erfc(sqrt(h)) + e * sqrt(h) * (2 / sqrt(pi)) * sum_{j <= (F-3)/2} t_j, t_0 = 1,
+ *             t_j = t_{j-1} * h / (j + 0.5), no second term for F = 1.  lpair follows the device's exp, erfc and sqrt
+ *             and is therefore not bit-exact against another library (DESIGN 3.17 has the measured difference).
+ *   refused   before any GPU work: HMMSORT_EINVAL for a null required argument, F or U outside their ranges,
+ *             descending offs, n != offs[U] - offs[0], any other non-finite mu / Vinv entry of a scored unit;
+ *             HMMSORT_EUNSUP for U n > 2^30.
+ *   forms     hmmsort_cluster_isolation: host feat / used.  _device: device feat / used; synchronises the stream. */
+#define HMMSORT_FEAT_MAX_P1 128
+#define HMMSORT_FEAT_MAX_F2 64
+typedef struct hmmsort_feat_opt {
+    int64_t pre;           /* samples of the window before the spike time */
+    int64_t W;             /* window length */
+    int64_t M;             /* slots (chan != NULL) */
+    const int32_t *chan;   /* [M] host row or NULL: all C channels in order */
+    int64_t P;             /* components per slot (basis != NULL) */
+    const double *basis;   /* [M][P][W] host or NULL */
+    const double *centre;  /* [M][W] host or NULL: zeros */
+    int64_t moments;       /* 0: none, 1: per unit and slot, 2: per unit */
+} hmmsort_feat_opt;
+typedef struct hmmsort_feat_out {
+    double *feat;          /* [n_total][F], may be NULL; device memory in the device and plan forms */
+    unsigned char *used;   /* [n_total], may be NULL; likewise */
+    int64_t cap_rows;      /* plan form: rows feat and used can hold */
+    int64_t *n;            /* [U], required */
+    int64_t *nused;        /* [U], may be NULL */
+    double *b1, *b2;       /* moments = 1: [U][M][P], [U][M][P][P] */
+    double *g1, *g2;       /* moments = 2: [U][F], [U][F][F] */
+} hmmsort_feat_out;
+int hmmsort_snippet_features(const void *y, int sample_type, int64_t C, int64_t T, int64_t U,
+                             const int64_t *const *times, const int64_t *counts, const hmmsort_feat_opt *opt,
+                             hmmsort_feat_out *out);
+int hmmsort_snippet_features_device(const double *d_y, int64_t C, int64_t T, int64_t U, const int64_t *d_times,
+                                    const int64_t *offs, const hmmsort_feat_opt *opt, hmmsort_feat_out *out,
+                                    void *stream);
+int hmmsort_plan_snippet_features(hmmsort_plan *plan, const int16_t *d_x, const double *d_block, int64_t Cb,
+                                  const hmmsort_feat_opt *opt, hmmsort_feat_out *out, void *stream);
+typedef struct hmmsort_iso_out {
+    double *iso_d2;    /* [U], may be NULL */
+    int64_t *closer;   /* [U][U], may be NULL */
+    double *lpair;     /* [U][U], may be NULL */
+} hmmsort_iso_out;
+int hmmsort_cluster_isolation(const double *feat, int64_t n, int64_t F, int64_t U, const int64_t *offs,
+                              const unsigned char *used, const double *mu, const double *Vinv, hmmsort_iso_out *out);
+int hmmsort_cluster_isolation_device(const double *d_feat, int64_t n, int64_t F, int64_t U, const int64_t *offs,
+                                     const unsigned char *d_used, const double *mu, const double *Vinv,
+                                     hmmsort_iso_out *out, void *stream);
+
 /* Spatial whitening (an extension): the noise covariance of the quiet samples of a block, and a mix of
  * its channels, on the fp64 channel-major block [C][T] that hmmsort_preprocess_device writes.  The C x C matrix itself
  * (ZCA, global or local) is the host's work: api.whitening_matrix.  All indices 0-based.  No floating-point atomics,

@@ -579,6 +579,134 @@ function footprints_plan(plan::Ptr{Cvoid}, d_x::Ptr{Int16}, d_block::Ptr{Float64
     end
 end
 
+# struct hmmsort_feat_opt / hmmsort_feat_out / hmmsort_iso_out (include/hmmsort.h)
+struct CFeatOpt
+    pre::Int64; W::Int64; M::Int64; chan::Ptr{Int32}; P::Int64; basis::Ptr{Float64}; centre::Ptr{Float64}; moments::Int64
+end
+struct CFeatOut
+    feat::Ptr{Float64}; used::Ptr{UInt8}; cap_rows::Int64; n::Ptr{Int64}; nused::Ptr{Int64}
+    b1::Ptr{Float64}; b2::Ptr{Float64}; g1::Ptr{Float64}; g2::Ptr{Float64}
+end
+struct CIsoOut
+    iso_d2::Ptr{Float64}; closer::Ptr{Int64}; lpair::Ptr{Float64}
+end
+
+# call(opt::Ref{CFeatOpt}, out::Ref{CFeatOut}) -> code.  `channels`: empty (all C channels in order) or the 0-based block
+# channels of the M slots, one row for all units; `basis` W × P × M (empty: none, P := W), `centre` W × M (empty: zeros);
+# feat / used: where the rows go (host arrays in the host form, device memory otherwise; C_NULL: no rows), cap_rows what
+# they hold.  Moments come back column-major: b1 P × M × U, b2 P × P × M × U, g1 F × U, g2 F × F × U.
+function _feat_run(call, U, C, pre, W, channels::Vector{Int32}, basis::Array{Float64,3}, centre::Matrix{Float64},
+                   moments, feat, used, cap_rows)
+    M = isempty(channels) ? C : length(channels)
+    P = isempty(basis) ? W : size(basis, 2)
+    F = M * P
+    n = zeros(Int64, U); nused = zeros(Int64, U)
+    b1 = moments == 1 ? zeros(Float64, P, M, U) : zeros(Float64, 0, 0, 0)
+    b2 = moments == 1 ? zeros(Float64, P, P, M, U) : zeros(Float64, 0, 0, 0, 0)
+    g1 = moments == 2 ? zeros(Float64, F, U) : zeros(Float64, 0, 0)
+    g2 = moments == 2 ? zeros(Float64, F, F, U) : zeros(Float64, 0, 0, 0)
+    nul(a) = isempty(a) ? Ptr{eltype(a)}(C_NULL) : pointer(a)
+    GC.@preserve channels basis centre n nused b1 b2 g1 g2 begin
+        check(call(Ref(CFeatOpt(pre, W, M, nul(channels), isempty(basis) ? 1 : P, nul(basis), nul(centre), moments)),
+                   Ref(CFeatOut(feat, used, cap_rows, pointer(n), pointer(nused), nul(b1), nul(b2), nul(g1), nul(g2)))))
+    end
+    (n=n, nused=nused, b1=b1, b2=b2, g1=g1, g2=g2, F=F)
+end
+
+"""
+    snippet_features(block, times; pre=20, W=60, channels=Int32[], basis, centre, moments=0, rows=true)
+        -> (features, used, n, nused, b1, b2, g1, g2)
+
+One feature row per spike (`hmmsort_snippet_features`; an extension, INTEGRATION.md "Isolation"): `block` and `times` as
+`footprints` takes them; `features` is F × n_total (row `r` of the C layout is column `r`), rows in unit order.  Without
+a basis the row is the spike's snippets on the listed channels minus `centre`; with `basis` (W × P × M) the P
+projections per channel.  `moments`: 1 the per-channel sums for the PCA, 2 the per-unit sums over whole rows.
+"""
+function snippet_features(block::Matrix{T}, times::Vector{Vector{Int64}}; pre::Integer=20, W::Integer=60,
+                          channels::Vector{Int32}=Int32[], basis::Array{Float64,3}=zeros(Float64, 0, 0, 0),
+                          centre::Matrix{Float64}=zeros(Float64, 0, 0), moments::Integer=0,
+                          rows::Bool=true) where T <: Union{Float64,Int16}
+    n, C = size(block); U = length(times)
+    ptrs = [isempty(t) ? Ptr{Int64}(C_NULL) : pointer(t) for t in times]; counts = Int64.(length.(times))
+    M = isempty(channels) ? C : length(channels)
+    F = M * (isempty(basis) ? W : size(basis, 2)); total = sum(counts)
+    feat = rows ? zeros(Float64, F, total) : zeros(Float64, 0, 0); used = rows ? zeros(UInt8, total) : UInt8[]
+    GC.@preserve block times ptrs counts feat used begin
+        r = _feat_run(U, C, pre, W, channels, basis, centre, moments,
+                      rows ? pointer(feat) : Ptr{Float64}(C_NULL), rows ? pointer(used) : Ptr{UInt8}(C_NULL), total) do opt, out
+            ccall((:hmmsort_snippet_features, lib), Cint,
+                (Ptr{Cvoid}, Cint, Int64, Int64, Int64, Ptr{Ptr{Int64}}, Ptr{Int64}, Ref{CFeatOpt}, Ref{CFeatOut}),
+                block, T === Int16 ? HMMSORT_SAMPLES_I16 : HMMSORT_SAMPLES_F64, C, n, U, ptrs, counts, opt, out)
+        end
+    end
+    (features=feat, used=used, n=r.n, nused=r.nused, b1=r.b1, b2=r.b2, g1=r.g1, g2=r.g2)
+end
+
+"`snippet_features` of a resident `[C][n]` Float64 block and resident lists (`hmmsort_snippet_features_device`); `d_feat` / `d_used`: device memory for `offs[end] - offs[1]` rows, or `C_NULL`; synchronises `stream`"
+function snippet_features_device(d_y::Ptr{Float64}, C::Integer, n::Integer, d_times::Ptr{Int64}, offs::Vector{Int64};
+                                 pre::Integer=20, W::Integer=60, channels::Vector{Int32}=Int32[],
+                                 basis::Array{Float64,3}=zeros(Float64, 0, 0, 0),
+                                 centre::Matrix{Float64}=zeros(Float64, 0, 0), moments::Integer=0,
+                                 d_feat::Ptr{Float64}=Ptr{Float64}(C_NULL), d_used::Ptr{UInt8}=Ptr{UInt8}(C_NULL),
+                                 stream::Ptr{Cvoid}=C_NULL)
+    U = length(offs) - 1
+    GC.@preserve offs begin
+        _feat_run(U, C, pre, W, channels, basis, centre, moments, d_feat, d_used, offs[end] - offs[1]) do opt, out
+            ccall((:hmmsort_snippet_features_device, lib), Cint,
+                (Ptr{Float64}, Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ref{CFeatOpt}, Ref{CFeatOut}, Ptr{Cvoid}),
+                d_y, C, n, U, d_times, offs, opt, out, stream)
+        end
+    end
+end
+
+"`snippet_features` of the units `u = ch N + a` a plan finds on its resident path(s) `d_x` (`hmmsort_plan_snippet_features`); a first call without rows returns `n`; `cap_rows` is what `d_feat` / `d_used` hold (fewer than `sum(n)`: no row is written); synchronises `stream`"
+function snippet_features_plan(plan::Ptr{Cvoid}, d_x::Ptr{Int16}, d_block::Ptr{Float64}, Cb::Integer, U::Integer;
+                               pre::Integer=20, W::Integer=60, channels::Vector{Int32}=Int32[],
+                               basis::Array{Float64,3}=zeros(Float64, 0, 0, 0),
+                               centre::Matrix{Float64}=zeros(Float64, 0, 0), moments::Integer=0,
+                               d_feat::Ptr{Float64}=Ptr{Float64}(C_NULL), d_used::Ptr{UInt8}=Ptr{UInt8}(C_NULL),
+                               cap_rows::Integer=0, stream::Ptr{Cvoid}=C_NULL)
+    _feat_run(U, Cb, pre, W, channels, basis, centre, moments, d_feat, d_used, cap_rows) do opt, out
+        ccall((:hmmsort_plan_snippet_features, lib), Cint,
+            (Ptr{Cvoid}, Ptr{Int16}, Ptr{Float64}, Int64, Ref{CFeatOpt}, Ref{CFeatOut}, Ptr{Cvoid}),
+            plan, d_x, d_block, Cb, opt, out, stream)
+    end
+end
+
+"""
+    cluster_isolation(features, offs, mu, Vinv; used=UInt8[]) -> (iso_d2, closer, lpair)
+
+`hmmsort_cluster_isolation`: `features` F × n (column `r` is row `r`), `offs` the U + 1 0-based row offsets, `mu` F × U,
+`Vinv` F × F × U with `Vinv[b, a, u]` the C entry `[u][a][b]` (a unit whose `Vinv[1, 1, u]` is NaN is not scored).
+`closer[v, u]` and `lpair[v, u]` are the C entries `[u][v]`.
+"""
+function cluster_isolation(features::Matrix{Float64}, offs::Vector{Int64}, mu::Matrix{Float64}, Vinv::Array{Float64,3};
+                           used::Vector{UInt8}=UInt8[])
+    F, n = size(features); U = length(offs) - 1
+    d2 = zeros(Float64, U); closer = zeros(Int64, U, U); lpair = zeros(Float64, U, U)
+    GC.@preserve features offs mu Vinv used d2 closer lpair begin
+        check(ccall((:hmmsort_cluster_isolation, lib), Cint,
+            (Ptr{Float64}, Int64, Int64, Int64, Ptr{Int64}, Ptr{UInt8}, Ptr{Float64}, Ptr{Float64}, Ref{CIsoOut}),
+            features, n, F, U, offs, isempty(used) ? Ptr{UInt8}(C_NULL) : pointer(used), mu, Vinv,
+            Ref(CIsoOut(pointer(d2), pointer(closer), pointer(lpair)))))
+    end
+    (iso_d2=d2, closer=closer, lpair=lpair)
+end
+
+"`cluster_isolation` on resident rows `d_feat` (`[n][F]`) and used bytes `d_used` (or `C_NULL`) (`hmmsort_cluster_isolation_device`); synchronises `stream`"
+function cluster_isolation_device(d_feat::Ptr{Float64}, n::Integer, F::Integer, offs::Vector{Int64}, mu::Matrix{Float64},
+                                  Vinv::Array{Float64,3}; d_used::Ptr{UInt8}=Ptr{UInt8}(C_NULL),
+                                  stream::Ptr{Cvoid}=C_NULL)
+    U = length(offs) - 1
+    d2 = zeros(Float64, U); closer = zeros(Int64, U, U); lpair = zeros(Float64, U, U)
+    GC.@preserve offs mu Vinv d2 closer lpair begin
+        check(ccall((:hmmsort_cluster_isolation_device, lib), Cint,
+            (Ptr{Float64}, Int64, Int64, Int64, Ptr{Int64}, Ptr{UInt8}, Ptr{Float64}, Ptr{Float64}, Ref{CIsoOut}, Ptr{Cvoid}),
+            d_feat, n, F, U, offs, d_used, mu, Vinv, Ref(CIsoOut(pointer(d2), pointer(closer), pointer(lpair))), stream))
+    end
+    (iso_d2=d2, closer=closer, lpair=lpair)
+end
+
 function reconstruct_signal(x::Array{T,1}, lA::StateMatrix, μ::Array{Float64,2}, σ::Float64) where T <: Integer
     xs = T === Int16 ? x : Int16.(x)
     Y2 = zeros(Float64, length(xs))
