@@ -12,7 +12,7 @@ from .api import (Correlograms, Footprints, HMMSpikeTemplateModel, HMMSpikingMod
                   quality_from_summary, spike_fit, unit_quality, correlograms, duplicate_units, footprints, unit_locations,
                   footprint_similarity, resolve_duplicates,
                   Isolation, SnippetFeatures, cluster_isolation, isolation_scores, pca_basis, snippet_features,
-                  unassigned_events, unit_gaussians,
+                  unassigned_events, unit_gaussians, UnitStability, quantile_fractions, unit_stability,
                   Whitening, channel_mix, noise_covariance, noise_sums, whiten, whitening_matrix,
                   posterior_decode, posteriors, predict, design_fir, preprocess, reconstruct_signal, reconstruct_tracked, seed_templates, spike_confidence, train_model, train_step, unroll_mlseq, update,
                   viterbi, viterbi_step)
@@ -35,4 +35,4 @@ __all__ = ["StateMatrix", "HMMSpikeTemplateModel", "HMMSpikingModel", "forward",
            "footprints", "unit_locations", "footprint_similarity", "resolve_duplicates", "Whitening", "channel_mix",
            "noise_covariance", "noise_sums", "whiten", "whitening_matrix", "Isolation", "SnippetFeatures",
            "cluster_isolation", "isolation_scores", "pca_basis", "snippet_features", "unassigned_events",
-           "unit_gaussians"]
+           "unit_gaussians", "UnitStability", "quantile_fractions", "unit_stability"]

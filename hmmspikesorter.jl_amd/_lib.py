@@ -121,6 +121,19 @@ class IsoOut(C.Structure):
     _fields_ = [("iso_d2", _vp), ("closer", _vp), ("lpair", _vp)]
 
 
+class StabOpt(C.Structure):
+    """struct hmmsort_stab_opt: recording length, samples per time bin, the quantiles q_num[k] / q_den, and the
+    histogram (bins, left edge, 1 / bin width)"""
+    _fields_ = [("T", _i64), ("bin", _i64), ("nq", _i64), ("q_num", _i64 * 8), ("q_den", _i64), ("HB", _i64),
+                ("hist_lo", _f64), ("hist_scale", _f64)]
+
+
+class StabOut(C.Structure):
+    """struct hmmsort_stab_out: host arrays hmmsort_unit_stability fills (n is required, the others may be NULL)"""
+    _fields_ = [(k, _vp) for k in ("n", "count", "valid", "quant", "sum", "sumsq", "uvalid", "uquant", "umin", "umax",
+                                   "usum", "usumsq", "hist", "under", "over")]
+
+
 class PreOpt(C.Structure):
     """struct hmmsort_pre_opt: half filter (taps NULL: none), reference mode, group id per channel (NULL: one group)
     and, in the host form, the rows to return (NULL: all)"""
@@ -146,6 +159,7 @@ CCG_MAX_UNITS, CCG_MAX_HALF_BINS = 4096, 2048
 FP_MAX_UNITS, FP_MAX_W, FP_MAX_SLOTS = 4096, 1024, 1024
 WHITEN_MAX_CHANNELS, WHITEN_MAX_GUARD = 1024, 65536
 FEAT_MAX_P1, FEAT_MAX_F2 = 128, 64
+STAB_MAX_UNITS, STAB_MAX_Q, STAB_MAX_QDEN, STAB_MAX_HIST, STAB_MAX_BINS = 4096, 8, 1 << 20, 4096, 1 << 24
 
 # name -> (restype, argtypes); every symbol include/hmmsort.h declares
 SIGNATURES = {
@@ -243,6 +257,10 @@ SIGNATURES = {
     "hmmsort_plan_snippet_features": (_int, [_vp, _vp, _vp, _i64, C.POINTER(FeatOpt), C.POINTER(FeatOut), _vp]),
     "hmmsort_cluster_isolation": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, C.POINTER(IsoOut)]),
     "hmmsort_cluster_isolation_device": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, C.POINTER(IsoOut), _vp]),
+    "hmmsort_unit_stability": (_int, [_i64, C.POINTER(_vp), C.POINTER(_vp), _vp, C.POINTER(StabOpt),
+                                      C.POINTER(StabOut)]),
+    "hmmsort_unit_stability_device": (_int, [_i64, _vp, _vp, _vp, C.POINTER(StabOpt), C.POINTER(StabOut), _vp]),
+    "hmmsort_plan_unit_stability": (_int, [_vp, _vp, _vp, C.POINTER(StabOpt), C.POINTER(StabOut), _vp]),
     "hmmsort_plan_profile": (_int, [_vp, _int]),
     "hmmsort_plan_profile_read": (_int, [_vp, _vp, C.c_char_p, _i64, C.POINTER(_f64), _pi64, _i64,
                                          _pi64]),

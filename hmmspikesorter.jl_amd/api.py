@@ -1679,3 +1679,159 @@ def unassigned_events(events, units, tol=10):
     left = np.abs(ev - spikes[np.maximum(i - 1, 0)])
     right = np.abs(spikes[np.minimum(i, len(spikes) - 1)] - ev)
     return ev[np.minimum(left, right) > int(tol)]
+
+
+_STAB_SMOOTH = np.array([1.0, 4.0, 6.0, 4.0, 1.0]) / 16.0
+
+
+@dataclass
+class UnitStability:
+    """The tables of hmmsort_unit_stability for U units and B time bins (definitions in include/hmmsort.h) and the
+    figures that follow from them on the host.  Without values only n and count are filled, the rest is None."""
+    n: np.ndarray        # [U]: spikes per unit
+    count: np.ndarray    # [U, B]: spikes per unit and time bin
+    valid: np.ndarray    # [U, B]: of them with a value (not NaN)
+    quant: np.ndarray    # [U, B, nq]: exact order statistics of the values of a bin, NaN where valid == 0
+    sum: np.ndarray      # [U, B]: sum of the values
+    sumsq: np.ndarray    # [U, B]: sum of their squares
+    uvalid: np.ndarray   # [U]: values per unit over the whole recording
+    uquant: np.ndarray   # [U, nq]: their order statistics
+    umin: np.ndarray     # [U]
+    umax: np.ndarray     # [U]
+    usum: np.ndarray     # [U]: the bin sums folded in bin order
+    usumsq: np.ndarray   # [U]
+    hist: np.ndarray     # [U, HB]: values with floor((v - hist_lo) * hist_scale) == k
+    under: np.ndarray    # [U]: values below bin 0
+    over: np.ndarray     # [U]: values at or beyond bin HB
+    T: int               # recording length in samples
+    bin: int             # samples per time bin
+    q_num: tuple         # the quantiles are q_num[k] / q_den
+    q_den: int
+    hist_lo: float
+    hist_scale: float
+
+    @property
+    def bin_samples(self):
+        """[B]: samples per time bin; the last one may be short"""
+        B = self.count.shape[1]
+        return np.minimum(self.bin, self.T - np.arange(B, dtype=np.int64) * self.bin)
+
+    def firing_rate(self, fs):
+        """[U, B]: spikes per second in every time bin at the sampling rate fs"""
+        return self.count / (self.bin_samples / float(fs))
+
+    def presence_ratio(self, min_count=1):
+        """[U]: the share of full-length bins with at least min_count spikes; the short last bin is left out unless
+        it is the only bin"""
+        full = self.bin_samples == self.bin
+        if not full.any():
+            full[:] = True
+        return np.sum(self.count[:, full] >= int(min_count), axis=1) / float(np.sum(full))
+
+    def _median_index(self):
+        for k, q in enumerate(self.q_num):
+            if 2 * q == self.q_den:
+                return k
+        raise ValueError("amplitude_drift needs the quantile 1/2 among the quantiles")
+
+    def amplitude_drift(self, min_valid=20):
+        """[U]: (largest - smallest per-bin median) / overall median, over the bins with at least min_valid values;
+        NaN for a unit without such a bin"""
+        k = self._median_index()
+        out = np.full(len(self.n), np.nan)
+        for u in range(len(self.n)):
+            med = self.quant[u, self.valid[u] >= int(min_valid), k]
+            if len(med):
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    out[u] = (med.max() - med.min()) / self.uquant[u, k]
+        return out
+
+    def amplitude_cutoff(self):
+        """[U]: the estimated share of spikes lost below the detection floor (Hill et al. 2011), from the histogram:
+        the counts smoothed with the binomial kernel (1, 4, 6, 4, 1) / 16 (zero padded), the peak at the first largest
+        smoothed bin, the low edge at the first non-empty bin (bin 0 when `under` counts anything); the mass of the
+        smoothed bins at or above the mirror image of the low edge about the peak, plus `over`, over the total count,
+        capped at 0.5.  NaN for a unit without a value or without a histogram."""
+        HB = self.hist.shape[1]
+        out = np.full(len(self.n), np.nan)
+        for u in range(len(self.n)):
+            h = self.hist[u].astype(np.float64)
+            total = float(self.under[u] + self.hist[u].sum() + self.over[u])
+            if total == 0 or HB == 0:
+                continue
+            sm = np.convolve(h, _STAB_SMOOTH, mode="same") if HB >= len(_STAB_SMOOTH) else h
+            peak = int(np.argmax(sm))
+            nz = np.nonzero(self.hist[u])[0]
+            low = 0 if self.under[u] > 0 or len(nz) == 0 else int(nz[0])
+            mirror = 2 * peak - low
+            mass = float(sm[mirror:].sum()) if mirror < HB else 0.0
+            out[u] = min(0.5, (mass + float(self.over[u])) / total)
+        return out
+
+
+def quantile_fractions(quantiles):
+    """(q_num, q_den) of float quantiles, the integers hmmsort_unit_stability ranks with: every q becomes the closest
+    fraction with a denominator of at most 4096 (Fraction.limit_denominator, so 1/4, 1/3 or 0.9 are exact) and q_den
+    is the least common multiple of the denominators; should that exceed 2^20, q_den = 2^20 and
+    q_num = floor(q 2^20 + 1/2) instead."""
+    from fractions import Fraction
+    from math import lcm
+    fr = [Fraction(float(q)).limit_denominator(4096) for q in quantiles]
+    den = lcm(*[f.denominator for f in fr]) if fr else 1
+    if den <= _lib.STAB_MAX_QDEN:
+        return tuple(int(f.numerator * (den // f.denominator)) for f in fr), int(den)
+    den = _lib.STAB_MAX_QDEN
+    return tuple(int(np.floor(float(q) * den + 0.5)) for q in quantiles), den
+
+
+def _stab_run(call, U, T, bin, quantiles, hist, with_values):
+    """call(byref(hmmsort_stab_opt), byref(hmmsort_stab_out)) -> rc into the UnitStability of U units; hist: None or
+    (bins, lo, hi), the histogram's bin k being [lo + k w, lo + (k + 1) w) with 1 / w = bins / (hi - lo)"""
+    T, bin = int(T), int(bin)
+    q_num, q_den = quantile_fractions(quantiles)
+    nq = len(q_num)
+    HB, lo, scale = 0, 0.0, 1.0
+    if hist is not None:
+        HB, lo, hi = int(hist[0]), float(hist[1]), float(hist[2])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            scale = float(np.float64(HB) / (np.float64(hi) - np.float64(lo)))
+    # sizes the library refuses get token arrays: it checks before it writes, and its message says what is wrong
+    B = (T + bin - 1) // bin if bin >= 1 else 0
+    ok = (1 <= U <= _lib.STAB_MAX_UNITS and 1 <= B <= _lib.STAB_MAX_BINS and U * B <= _lib.STAB_MAX_BINS
+          and nq <= _lib.STAB_MAX_Q and 0 <= HB <= _lib.STAB_MAX_HIST)
+    Ua, Ba, qa, Ha = (U, B, nq, HB) if ok else (1, 1, min(nq, _lib.STAB_MAX_Q), 0)
+    i64 = dict(n=(Ua,), count=(Ua, Ba), valid=(Ua, Ba), uvalid=(Ua,), hist=(Ua, Ha), under=(Ua,), over=(Ua,))
+    f64 = dict(quant=(Ua, Ba, qa), sum=(Ua, Ba), sumsq=(Ua, Ba), uquant=(Ua, qa), umin=(Ua,), umax=(Ua,), usum=(Ua,),
+               usumsq=(Ua,))
+    a = {k: np.zeros(s, dtype=np.int64) for k, s in i64.items()}
+    a.update({k: np.zeros(s) for k, s in f64.items()})
+    opt = _lib.StabOpt(T, bin, nq, (C.c_int64 * 8)(*q_num[:8]), q_den, HB, lo, scale)
+    out = _lib.StabOut(*[a[k].ctypes.data for k, _ in _lib.StabOut._fields_])
+    check(call(C.byref(opt), C.byref(out)))
+    if not with_values:
+        a.update({k: None for k in a if k not in ("n", "count")})
+    return UnitStability(*[a[k] for k, _ in _lib.StabOut._fields_], T, bin, q_num, q_den, lo, scale)
+
+
+def unit_stability(times, values=None, T=None, bin=None, quantiles=(1 / 4, 1 / 2, 3 / 4), hist=None):
+    """unit_stability(units[, values]; T, bin, quantiles, hist) -> UnitStability (an extension, INTEGRATION.md
+    "Stability"): per unit and time bin of `bin` samples the spike count and, of one value per spike, exact order
+    statistics, sums and a histogram -- was the unit there the whole time, and did its amplitude sink?  `units` is a
+    list of spike-time arrays (1-based samples, strictly ascending, at most T) or HMMSpikingModels, as correlograms
+    takes them; `values` a list of float64 arrays of the same lengths (NaN: no value) or None for the counts alone.
+    `quantiles` are floats in 0..1 turned into integer fractions by quantile_fractions; a quantile is the value of
+    rank floor(q (m - 1)) among the m values of a bin, never interpolated.  `hist`: None or (bins, lo, hi)."""
+    lists = _time_lists(times)
+    U = len(lists)
+    if T is None or bin is None:
+        raise ValueError("unit_stability: T and bin are required")
+    ptrs = (C.c_void_p * max(U, 1))(*[t.ctypes.data if len(t) else None for t in lists])
+    cnt = np.array([len(t) for t in lists] + [0] * (U == 0), dtype=np.int64)
+    vptrs = None
+    if values is not None:
+        vals = [np.ascontiguousarray(v, dtype=np.float64).ravel() for v in values]
+        if [len(v) for v in vals] != [len(t) for t in lists]:
+            raise ValueError("unit_stability: values must hold one array per unit, as long as its times")
+        vptrs = (C.c_void_p * max(U, 1))(*[v.ctypes.data if len(v) else None for v in vals])
+    return _stab_run(lambda opt, out: lib().hmmsort_unit_stability(U, ptrs, vptrs, ptr(cnt), opt, out), U, T, bin,
+                     quantiles, hist, values is not None)

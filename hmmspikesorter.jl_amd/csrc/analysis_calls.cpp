@@ -1,8 +1,8 @@
 // Analysis entry points of libhmmsort_hip.so (include/hmmsort.h): what works on a recording, a decoded path or spike
 // lists without the escalation ladder -- sample widening, the front end, whitening, reconstruct / unroll / extract,
-// spike confidence, the per-spike fit, the template seed, correlograms, footprints, features and isolation, each in its host, device and
-// plan forms -- and the host staging they share.  Every call checks its arguments before it asks for a device, keeps
-// no plan and no cached slot, and has no CPU compute path.
+// spike confidence, the per-spike fit, the template seed, correlograms, footprints, features, isolation and unit
+// stability, each in its host, device and plan forms -- and the host staging they share.  Every call checks its
+// arguments before it asks for a device, keeps no plan and no cached slot, and has no CPU compute path.
 #include <algorithm>
 #include <vector>
 
@@ -195,6 +195,38 @@ int spike_fit_check(const char *who, int64_t N, int64_t S, const double *mu, int
     return HMMSORT_OK;
 }
 
+// the device side of one channel's fit: what dev_spike_fit reads and fills, rows of dcap entries per template
+struct FitDev {
+    DevBuf dst, dM, dfirst, damp, drss, den, dnu, dch, dpart, dsum;
+};
+
+// the fit of the compacted events d_t [N][dcap] (counts per template, at least one event in all), left in device memory
+int spike_fit_rows(const double *d_y, const int16_t *d_x, int64_t T, const int16_t *states, int64_t N, int64_t S,
+                   const double *mu, int64_t K, const int32_t *qv, int64_t nchunks, const int64_t *first,
+                   const double *mu_track, const int64_t *d_t, int64_t dcap, const int64_t *counts, FitDev &f,
+                   hipStream_t st)
+{
+    const int64_t L = spike_fit_len(K);
+    int64_t maxn = 0;
+    for (int64_t a = 0; a < N; a++) maxn = std::max(maxn, counts[a]);
+    const int64_t nblk = spike_fit_blocks(maxn), nM = (nchunks > 0 ? nchunks : 1) * K * N;
+    int rc;
+    if ((rc = f.dst.alloc(N * S * sizeof(int16_t))) || (rc = f.dM.alloc(nM * sizeof(double))) ||
+        (rc = f.dfirst.alloc(std::max<int64_t>(1, nchunks) * sizeof(int64_t))) ||
+        (rc = f.damp.alloc(N * dcap * sizeof(double))) || (rc = f.drss.alloc(N * dcap * sizeof(double))) ||
+        (rc = f.den.alloc(N * dcap * sizeof(double))) || (rc = f.dnu.alloc(N * dcap * sizeof(int32_t))) ||
+        (rc = f.dch.alloc(N * dcap * sizeof(int32_t))) || (rc = f.dpart.alloc(N * nblk * L * sizeof(double))) ||
+        (rc = f.dsum.alloc(N * L * sizeof(double))))
+        return rc;
+    HS_HIP(hipMemcpyAsync(f.dst.p, states, N * S * sizeof(int16_t), hipMemcpyHostToDevice, st));
+    HS_HIP(hipMemcpyAsync(f.dM.p, nchunks > 0 ? mu_track : mu, nM * sizeof(double), hipMemcpyHostToDevice, st));
+    if (nchunks > 0)
+        HS_HIP(hipMemcpyAsync(f.dfirst.p, first, nchunks * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    return dev_spike_fit(d_y, d_x, T, f.dst.as<int16_t>(), N, S, K, f.dM.as<double>(), nchunks, f.dfirst.as<int64_t>(),
+                         d_t, dcap, counts, qv, f.damp.as<double>(), f.drss.as<double>(), f.den.as<double>(),
+                         f.dnu.as<int32_t>(), f.dch.as<int32_t>(), f.dpart.as<double>(), f.dsum.as<double>(), st);
+}
+
 // one channel: resident signal and path in, host arrays out (rows of `cap` entries; any of them may be null)
 int spike_fit_channel(const double *d_y, const int16_t *d_x, int64_t T, const int16_t *states, int64_t N, int64_t S,
                       const double *mu, int64_t K, const int32_t *qv, int64_t nchunks, const int64_t *first,
@@ -223,36 +255,22 @@ int spike_fit_channel(const double *d_y, const int16_t *d_x, int64_t T, const in
     int64_t maxn = 0;
     for (int64_t a = 0; a < N; a++) maxn = std::max(maxn, counts[a]);
     if (maxn == 0) return HMMSORT_OK;
-    const int64_t nblk = spike_fit_blocks(maxn), nM = (nchunks > 0 ? nchunks : 1) * K * N;
-    DevBuf dst, dM, dfirst, damp, drss, den, dnu, dch, dpart, dsum;
-    if ((rc = dst.alloc(N * S * sizeof(int16_t))) || (rc = dM.alloc(nM * sizeof(double))) ||
-        (rc = dfirst.alloc(std::max<int64_t>(1, nchunks) * sizeof(int64_t))) ||
-        (rc = damp.alloc(N * dcap * sizeof(double))) || (rc = drss.alloc(N * dcap * sizeof(double))) ||
-        (rc = den.alloc(N * dcap * sizeof(double))) || (rc = dnu.alloc(N * dcap * sizeof(int32_t))) ||
-        (rc = dch.alloc(N * dcap * sizeof(int32_t))) || (rc = dpart.alloc(N * nblk * L * sizeof(double))) ||
-        (rc = dsum.alloc(N * L * sizeof(double))))
-        return rc;
-    HS_HIP(hipMemcpyAsync(dst.p, states, N * S * sizeof(int16_t), hipMemcpyHostToDevice, st));
-    HS_HIP(hipMemcpyAsync(dM.p, nchunks > 0 ? mu_track : mu, nM * sizeof(double), hipMemcpyHostToDevice, st));
-    if (nchunks > 0)
-        HS_HIP(hipMemcpyAsync(dfirst.p, first, nchunks * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    if ((rc = dev_spike_fit(d_y, d_x, T, dst.as<int16_t>(), N, S, K, dM.as<double>(), nchunks, dfirst.as<int64_t>(),
-                            dt.as<int64_t>(), dcap, counts, qv, damp.as<double>(), drss.as<double>(),
-                            den.as<double>(), dnu.as<int32_t>(), dch.as<int32_t>(), dpart.as<double>(),
-                            dsum.as<double>(), st)))
+    FitDev f;
+    if ((rc = spike_fit_rows(d_y, d_x, T, states, N, S, mu, K, qv, nchunks, first, mu_track, dt.as<int64_t>(), dcap,
+                             counts, f, st)))
         return rc;
     for (int64_t a = 0; a < N; a++) {
         const size_t n = (size_t)std::min(counts[a], cap);
         if (n == 0) continue;
-        if (amp) HS_HIP(hipMemcpyAsync(amp + a * cap, damp.as<double>() + a * dcap, n * 8, hipMemcpyDeviceToHost, st));
-        if (rss) HS_HIP(hipMemcpyAsync(rss + a * cap, drss.as<double>() + a * dcap, n * 8, hipMemcpyDeviceToHost, st));
+        if (amp) HS_HIP(hipMemcpyAsync(amp + a * cap, f.damp.as<double>() + a * dcap, n * 8, hipMemcpyDeviceToHost, st));
+        if (rss) HS_HIP(hipMemcpyAsync(rss + a * cap, f.drss.as<double>() + a * dcap, n * 8, hipMemcpyDeviceToHost, st));
         if (energy)
-            HS_HIP(hipMemcpyAsync(energy + a * cap, den.as<double>() + a * dcap, n * 8, hipMemcpyDeviceToHost, st));
+            HS_HIP(hipMemcpyAsync(energy + a * cap, f.den.as<double>() + a * dcap, n * 8, hipMemcpyDeviceToHost, st));
         if (nused)
-            HS_HIP(hipMemcpyAsync(nused + a * cap, dnu.as<int32_t>() + a * dcap, n * 4, hipMemcpyDeviceToHost, st));
+            HS_HIP(hipMemcpyAsync(nused + a * cap, f.dnu.as<int32_t>() + a * dcap, n * 4, hipMemcpyDeviceToHost, st));
     }
     std::vector<double> sum(summary ? N * L : 0);
-    if (summary) HS_HIP(hipMemcpyAsync(sum.data(), dsum.p, N * L * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (summary) HS_HIP(hipMemcpyAsync(sum.data(), f.dsum.p, N * L * sizeof(double), hipMemcpyDeviceToHost, st));
     HS_HIP(hipStreamSynchronize(st));
     for (int64_t i = 0; summary && i < N * L; i++)
         if (i % L != 7) summary[i] = sum[i];
@@ -265,18 +283,22 @@ int spike_fit_channel(const double *d_y, const int16_t *d_x, int64_t T, const in
 // hmmsort_plan_extract_spiketimes finds them and concatenated into dt in unit order u = ch N + a behind the host
 // offsets offs[0 .. U]; only the counts come to the host.  Shared by the calls that work on the units of a plan.  The
 // copies into dt are enqueued on st and read `rows`, so the record must outlive the caller's next synchronisation.
+// With the resident signal d_y, dv receives the amplitude of every event beside its time: hmmsort_plan_spike_fit's amp
+// under the plan's current model (spike_fit_rows; the caller has run spike_fit_check on every channel).
 struct PlanUnits {
     std::vector<DevBuf> rows;   // per channel: rows of dcap[ch] entries per template
-    DevBuf dt;
+    std::vector<FitDev> fits;   // per channel, with d_y
+    DevBuf dt, dv;
     std::vector<int64_t> offs;
 };
 
-int plan_compact_units(hmmsort_plan *p, const int16_t *d_x, hipStream_t st, PlanUnits *pu)
+int plan_compact_units(hmmsort_plan *p, const int16_t *d_x, hipStream_t st, PlanUnits *pu, const double *d_y = nullptr)
 {
     const int64_t N = p->model.N, nC = p->C, U = nC * N, T = p->T;
     int rc;
     std::vector<int64_t> dcap((size_t)nC, 1), &offs = pu->offs;
     pu->rows = std::vector<DevBuf>((size_t)nC);
+    pu->fits = std::vector<FitDev>(d_y ? (size_t)nC : 0);
     offs.assign((size_t)U + 1, 0);
     for (int64_t ch = 0; ch < nC; ch++) {
         const HostModel &m = nC > 1 ? p->models[ch] : p->model;
@@ -285,13 +307,24 @@ int plan_compact_units(hmmsort_plan *p, const int16_t *d_x, hipStream_t st, Plan
                                       &pu->rows[ch], &dcap[ch])))
             return rc;
         for (int64_t a = 0; a < N; a++) offs[ch * N + a + 1] = offs[ch * N + a] + counts[a];
+        if (d_y && offs[ch * N + N] > offs[ch * N]) {
+            int32_t qv[32];
+            for (int64_t a = 0; a < N; a++) qv[a] = trough_value(m.mu.data(), m.K, a);
+            if ((rc = spike_fit_rows(d_y + ch * T, d_x + ch * T, T, m.states.data(), N, m.S, m.mu.data(), m.K, qv, 0,
+                                     nullptr, nullptr, pu->rows[ch].as<int64_t>(), dcap[ch], counts, pu->fits[ch], st)))
+                return rc;
+        }
     }
     if ((rc = pu->dt.alloc((size_t)offs[U] * sizeof(int64_t)))) return rc;
+    if (d_y && (rc = pu->dv.alloc((size_t)offs[U] * sizeof(double)))) return rc;
     for (int64_t u = 0; u < U; u++) {
         const int64_t n = offs[u + 1] - offs[u], ch = u / N, a = u % N;
         if (n > 0)
             HS_HIP(hipMemcpyAsync(pu->dt.as<int64_t>() + offs[u], pu->rows[ch].as<int64_t>() + a * dcap[ch],
                                   (size_t)n * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+        if (n > 0 && d_y)
+            HS_HIP(hipMemcpyAsync(pu->dv.as<double>() + offs[u], pu->fits[ch].damp.as<double>() + a * dcap[ch],
+                                  (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
     }
     return HMMSORT_OK;
 }
@@ -833,6 +866,84 @@ int hmmsort_cluster_isolation(const double *feat, int64_t n, int64_t F, int64_t 
     }
     return dev_cluster_isolation(df.as<double>(), n, F, U, offs, used ? du.as<unsigned char>() : nullptr, mu, Vinv,
                                  scored, out, nullptr);
+}
+
+// ---- unit stability (stability.hip) -----------------------------------------------------------------
+
+int hmmsort_unit_stability_device(int64_t U, const int64_t *d_times, const double *d_values, const int64_t *offs,
+                                  const hmmsort_stab_opt *opt, hmmsort_stab_out *out, void *stream)
+{
+    HS_CHECK(offs, HMMSORT_EINVAL, "unit_stability_device: null argument (offs is required)");
+    int64_t B;
+    int rc = stab_check("unit_stability_device", U, opt, out, &B);
+    if (rc) return rc;
+    HS_CHECK(offs[0] >= 0, HMMSORT_EINVAL, "unit_stability_device: offs[0] = %lld", (long long)offs[0]);
+    for (int64_t u = 0; u < U; u++)
+        HS_CHECK(offs[u + 1] >= offs[u], HMMSORT_EINVAL, "unit_stability_device: offs: unit %lld has a count of %lld",
+                 (long long)u, (long long)(offs[u + 1] - offs[u]));
+    HS_CHECK(d_times || offs[U] == offs[0], HMMSORT_EINVAL, "unit_stability_device: null d_times");
+    HS_CHECK(offs[U] - offs[0] < (1ll << 31), HMMSORT_EUNSUP, "unit_stability_device: %lld spikes in all (below 2^31)",
+             (long long)(offs[U] - offs[0]));
+    if ((rc = need_device())) return rc;
+    return dev_unit_stability(U, d_times, d_values, offs, opt, out, B, (hipStream_t)stream);
+}
+
+int hmmsort_unit_stability(int64_t U, const int64_t *const *times, const double *const *values, const int64_t *counts,
+                           const hmmsort_stab_opt *opt, hmmsort_stab_out *out)
+{
+    HS_CHECK(times && counts, HMMSORT_EINVAL, "unit_stability: null argument (times and counts are required)");
+    int64_t B;
+    int rc = stab_check("unit_stability", U, opt, out, &B);
+    if (rc) return rc;
+    std::vector<int64_t> offs;
+    if ((rc = check_unit_lists("unit_stability", U, times, counts, offs))) return rc;
+    for (int64_t u = 0; u < U; u++) {
+        HS_CHECK(counts[u] == 0 || times[u][counts[u] - 1] <= opt->T, HMMSORT_EINVAL, "unit_stability: times: unit %lld: "
+                 "time %lld outside 1..T = %lld", (long long)u, (long long)times[u][counts[u] - 1], (long long)opt->T);
+        HS_CHECK(!values || counts[u] == 0 || values[u], HMMSORT_EINVAL, "unit_stability: values: unit %lld has a null "
+                 "list of %lld values", (long long)u, (long long)counts[u]);
+    }
+    HS_CHECK(offs[(size_t)U] < (1ll << 31), HMMSORT_EUNSUP, "unit_stability: %lld spikes in all (below 2^31)",
+             (long long)offs[(size_t)U]);
+    if ((rc = need_device())) return rc;
+    DevBuf dt, dv;
+    if ((rc = upload_unit_lists(U, times, counts, offs, dt))) return rc;
+    if (values) {
+        if ((rc = dv.alloc((size_t)offs[(size_t)U] * sizeof(double)))) return rc;
+        for (int64_t u = 0; u < U; u++)
+            if (counts[u] > 0)
+                HS_HIP(hipMemcpy(dv.as<double>() + offs[u], values[u], (size_t)counts[u] * sizeof(double),
+                                 hipMemcpyHostToDevice));
+    }
+    return dev_unit_stability(U, dt.as<int64_t>(), values ? dv.as<double>() : nullptr, offs.data(), opt, out, B, nullptr);
+}
+
+int hmmsort_plan_unit_stability(hmmsort_plan *p, const double *d_y, const int16_t *d_x, const hmmsort_stab_opt *opt,
+                                hmmsort_stab_out *out, void *stream)
+{
+    HS_CHECK(p && d_y && d_x, HMMSORT_EINVAL, "plan_unit_stability: null argument (the plan, d_y and d_x are required)");
+    const int64_t N = p->model.N, U = p->C * N;
+    HS_CHECK(N <= 32, HMMSORT_EINVAL, "plan_unit_stability: more than 32 templates");
+    int64_t B;
+    int rc = stab_check("plan_unit_stability", U, opt, out, &B);
+    if (rc) return rc;
+    HS_CHECK(opt->T == p->T, HMMSORT_EINVAL, "plan_unit_stability: T = %lld, the plan has %lld samples",
+             (long long)opt->T, (long long)p->T);
+    hmmsort_spike_fit_out none = {};
+    int32_t qv[32];
+    for (int64_t ch = 0; ch < p->C; ch++) {
+        const HostModel &m = p->C > 1 ? p->models[ch] : p->model;
+        if ((rc = spike_fit_check("plan_unit_stability", N, m.S, m.mu.data(), m.K, 0, nullptr, nullptr, &none, qv)))
+            return rc;
+    }
+    if ((rc = need_device())) return rc;
+    PlanUnits pu;
+    if ((rc = plan_compact_units(p, d_x, (hipStream_t)stream, &pu, d_y))) {
+        (void)hipStreamSynchronize((hipStream_t)stream);   // the compaction's copies read `pu`
+        return rc;
+    }
+    return dev_unit_stability(U, pu.dt.as<int64_t>(), pu.dv.as<double>(), pu.offs.data(), opt, out, B,
+                              (hipStream_t)stream);
 }
 
 }  // extern "C"

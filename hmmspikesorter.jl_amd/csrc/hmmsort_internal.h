@@ -373,6 +373,13 @@ int iso_check(const char *who, int64_t n, int64_t F, int64_t U, const int64_t *o
 int dev_cluster_isolation(const double *d_feat, int64_t n, int64_t F, int64_t U, const int64_t *offs,
                           const unsigned char *d_used, const double *mu, const double *vinv,
                           const std::vector<unsigned char> &scored, const hmmsort_iso_out *out, hipStream_t st);
+// unit stability (stability.hip; rules in include/hmmsort.h).  stab_check is what the three entry points refuse about U,
+// the options and the output record before any GPU work (*B: the time bins).  dev_unit_stability takes the U lists of
+// times and values (d_vals null: counts only) concatenated in device memory behind the host offsets, as
+// dev_correlograms does, fills the caller's host arrays and synchronises st.
+int stab_check(const char *who, int64_t U, const hmmsort_stab_opt *opt, const hmmsort_stab_out *out, int64_t *B);
+int dev_unit_stability(int64_t U, const int64_t *d_times, const double *d_vals, const int64_t *offs,
+                       const hmmsort_stab_opt *opt, const hmmsort_stab_out *out, int64_t B, hipStream_t st);
 
 }  // namespace hmmsort
 

@@ -269,6 +269,30 @@ def cluster_isolation(d_block, d_times, offs, pre=20, W=60, channels=None, P=3, 
         d_block, d_times, offs, pre, W, channels, basis, centre, moments, features, stream), P, keep_features)
 
 
+def unit_stability(d_times, offs, d_values=None, T=None, bin=None, quantiles=(1 / 4, 1 / 2, 3 / 4), hist=None,
+                   stream=None):
+    """api.unit_stability for spike lists and values that are already resident (hmmsort_unit_stability_device):
+    d_times one int64 device tensor holding the U lists one after the other, d_values a float64 device tensor laid out
+    the same way (None: counts only), offs the U + 1 host offsets.  Returns api.UnitStability; only the tables cross to
+    the host.  The call synchronises `stream` (default torch's current one)."""
+    from .api import _stab_run
+    if T is None or bin is None:
+        raise ValueError("unit_stability: T and bin are required")
+    offs = np.ascontiguousarray(offs, dtype=np.int64).ravel()
+    U = len(offs) - 1
+    if d_times.element_size() != 8 or d_times.is_floating_point() or not d_times.is_contiguous():
+        raise TypeError("unit_stability: d_times must be a contiguous int64 device tensor")
+    if d_values is not None and not (d_values.is_floating_point() and d_values.element_size() == 8
+                                     and d_values.is_contiguous()):
+        raise TypeError("unit_stability: d_values must be a contiguous float64 device tensor")
+    for name, t in (("d_times", d_times), ("d_values", d_values)):
+        if t is not None and U >= 1 and int(offs[-1]) > int(t.numel()):
+            raise ValueError("unit_stability: offs ends at %d, %s has %d entries" % (offs[-1], name, t.numel()))
+    return _stab_run(lambda opt, out: lib().hmmsort_unit_stability_device(
+        U, _dptr(d_times), _dptr(d_values), ptr(offs), opt, out, _stream(stream)), U, T, bin, quantiles, hist,
+        d_values is not None)
+
+
 class Plan:
     """One recording channel of length T with a fixed model shape."""
 
@@ -526,6 +550,17 @@ class Plan:
         """api.Isolation of the plan's units on the resident block: device.cluster_isolation on the plan form."""
         return _isolation_from(lambda basis, centre, moments, features: self.snippet_features(
             d_x, d_block, pre, W, channels, basis, centre, moments, features, stream), P, keep_features)
+
+    def unit_stability(self, d_y, d_x, bin, quantiles=(1 / 4, 1 / 2, 3 / 4), hist=None, stream=0):
+        """api.UnitStability of the events extract_spiketimes reports on the resident path(s) d_x of the resident
+        signal(s) d_y under the plan's current model, with spike_fit's amplitude as the value of every event
+        (hmmsort_plan_unit_stability): units are u = channel * N + template.  Events and amplitudes stay on the
+        device; only the tables cross."""
+        from .api import _stab_run
+        U = getattr(self, "C", 1) * self.N
+        return _stab_run(lambda opt, out: lib().hmmsort_plan_unit_stability(self._h, _dptr(d_y), _dptr(d_x), opt, out,
+                                                                            C.c_void_p(stream)),
+                         U, self.T, bin, quantiles, hist, True)
 
     def expected_counts(self, stream=0):
         """expected number of spikes per template, sum_t onset[a, t] ([C][N]; [N] for a single-channel plan)"""

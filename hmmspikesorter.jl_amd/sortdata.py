@@ -152,7 +152,7 @@ def front_end_block(data, preprocess, info=None):
 
 def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_templates=4,
               chunksize=100_000, confidence=False, jitter=2, refine_steps=0, adapt_halflife=None, quality=False,
-              correlograms=None, preprocess=None, channel=0, footprints=None, isolation=None):
+              correlograms=None, preprocess=None, channel=0, footprints=None, isolation=None, stability=None):
     """sort_data(inputfile, datafile, outputfile; dosave, max_templates)   hmmsort.jl:36-104.
 
     Returns the reference's output dictionary; {} when there are more templates than
@@ -205,7 +205,15 @@ def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_temp
     `isolation=True` or dict(pre=, W=, P=, channels=) (an extension; default None, output unchanged) adds
     "unit_isolation": per-template "distance" (isolation distance), "l_ratio", "n_used" and the templates x templates
     "lpair" and "closer" of api.cluster_isolation on the stitched path -- measured on every channel (or `channels`) of
-    the preprocessed block, kept on the device, when `preprocess` is given, else on the sorted channel alone."""
+    the preprocessed block, kept on the device, when `preprocess` is given, else on the sorted channel alone.
+
+    `stability=True` or dict(bin=, quantiles=, hist=) (an extension; default None, output unchanged) adds
+    "unit_stability": the tables of api.unit_stability on the stitched path's events with api.spike_fit's amplitudes as
+    values ("count", "valid", "quant", "sum", "sumsq", "uvalid", "uquant", "umin", "umax", "usum", "usumsq", "hist",
+    "under", "over"), "bin" (samples per time bin; default a hundredth of the recording, rounded up), "quantiles" and
+    the per-template "presence_ratio", "amplitude_drift" (when 1/2 is among the quantiles) and "amplitude_cutoff"
+    (with a histogram; default 512 bins over 0..4 template amplitudes).  With `adapt_halflife` every spike is measured
+    against the templates its chunk was decoded with."""
     want_fp = footprints is not None and footprints is not False
     want_iso = isolation is not None and isolation is not False
     if want_fp and preprocess is None:
@@ -298,6 +306,20 @@ def sort_data(spike_forms, cinv, p, data, outputfile=None, dosave=True, max_temp
         iso = device.cluster_isolation(d_iso, d_times, offs, **({} if isolation is True else dict(isolation)))
         out["unit_isolation"] = {"distance": iso.distance, "l_ratio": iso.l_ratio, "lpair": iso.lpair,
                                  "closer": iso.closer, "n_used": iso.n_used}
+    if stability is not None and stability is not False:
+        so = dict(bin=max(1, -(-len(dataf) // 100)), quantiles=(1 / 4, 1 / 2, 3 / 4), hist=(512, 0.0, 4.0))
+        so.update({} if stability is True else dict(stability))
+        fits = api.spike_fit(modelf, track)
+        us = api.unit_stability([f.times for f in fits], [f.amp for f in fits], T=len(dataf), **so)
+        d = {k: getattr(us, k) for k in ("count", "valid", "quant", "sum", "sumsq", "uvalid", "uquant", "umin", "umax",
+                                         "usum", "usumsq", "hist", "under", "over")}
+        d["bin"], d["quantiles"] = us.bin, np.array(us.q_num, dtype=np.float64) / us.q_den
+        d["presence_ratio"] = us.presence_ratio()
+        if any(2 * q == us.q_den for q in us.q_num):
+            d["amplitude_drift"] = us.amplitude_drift()
+        if so["hist"] is not None:
+            d["amplitude_cutoff"] = us.amplitude_cutoff()
+        out["unit_stability"] = d
     if dosave and outputfile is not None:
         from scipy.io import savemat
         savemat(outputfile, out)                                              # MAT.matwrite :100
@@ -387,6 +409,11 @@ def main(argv=None):
                     help="local whitening: each channel against its M nearest by channel index (default: all)")
     ap.add_argument("--isolation", action="store_true",
                     help="add unit_isolation (isolation distance, L-ratio) of the sorted templates to the output")
+    ap.add_argument("--stability", action="store_true",
+                    help="add unit_stability (counts and amplitude quantiles per time bin, presence ratio, amplitude "
+                         "drift and cutoff) of the sorted templates to the output")
+    ap.add_argument("--stability-bin", type=int, metavar="N",
+                    help="samples per time bin of --stability (default: a hundredth of the recording)")
     a = ap.parse_args(argv)
     pre = None
     if a.highpass is not None or a.lowpass is not None or a.reference is not None or a.channel != 0 or a.whiten:
@@ -411,7 +438,8 @@ def main(argv=None):
     if data is None:
         data = load_data(a.datafile, a.dataname)
     out = sort_data(*t, data, a.outfile, max_templates=a.max_templates, preprocess=pre, channel=a.channel,
-                    isolation=True if a.isolation else None)
+                    isolation=True if a.isolation else None,
+                    stability=(dict(bin=a.stability_bin) if a.stability_bin else True) if a.stability else None)
     print("Done! Results saved to %s" % a.outfile if out else "Too many templates. Bailing out...")
     return 0
 

@@ -942,6 +942,87 @@ int hmmsort_cluster_isolation_device(const double *d_feat, int64_t n, int64_t F,
                                      const unsigned char *d_used, const double *mu, const double *Vinv,
                                      hmmsort_iso_out *out, void *stream);
 
+/* Unit stability over time (an extension): was the unit there the whole time?  Spike counts per unit and
+ * time bin, and of one fp64 value per spike (its amplitude, usually) exact order statistics, sums and a histogram, per
+ * unit and time bin and per unit over the whole recording -- what firing rate per bin, presence ratio, amplitude drift
+ * and amplitude cutoff rest on (api.UnitStability has those finishers).  Every result is a fixed function of the input
+ * that tests/stability_model.py reproduces bit for bit: no interpolation, no fused multiply-add, no floating-point
+ * atomics, no matrix-core instructions.  All indices 0-based except spike times.
+ *   units     u = 0..U-1; unit u has n_u >= 0 spike times, 1-based samples, strictly ascending, each in 1..T, and, when
+ *             values are given, one fp64 value per spike.  A NaN value means "no value": it is not valid and takes no
+ *             part in order statistics, sums or histogram.  values == NULL: only n and count are written.
+ *   options   T the recording length; bin >= 1 samples per time bin, B = ceil(T / bin), bin b holds the times with
+ *             (t - 1) / bin == b in integer division, the last bin may be short.  nq <= HMMSORT_STAB_MAX_Q quantiles
+ *             q_num[k] / q_den with 0 <= q_num[k] <= q_den <= HMMSORT_STAB_MAX_QDEN.  A histogram of HB >= 0 bins.
+ *   segment   (u, b): the spikes of unit u in bin b, a contiguous range of its list; (u): all of them.
+ *   order     of values: that of the bit patterns mapped monotonically, -Inf < ... < -0.0 < +0.0 < ... < +Inf.
+ *   quantile  k of a segment with m valid values: the order statistic of 0-based rank floor(q_num[k] (m - 1) / q_den),
+ *             in 64-bit integers (q_num <= 2^20 and m < 2^31, so the product stays below 2^51).  The result is one of
+ *             the inputs, bit for bit; ties between equal patterns cannot change it.  NaN when m == 0.
+ *   sums      sum and sumsq of a segment (u, b): its valid values in ascending event order are cut into tiles of 256;
+ *             within a tile a serial fold from +0.0: ps = ps + v; pq = pq + v * v, the square rounded on its own; the
+ *             tile partials are folded serially from +0.0 in tile order.  usum[u] / usumsq[u] fold sum[u][.] /
+ *             sumsq[u][.] serially from +0.0 in bin order (the bin sums, not the events again).
+ *   histogram of unit u over its valid values: p = (v - hist_lo) * hist_scale, the subtraction and the product rounded
+ *             separately; p < 0 counts in under[u], p >= HB in over[u], else hist[u][floor(p)].
+ *   outputs   host arrays, any of them except n may be NULL: n[U]; count[U][B], valid[U][B] int64; quant[U][B][nq];
+ *             sum[U][B], sumsq[U][B]; uvalid[U]; uquant[U][nq]; umin[U], umax[U] (ranks 0 and m - 1, NaN when there is
+ *             no valid value); usum[U], usumsq[U]; hist[U][HB], under[U], over[U] int64.
+ *   refused   before any GPU work, every output untouched, the message names the argument.  HMMSORT_EINVAL: a null
+ *             required pointer, U outside 1..HMMSORT_STAB_MAX_UNITS, T outside 1..2^40, bin < 1, nq outside
+ *             0..HMMSORT_STAB_MAX_Q, q_den outside 1..HMMSORT_STAB_MAX_QDEN, a q_num outside 0..q_den, HB outside
+ *             0..HMMSORT_STAB_MAX_HIST, with HB > 0 a hist_scale that is not finite and positive or a hist_lo that is
+ *             not finite, a negative count, a time outside 1..T, a list that is not strictly ascending, a unit with
+ *             spikes and a null values[u] beside a non-null values.  HMMSORT_EUNSUP, naming the number: B or U B above
+ *             HMMSORT_STAB_MAX_BINS (so quant stays below 2^28 entries), 2^31 spikes or more in all.
+ *   forms     hmmsort_unit_stability: host lists, times[u] and values[u] host pointers (NULL allowed for an empty
+ *             unit); uploads once, no plan is involved.
+ *             hmmsort_unit_stability_device: d_times and d_values (or NULL) hold the U lists one after the other in
+ *             device memory behind U + 1 host offsets (offs[0] >= 0, ascending), as hmmsort_footprints_device takes
+ *             them.  The times cannot be checked before the GPU runs: a time below 1 counts in bin 0, one beyond T in
+ *             the last bin, and a list whose bin boundaries step back is refused after the search (HMMSORT_EINVAL, n
+ *             already written); nothing outside [offs[0], offs[U]) is read.  Synchronises the stream.
+ *             hmmsort_plan_unit_stability: units u = ch N + a of the resident path(s) d_x of a plan ([C][T] for a
+ *             batched plan), exactly the events of hmmsort_plan_extract_spiketimes; the value of an event is the amp of
+ *             hmmsort_plan_spike_fit under the plan's current model (no track), computed by the same code.  opt->T must
+ *             be the plan's T.  Neither events nor amplitudes come to the host.  Any engine.  Synchronises the
+ *             stream. */
+#define HMMSORT_STAB_MAX_UNITS 4096
+#define HMMSORT_STAB_MAX_Q 8
+#define HMMSORT_STAB_MAX_QDEN (1ll << 20)
+#define HMMSORT_STAB_MAX_HIST 4096
+#define HMMSORT_STAB_MAX_BINS (1ll << 24)
+typedef struct hmmsort_stab_opt {
+    int64_t T;            /* recording length in samples */
+    int64_t bin;          /* samples per time bin */
+    int64_t nq;           /* quantiles */
+    int64_t q_num[HMMSORT_STAB_MAX_Q];
+    int64_t q_den;
+    int64_t HB;           /* histogram bins, 0: none */
+    double hist_lo;       /* left edge of histogram bin 0 */
+    double hist_scale;    /* 1 / bin width */
+} hmmsort_stab_opt;
+typedef struct hmmsort_stab_out {
+    int64_t *n;           /* [U], required */
+    int64_t *count;       /* [U][B] */
+    int64_t *valid;       /* [U][B] */
+    double *quant;        /* [U][B][nq] */
+    double *sum, *sumsq;  /* [U][B] */
+    int64_t *uvalid;      /* [U] */
+    double *uquant;       /* [U][nq] */
+    double *umin, *umax;  /* [U] */
+    double *usum, *usumsq; /* [U] */
+    int64_t *hist;        /* [U][HB] */
+    int64_t *under, *over; /* [U] */
+} hmmsort_stab_out;
+int hmmsort_unit_stability(int64_t U, const int64_t *const *times, const double *const *values /* may be NULL */,
+                           const int64_t *counts, const hmmsort_stab_opt *opt, hmmsort_stab_out *out);
+int hmmsort_unit_stability_device(int64_t U, const int64_t *d_times, const double *d_values /* may be NULL */,
+                                  const int64_t *offs, const hmmsort_stab_opt *opt, hmmsort_stab_out *out,
+                                  void *stream);
+int hmmsort_plan_unit_stability(hmmsort_plan *plan, const double *d_y, const int16_t *d_x, const hmmsort_stab_opt *opt,
+                                hmmsort_stab_out *out, void *stream);
+
 /* Spatial whitening (an extension): the noise covariance of the quiet samples of a block, and a mix of
  * its channels, on the fp64 channel-major block [C][T] that hmmsort_preprocess_device writes.  The C x C matrix itself
  * (ZCA, global or local) is the host's work: api.whitening_matrix.  All indices 0-based.  No floating-point atomics,

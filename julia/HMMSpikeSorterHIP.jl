@@ -707,6 +707,87 @@ function cluster_isolation_device(d_feat::Ptr{Float64}, n::Integer, F::Integer, 
     (iso_d2=d2, closer=closer, lpair=lpair)
 end
 
+# struct hmmsort_stab_opt / hmmsort_stab_out (include/hmmsort.h)
+struct CStabOpt
+    T::Int64; bin::Int64; nq::Int64; q_num::NTuple{8,Int64}; q_den::Int64; HB::Int64; hist_lo::Float64; hist_scale::Float64
+end
+struct CStabOut
+    n::Ptr{Int64}; count::Ptr{Int64}; valid::Ptr{Int64}; quant::Ptr{Float64}; sum::Ptr{Float64}; sumsq::Ptr{Float64}
+    uvalid::Ptr{Int64}; uquant::Ptr{Float64}; umin::Ptr{Float64}; umax::Ptr{Float64}; usum::Ptr{Float64}
+    usumsq::Ptr{Float64}; hist::Ptr{Int64}; under::Ptr{Int64}; over::Ptr{Int64}
+end
+
+# call(opt::Ref{CStabOpt}, out::Ref{CStabOut}) -> code, into a named tuple of the tables; arrays are column-major, so
+# count is B × U, quant nq × B × U, hist HB × U.  `quantiles` are exact rationals (q_num = q .* q_den), `hist` is
+# nothing or (bins, lo, scale)
+function _stab_run(call, U, n, bin, quantiles::Vector{<:Rational}, hist)
+    nq = length(quantiles); nq <= 8 || error("unit_stability: at most 8 quantiles")
+    q_den = nq == 0 ? 1 : lcm(denominator.(quantiles)...)
+    q_num = ntuple(k -> k <= nq ? Int64(numerator(quantiles[k]) * (q_den ÷ denominator(quantiles[k]))) : Int64(0), 8)
+    HB, lo, scale = hist === nothing ? (0, 0.0, 1.0) : hist
+    B = cld(n, bin)
+    cnt = zeros(Int64, B, U); valid = zeros(Int64, B, U); quant = zeros(Float64, nq, B, U)
+    s = zeros(Float64, B, U); q = zeros(Float64, B, U); nn = zeros(Int64, U); uvalid = zeros(Int64, U)
+    uquant = zeros(Float64, nq, U); umin = zeros(Float64, U); umax = zeros(Float64, U); usum = zeros(Float64, U)
+    usumsq = zeros(Float64, U); h = zeros(Int64, HB, U); under = zeros(Int64, U); over = zeros(Int64, U)
+    GC.@preserve cnt valid quant s q nn uvalid uquant umin umax usum usumsq h under over begin
+        check(call(Ref(CStabOpt(n, bin, nq, q_num, q_den, HB, lo, scale)),
+                   Ref(CStabOut(pointer(nn), pointer(cnt), pointer(valid), pointer(quant), pointer(s), pointer(q),
+                                pointer(uvalid), pointer(uquant), pointer(umin), pointer(umax), pointer(usum),
+                                pointer(usumsq), pointer(h), pointer(under), pointer(over)))))
+    end
+    (n=nn, count=cnt, valid=valid, quant=quant, sum=s, sumsq=q, uvalid=uvalid, uquant=uquant, umin=umin, umax=umax,
+     usum=usum, usumsq=usumsq, hist=h, under=under, over=over)
+end
+
+"""
+    unit_stability(times, values, n; bin, quantiles=[1//4, 1//2, 3//4], hist=nothing) -> named tuple of tables
+
+Spike counts per unit and time bin of `bin` samples of a recording of `n` samples and, of one Float64 value per spike
+(NaN: no value), exact order statistics, sums and a histogram per unit and bin and per unit (`hmmsort_unit_stability`; an
+extension, INTEGRATION.md "Stability").  `times` is one ascending vector of 1-based spike times per unit, `values` one
+vector per unit of the same lengths or `nothing` for the counts alone (the other tables then stay zero).  A quantile is
+the value of rank `floor(q (m - 1))` among the `m` values of a bin, never interpolated.
+"""
+function unit_stability(times::Vector{Vector{Int64}}, values::Union{Nothing,Vector{Vector{Float64}}}, n::Integer;
+                        bin::Integer, quantiles::Vector{<:Rational}=[1//4, 1//2, 3//4], hist=nothing)
+    U = length(times)
+    ptrs = [isempty(t) ? Ptr{Int64}(C_NULL) : pointer(t) for t in times]; counts = Int64.(length.(times))
+    vptrs = values === nothing ? Ptr{Float64}[] : [isempty(v) ? Ptr{Float64}(C_NULL) : pointer(v) for v in values]
+    GC.@preserve times values ptrs vptrs counts begin
+        _stab_run(U, n, bin, quantiles, hist) do opt, out
+            ccall((:hmmsort_unit_stability, lib), Cint,
+                (Int64, Ptr{Ptr{Int64}}, Ptr{Ptr{Float64}}, Ptr{Int64}, Ref{CStabOpt}, Ref{CStabOut}),
+                U, ptrs, values === nothing ? C_NULL : vptrs, counts, opt, out)
+        end
+    end
+end
+
+"`unit_stability` of spike lists and values concatenated in device memory behind the `U + 1` host offsets `offs` (`hmmsort_unit_stability_device`; `d_values` may be `C_NULL`); synchronises `stream`"
+function unit_stability_device(d_times::Ptr{Int64}, d_values::Ptr{Float64}, offs::Vector{Int64}, n::Integer;
+                               bin::Integer, quantiles::Vector{<:Rational}=[1//4, 1//2, 3//4], hist=nothing,
+                               stream::Ptr{Cvoid}=C_NULL)
+    U = length(offs) - 1
+    GC.@preserve offs begin
+        _stab_run(U, n, bin, quantiles, hist) do opt, out
+            ccall((:hmmsort_unit_stability_device, lib), Cint,
+                (Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}, Ref{CStabOpt}, Ref{CStabOut}, Ptr{Cvoid}),
+                U, d_times, d_values, offs, opt, out, stream)
+        end
+    end
+end
+
+"`unit_stability` of the units `u = ch N + a` a plan finds on its resident path(s) `d_x`, with the amplitude `hmmsort_plan_spike_fit` gives every event on the resident signal(s) `d_y` as its value (`hmmsort_plan_unit_stability`); `n` is the plan's length, `U` its channels × templates; synchronises `stream`"
+function unit_stability_plan(plan::Ptr{Cvoid}, d_y::Ptr{Float64}, d_x::Ptr{Int16}, n::Integer, U::Integer;
+                             bin::Integer, quantiles::Vector{<:Rational}=[1//4, 1//2, 3//4], hist=nothing,
+                             stream::Ptr{Cvoid}=C_NULL)
+    _stab_run(U, n, bin, quantiles, hist) do opt, out
+        ccall((:hmmsort_plan_unit_stability, lib), Cint,
+            (Ptr{Cvoid}, Ptr{Float64}, Ptr{Int16}, Ref{CStabOpt}, Ref{CStabOut}, Ptr{Cvoid}),
+            plan, d_y, d_x, opt, out, stream)
+    end
+end
+
 function reconstruct_signal(x::Array{T,1}, lA::StateMatrix, μ::Array{Float64,2}, σ::Float64) where T <: Integer
     xs = T === Int16 ? x : Int16.(x)
     Y2 = zeros(Float64, length(xs))
